@@ -33,6 +33,10 @@ chromosome: equal (qry_str, qry_end) keys and tied path scores, the multi-mappin
 its phase times and its ratio to the uniform step; `e2e` (the `alignasm` command line on the C3 file
 with cs tags: stage seconds and file bytes; skipped with --no-e2e).
 
+--dump-outputs DIR: what the last timed step computed for rank 0's contigs (DeviceResult.fetch(): main / alt / all records,
+their offsets, a per-contig table of status and counts) as DIR/<name>.npy in float64, at most 64 MB in all (a seeded
+sample of contigs when larger; see dump_outputs).  The inputs are seeded, so two builds run with the same arguments can be compared array by array.
+
 roofline: the dominant kernel of the timed region (largest average HIP-event time on the
 library's stream), its ALGORITHMIC bytes per launch (byte model: DESIGN.md "Byte model")
 and the HBM peak of /opt/skills/guides/MI355X_MICROARCH.md (8 TB/s).  `traffic` (PMC
@@ -46,6 +50,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -100,25 +106,102 @@ def merge_stats(acc, st):
     return acc
 
 
-def timed_steps(dbs, K, steps, barrier):
-    """steps x (every resident piece of this rank once); returns (elapsed seconds, summed phase times, stats of the last step)."""
+def timed_steps(dbs, K, steps, barrier, keep=None):
+    """steps x (every resident piece of this rank once); returns (elapsed seconds, summed phase times, stats of the last step).
+    keep: a list that receives the fetched outputs of every piece of the LAST step (the fetch is taken out of the elapsed time)."""
     if not isinstance(dbs, (list, tuple)):
         dbs = [dbs]
     phase_acc, stats = {}, None
+    fetch_s = 0.0
     barrier()
     t_begin = time.perf_counter()
-    for _ in range(steps):
+    for step in range(steps):
         stats = None
         for db in dbs:
             res = db.solve(max_paths=K, timing=True)      # enqueues the pipeline and syncs its stream
             st = res.stats()
+            if keep is not None and step == steps - 1:
+                t_fetch = time.perf_counter()
+                keep.append(res.fetch())
+                fetch_s += time.perf_counter() - t_fetch
             res.close()
             for k, v in st["phase_ms"].items():
                 phase_acc[k] = phase_acc.get(k, 0.0) + v
             stats = merge_stats(stats, st)
-    elapsed = time.perf_counter() - t_begin
+    elapsed = time.perf_counter() - t_begin - fetch_s
     barrier()
     return elapsed, phase_acc, stats
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6          # the files on disk, .npy headers included
+DUMP_SAMPLE_SEED = 12345
+REC_FIELDS = ("qs", "qe", "rs", "re", "ctg_index", "is_alt")
+
+
+def concat_outputs(outs):
+    """The fetched outputs of consecutive pieces of one file as one output (offsets shifted, contigs in file order)."""
+    if len(outs) == 1:
+        return outs[0]
+    cat = {"n_contigs": sum(o["n_contigs"] for o in outs)}
+    for key in ("main", "alt", "all", "status"):
+        cat[key] = np.concatenate([o[key] for o in outs])
+    for off, base in (("main_off", "main"), ("alt_off", "alt"), ("all_path_off", None), ("all_elem_off", "all")):
+        parts, shift = [np.zeros(1, np.int64)], 0
+        for o in outs:
+            parts.append(o[off][1:] + shift)
+            shift += len(o[base]) if base else len(o["all_elem_off"]) - 1
+        cat[off] = np.concatenate(parts)
+    return cat
+
+
+def records_f64(rec):
+    """Structured output records -> float64 [n, 6] (qs, qe, rs, re, ctg_index, is_alt); exact, the values are far below 2**53."""
+    a = np.stack([rec[f].astype(np.int64) for f in REC_FIELDS], axis=1) if len(rec) else np.zeros((0, len(REC_FIELDS)), np.int64)
+    assert a.size == 0 or int(np.abs(a).max()) < (1 << 53), "output value not exact in float64"
+    return a.astype(np.float64)
+
+
+def dump_outputs(out, path, limit=DUMP_LIMIT_BYTES):
+    """What a caller of the timed path receives (DeviceResult.fetch()) as DIR/<name>.npy, float64.
+    Every contig: contig_table [n_contigs, 4] = (status, main records, alt records, all-paths) - one table, as the status column
+    alone is all zero on a batch that solves cleanly.  The records themselves (main, alt, all, with
+    their offsets rebased to the dumped contigs): every contig when they fit in `limit` bytes, else the contigs of a fixed
+    seeded permutation, taken in that order while they fit and written in file order (contigs.npy names them)."""
+    nc = out["n_contigs"]
+    mo, ao, po, eo = out["main_off"], out["alt_off"], out["all_path_off"], out["all_elem_off"]
+    contig_table = np.stack([out["status"].astype(np.int64), np.diff(mo), np.diff(ao), np.diff(po)], axis=1)
+    row = 8 * len(REC_FIELDS)
+    cost = row * (np.diff(mo) + np.diff(ao) + (eo[po[1:]] - eo[po[:-1]])) + 8 * (4 + np.diff(po))     # bytes of a contig's rows + offsets
+    budget = limit - 8 * (5 * nc + 5) - 12 * 256                  # per-contig arrays, offset ends, .npy headers
+    if int(cost.sum()) <= budget:
+        pick = np.arange(nc)
+    else:
+        order = np.random.default_rng(DUMP_SAMPLE_SEED).permutation(nc)
+        fits = np.cumsum(cost[order]) <= budget
+        pick = np.sort(order[:int(np.argmin(fits)) if not fits.all() else nc])
+    main_rows = np.concatenate([np.arange(mo[c], mo[c + 1]) for c in pick]) if len(pick) else np.zeros(0, np.int64)
+    alt_rows = np.concatenate([np.arange(ao[c], ao[c + 1]) for c in pick]) if len(pick) else np.zeros(0, np.int64)
+    paths = np.concatenate([np.arange(po[c], po[c + 1]) for c in pick]) if len(pick) else np.zeros(0, np.int64)
+    all_rows = np.concatenate([np.arange(eo[p], eo[p + 1]) for p in paths]) if len(paths) else np.zeros(0, np.int64)
+    arrays = {
+        "contig_table": contig_table,
+        "contigs": pick,
+        "main": records_f64(out["main"][main_rows]),
+        "main_off": np.concatenate([[0], np.cumsum(np.diff(mo)[pick])]),
+        "alt": records_f64(out["alt"][alt_rows]),
+        "alt_off": np.concatenate([[0], np.cumsum(np.diff(ao)[pick])]),
+        "all": records_f64(out["all"][all_rows]),
+        "all_path_off": np.concatenate([[0], np.cumsum(np.diff(po)[pick])]),
+        "all_elem_off": np.concatenate([[0], np.cumsum(np.diff(eo)[paths])]),
+    }
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        f = os.path.join(path, name + ".npy")
+        np.save(f, np.ascontiguousarray(a, dtype=np.float64))
+        total += os.path.getsize(f)
+    assert total <= limit, total
+    return {"dir": path, "contigs_dumped": int(len(pick)), "contigs": int(nc), "bytes": int(total)}
 
 
 def library_identity(A):
@@ -145,7 +228,11 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=5000, help="contigs of the workload timed on the CPU oracle")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end command-line run")
     ap.add_argument("--allow-override", action="store_true", help="accept AASM_LIB_OVERRIDE (a diagnostic build of the library; the line names what it loaded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's contigs) as DIR/<name>.npy, float64, <= 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if os.environ.get("AASM_LIB_OVERRIDE") and not args.allow_override:
         raise SystemExit("bench.py: AASM_LIB_OVERRIDE is set (%s); the bench measures the in-tree library - unset it, or pass "
@@ -255,7 +342,9 @@ def main():
     for _ in range(args.warmup):
         for d_ in dbs:
             d_.solve(max_paths=K, timing=True).close()
-    elapsed, phase_acc, stats = timed_steps(dbs, K, args.steps, barrier)
+    kept = [] if (args.dump_outputs and rank == 0) else None
+    elapsed, phase_acc, stats = timed_steps(dbs, K, args.steps, barrier, keep=kept)
+    dumped = dump_outputs(concat_outputs(kept), args.dump_outputs) if kept else None
     elapsed = allreduce(elapsed, dist.ReduceOp.MAX if dist else None)
     total_edges = allreduce(stats["n_edges"], dist.ReduceOp.SUM if dist else None)
     max_contigs = allreduce(my_contigs, dist.ReduceOp.MAX if dist else None)
@@ -363,6 +452,8 @@ def main():
             "library": library_identity(A),
         }
         out.update(extras)
+        if dumped:
+            out["dump_outputs"] = dumped
         pmc = pmc_traffic(args.workload, custom or world > 1, dom_name)
         if pmc:
             out["roofline"].update(pmc)
