@@ -35,6 +35,42 @@ class Opts(C.Structure):
     ]
 
 
+# test hooks in Opts.reserved: the names and values of include/alignasm_amd.h (tests/test_abi.py compares them)
+AASM_H0_SEQ_SELECT, AASM_H0_HEAP_MW_ALL, AASM_H0_HEAP_MW_NONE, AASM_H0_ENUM_HEAP, AASM_H0_ENUM_SMALL = 0x1, 0x2, 0x4, 0x8, 0x10
+AASM_H0_GRID_ORDER, AASM_H0_CHAIN_MASK, AASM_H0_CHAIN_ALL, AASM_H0_CHAIN_NONE, AASM_H0_CHAIN_HALF = 0x20, 0xC0, 0x40, 0x80, 0xC0
+AASM_H0_MW_MASK, AASM_H0_MW_INPUT_ORDER, AASM_H0_MW_SHIFT, AASM_H0_GRAPH_LAUNCHES = 0xFF00, 1, 8, 0x10000
+AASM_H2_LAUNCH_FAILURE, AASM_H2_WRAP_DEVICES, AASM_H2_DIRTY_SCAN, AASM_H2_CHAIN_HDR_LOST, AASM_H2_CHAIN_DONE_LOST = 0x1, 0x2, 0x4, 0x8, 0x10
+AASM_H2_CHAIN_OWN_QUEUE, AASM_H2_SMALL_ROOT_RING, AASM_H2_SORT_DEPTH_MASK, AASM_H2_SORT_DEPTH_SHIFT = 0x20, 0x40, 0xFF00, 8
+HOOK_CONSTANTS = {k: v for k, v in globals().items() if k.startswith(("AASM_H0_", "AASM_H2_"))}
+_flag = lambda bits: {False: 0, True: bits}   # noqa: E731
+# keyword -> (word of Opts.reserved, {value: its bits}, or None: the value itself); every default is 0
+HOOKS = {
+    "sequential_select": (0, _flag(AASM_H0_SEQ_SELECT)), "heap_waves": (0, {"auto": 0, "all": AASM_H0_HEAP_MW_ALL, "none": AASM_H0_HEAP_MW_NONE}),
+    "enum_heap": (0, _flag(AASM_H0_ENUM_HEAP)), "enum_small": (0, _flag(AASM_H0_ENUM_SMALL)), "grid_order": (0, _flag(AASM_H0_GRID_ORDER)),
+    "chain": (0, {"auto": 0, "all": AASM_H0_CHAIN_ALL, "none": AASM_H0_CHAIN_NONE, "half": AASM_H0_CHAIN_HALF}),
+    "heap_input_order": (0, _flag(AASM_H0_MW_INPUT_ORDER << AASM_H0_MW_SHIFT)), "heap_block_waves": (0, {n: n << AASM_H0_MW_SHIFT for n in (0, 4, 8, 16)}),
+    "graph_launches": (0, _flag(AASM_H0_GRAPH_LAUNCHES)), "test_max_contigs": (1, None),
+    "test_inject_launch_failure": (2, _flag(AASM_H2_LAUNCH_FAILURE)), "wrap_devices": (2, _flag(AASM_H2_WRAP_DEVICES)), "test_dirty_scan": (2, _flag(AASM_H2_DIRTY_SCAN)),
+    "test_chain_lost": (2, {0: 0, 1: AASM_H2_CHAIN_HDR_LOST, 2: AASM_H2_CHAIN_DONE_LOST}), "chain_own_queue": (2, _flag(AASM_H2_CHAIN_OWN_QUEUE)),
+    "test_small_root_ring": (2, _flag(AASM_H2_SMALL_ROOT_RING)), "sort_depth_test": (2, {d: d << AASM_H2_SORT_DEPTH_SHIFT for d in range(256)}),
+}
+
+
+def make_opts(max_paths=10000, non_skip_linkable=False, device=0, timing=False, keep_debug=False, **hooks):
+    """Opts of a solve; hooks by the keywords of HOOKS (unknown name: TypeError, unknown value: ValueError)."""
+    o = Opts(int(max_paths), 1 if non_skip_linkable else 0, int(device), 1 if timing else 0, 1 if keep_debug else 0)
+    for name, value in hooks.items():
+        if name not in HOOKS:
+            raise TypeError(f"unknown test hook {name!r}")
+        word, table = HOOKS[name]
+        if table is not None and value not in table:
+            raise ValueError(f"test hook {name}={value!r}: not one of {sorted(table, key=str)}")
+        o.reserved[word] |= int(value) if table is None else table[value]
+    if hooks.get("heap_input_order") and hooks.get("heap_block_waves"):
+        raise ValueError("heap_input_order and heap_block_waves set the same field")
+    return o
+
+
 class OutElem(C.Structure):
     _fields_ = [
         ("edited_qry_str", C.c_int64), ("edited_qry_end", C.c_int64), ("edited_ref_str", C.c_int64),

@@ -76,7 +76,6 @@ AASM_DEF_KERNEL_LDS(aasm_k6_rev_sweep_g, KN_REV_SWEEP_G, 64, (AASM_WAVE / AASM_S
 AASM_DEF_KERNEL_LDS(aasm_k5_fwd_sweep_g, KN_FWD_SWEEP_G, 64, (AASM_WAVE / AASM_SWEEP_G) * AASM_FWD_LDS_BYTES, 4)
 AASM_DEF_KERNEL(aasm_k7_children, KN_CHILDREN, 256)
 AASM_DEF_KERNEL(aasm_k7_heap_cap, KN_HEAP_CAP, 256)
-AASM_DEF_KERNEL(aasm_k7_sidetrack, KN_SIDETRACK, 256)
 AASM_DEF_KERNEL_LDS(aasm_k7_sidetrack_w, KN_SIDETRACK_W, 64, AASM_SIDE_LDS_BYTES, 8)
 AASM_DEF_KERNEL(aasm_k7_heap_hdr, KN_HEAP_HDR, 256)
 AASM_DEF_KERNEL(aasm_k7_prep, KN_K7_PREP, 256)
@@ -85,7 +84,7 @@ AASM_DEF_KERNEL(aasm_k9_tnx16, KN_TNX16, 256)
 AASM_DEF_KERNEL_LDS(aasm_k9_tnx16_wg, KN_TNX16_WG, TNX_TPB, AASM_TNXWG_LDS_BYTES, 4)   // the 16-hop jump records of a small contig from its tree in LDS
 AASM_DEF_KERNEL_LDS(aasm_k7_heap, KN_HEAP, 64, AASM_HEAP_LDS_BYTES, 5)
 AASM_DEF_KERNEL_LDS(aasm_k67_chain, KN_CHAIN, 64 * CHAIN_WAVES, AASM_CHAIN_LDS_BYTES, 5)   // sweep + pre-pass + BFS order + heaps of one contig, a wave each (96 VGPRs, 19 spilled: worth it for the fifth wave slot per SIMD)
-AASM_DEF_KERNEL_LDS(aasm_k67_chain3, KN_CHAIN3, 64 * (CHAIN_WAVES - 1), AASM_CHAIN_LDS_BYTES, 5)   // ... without the order wave (the heap wave keeps its own queue): classes of more than 896 contigs
+AASM_DEF_KERNEL_LDS(aasm_k67_chain3, KN_CHAIN3, 64 * (CHAIN_WAVES - 1), AASM_CHAIN_LDS_BYTES, 5)   // ... without the order wave (the heap wave keeps its own queue): classes of more than AASM_CHAIN_ORD_MAX contigs
 AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw, KN_HEAP_MW, 256, AASM_MW_LDS_BYTES(4), 4)
 AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw8, KN_HEAP_MW8, 512, AASM_MW_LDS_BYTES(8), 4)
 AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw16, KN_HEAP_MW16, 1024, AASM_MW_LDS_BYTES(16), 4)
@@ -682,7 +681,7 @@ struct GpuBackend {
             L(KN_ROW_COUNT, aasm_k4_row_count) L(KN_ROW_FILL, aasm_k4_row_fill) L(KN_GRAPH, aasm_k46_graph) L(KN_GRAPH_L, aasm_k46_graph_l) L(KN_REV_FILL, aasm_k6_rev_fill) L(KN_REV_FILL_W, aasm_k6_rev_fill_w) L(KN_REV_FILL_ORD, aasm_k6_rev_fill_ord) L(KN_REV_FILL_ORD_S, aasm_k6_rev_fill_ord_s)
             L(KN_SORT_ROWS_REV, aasm_k6_rev_place) L(KN_REV_HDR, aasm_k6_rev_hdr) L(KN_REV_SWEEP, aasm_k6_rev_sweep) L(KN_FWD_SWEEP, aasm_k5_fwd_sweep) L(KN_REV_SWEEP_G, aasm_k6_rev_sweep_g) L(KN_FWD_SWEEP_G, aasm_k5_fwd_sweep_g)
             L(KN_CHILDREN, aasm_k7_children)
-            L(KN_HEAP_CAP, aasm_k7_heap_cap) L(KN_SIDETRACK, aasm_k7_sidetrack) L(KN_SIDETRACK_W, aasm_k7_sidetrack_w) L(KN_HEAP_HDR, aasm_k7_heap_hdr) L(KN_HEAP, aasm_k7_heap) L(KN_HEAP_MW, aasm_k7_heap_mw) L(KN_HEAP_MW8, aasm_k7_heap_mw8) L(KN_HEAP_MW16, aasm_k7_heap_mw16) L(KN_MW_RANK, aasm_k7_mw_rank) L(KN_ENUM, aasm_k8_enum) L(KN_ENUM_S, aasm_k8_enum_s) L(KN_ENUM_HEAP, aasm_k8_enum_heap) L(KN_SELECT, aasm_k9_select)
+            L(KN_HEAP_CAP, aasm_k7_heap_cap) L(KN_SIDETRACK_W, aasm_k7_sidetrack_w) L(KN_HEAP_HDR, aasm_k7_heap_hdr) L(KN_HEAP, aasm_k7_heap) L(KN_HEAP_MW, aasm_k7_heap_mw) L(KN_HEAP_MW8, aasm_k7_heap_mw8) L(KN_HEAP_MW16, aasm_k7_heap_mw16) L(KN_MW_RANK, aasm_k7_mw_rank) L(KN_ENUM, aasm_k8_enum) L(KN_ENUM_S, aasm_k8_enum_s) L(KN_ENUM_HEAP, aasm_k8_enum_heap) L(KN_SELECT, aasm_k9_select)
             L(KN_GATHER_OUT, aasm_k9_gather_out) L(KN_TOPO_COUNT, aasm_k9_topo_count) L(KN_TOPO_FILL, aasm_k9_topo_fill)
             L(KN_CHAIN, aasm_k67_chain) L(KN_CHAIN3, aasm_k67_chain3) L(KN_K7_PREP, aasm_k7_prep) L(KN_TNX, aasm_k9_tnx) L(KN_TNX16, aasm_k9_tnx16) L(KN_TNX16_WG, aasm_k9_tnx16_wg)
             L(KN_SEL_PLAN, aasm_k9_sel_plan) L(KN_SEL_PLANFILL, aasm_k9_sel_planfill) L(KN_SEL_RECOVER, aasm_k9_sel_recover) L(KN_SEL_CLASSIFY, aasm_k9_sel_classify) L(KN_SEL_CONVERT, aasm_k9_sel_convert) L(KN_SEL_FINAL, aasm_k9_sel_final)
@@ -805,7 +804,7 @@ static int solve_on_device(DevCtx &cx, const aasm_batch_in &dev_in, const aasm_o
     res->device = cx.device; res->stream = stream;
     std::memset(&res->stats, 0, sizeof(res->stats));
     if (timing) hipEventRecord(cx.ev_t0, stream);
-    be->test_dirty_scan = (opts.reserved[2] & 4) != 0;              // test hook: the next scan finds a ticket counter an aborted launch left behind
+    be->test_dirty_scan = decode_hooks(opts).dirty_scan;            // test hook: the next scan finds a ticket counter an aborted launch left behind
     int rc = run_pipeline(*be, dev_in, opts, res->w, res->sz);
     be->flush_zero();
     if (timing) hipEventRecord(cx.ev_t1, stream);
@@ -988,7 +987,7 @@ int aasm_debug_predicates(const int64_t *a, const int64_t *b, int64_t n, uint8_t
 }
 
 // Test entry (hazard B1): K1's std::sort replay alone, on arbitrary keys.  rec_off[n_contigs + 1] from 0; perm_out[r] per
-// record = the input index (relative to its contig) that std::sort leaves at sorted position r.  depth_test as aasm_opts.reserved[2] bits 8-15.
+// record = the input index (relative to its contig) that std::sort leaves at sorted position r.  depth_test as AASM_H2_SORT_DEPTH_MASK.
 int aasm_debug_sort_replay(const int64_t *rec_off, int64_t n_contigs, const int64_t *qs, const int64_t *qe, int32_t *perm_out, int depth_test, int device) {
     if (!rec_off || !qs || !qe || !perm_out || n_contigs <= 0 || rec_off[0] != 0) return AASM_E_INVAL;
     for (int64_t c = 0; c < n_contigs; c++) if (rec_off[c + 1] < rec_off[c]) return AASM_E_INVAL;
@@ -1378,8 +1377,9 @@ static void ctx_release_arena(int device) {
 }
 
 static int solve_range_once(const aasm_batch_in *in, int64_t c0, int64_t c1, const aasm_opts &o, aasm_batch_out *out) {
-    if (o.reserved[1] > 0 && c1 - c0 > o.reserved[1]) {               // test hook (opts.reserved[1]): pretend larger ranges do not fit
-        set_last_error("range exceeds the test limit opts.reserved[1]");
+    const int64_t limit = decode_hooks(o).range_limit;
+    if (limit > 0 && c1 - c0 > limit) {                               // test hook: pretend larger ranges do not fit
+        set_last_error("range exceeds the test hook's range limit");
         return AASM_E_NOMEM;
     }
     aasm_upload *up = nullptr;
@@ -1483,11 +1483,11 @@ int aasm_solve_batch_multi(const aasm_batch_in *in, const aasm_opts *opts, int n
     contig_costs(in, cost.data());
     std::vector<int64_t> cut(n_devices + 1, 0);
     partition_by_cost(cost.data(), C, n_devices, cut.data());
-    // test hook (opts.reserved[2] bit 1, or AASM_TEST_WRAP_DEVICES=1 for the CLI): device ordinals wrap around the devices
+    // test hook (AASM_H2_WRAP_DEVICES, or AASM_TEST_WRAP_DEVICES=1 for the CLI): device ordinals wrap around the devices
     // that exist, so that the one-thread-per-shard path runs on a box with fewer GPUs than shards (the shards of one
     // device take turns on its context)
     const char *wrap_env = getenv("AASM_TEST_WRAP_DEVICES");
-    const bool wrap = (o.reserved[2] & 2) != 0 || (wrap_env && wrap_env[0] == '1');
+    const bool wrap = decode_hooks(o).wrap_devices || (wrap_env && wrap_env[0] == '1');
     const int ndev = std::max(1, aasm_device_count());
     std::vector<aasm_batch_out> parts(n_devices);
     std::vector<int> rcs(n_devices, AASM_OK);

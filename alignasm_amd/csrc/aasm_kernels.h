@@ -7,7 +7,7 @@
 //   --  reversed CSR ............. k_shortest_walks.hpp:180-183 . kb_rev_fill, kb_rev_place, kb_rev_hdr
 //   K6  Kahn(rev)+DAG-SP ......... k_shortest_walks.hpp:132-175 . kb_rev_sweep
 //   K5/6 Kahn(fwd)+anomaly ....... paf_data.cpp:704-713,742-746 . kb_fwd_sweep
-//   K7  sidetrack heaps .......... k_shortest_walks.hpp:191-215, leftist_heap.hpp:29-40 .. kb_children, kb_sidetrack, kb_heap_hdr, kb_heap, kb_heap_mw
+//   K7  sidetrack heaps .......... k_shortest_walks.hpp:191-215, leftist_heap.hpp:29-40 .. kb_children, kb_sidetrack_w, kb_k7_prep, kb_heap_hdr, kb_heap, kb_heap_mw
 //   K8  enumeration .............. k_shortest_walks.hpp:217-249 . kb_enum
 //   K9  recover/upgrade/select ... k_shortest_walks.hpp:254-290, paf_data.cpp:750-921,1489-1649 .. kb_select
 //
@@ -118,7 +118,7 @@ struct WS {
     int32_t *mw_list, *mw_sorted;        // the contigs of the several-waves class: in any order; by node bound, largest first
     int32_t *mw_key;                     // the node bounds, in mw_list's order
     int32_t mw_n, mw_base;               // contigs of the class; kb_heap_mw by list (mw_base >= 0): block b builds mw_sorted[mw_base + b]
-    I4 *tnx;                             // next four vertices along best[] (kb_sidetrack) ...
+    I4 *tnx;                             // next four vertices along best[] (tnx_vertex) ...
     int32_t *tnx16;                      // ... and the next sixteen (kb_heap_hdr): path recovery reads one 64-byte record per sixteen tree edges
     I4 *rvh;                             // K6: per-vertex in-list header, 3 words (see kb_rev_hdr)
     I4 *r_pk;                            // K6: one packed record per in-edge, in in-list order
@@ -126,13 +126,13 @@ struct WS {
     // ---- the chain class (kb_chain): contigs whose K6 sweep, K7 pre-pass and K7 heaps run BESIDE each other in one workgroup
     int32_t chain_mode;                  // 0: by batch shape, 1: every sparse one-wave contig, 2: none (tests, probes)
     int32_t chain_all, chain_minN;       // mode 0: every contig of the batch (small batches) / contigs of at least this many records (the long tail)
-    int32_t chain_test;                  // test hooks (opts.reserved[2] bits 3, 4): 1 = the prep wave of contig 0 never publishes dest's header; 2 = ... and never says it is done (the heap wave's patience is 1 s then)
+    int32_t chain_test;                  // test hooks (AASM_H2_CHAIN_HDR_LOST, AASM_H2_CHAIN_DONE_LOST): 1 = the prep wave of contig 0 never publishes dest's header; 2 = ... and never says it is done (the heap wave's patience is 1 s then)
     int32_t *chain_flag, *chain_list;    // per contig: in the class; the contigs of the class, in any order
     int32_t *pend;                       // per vertex: in-neighbours whose keys are not written yet (the prep wave counts them down)
     int32_t *cq;                         // per contig slice: vertices whose header can be built, in the order they became ready
     I4 *bfsq;                            // per contig slice: the SP tree in BFS order, a record {vertex, position of its parent, start of its keys, #keys} per position (kb_chain's order wave -> heap wave)
     int32_t chain_ord;                   // kb_chain: 1 = the BFS order comes from a wave of its own (default), 0 = the heap wave keeps its own queue (probes, tests)
-    int32_t chain_rn;                    // test hook (opts.reserved[2] bit 6): kb_heap_ord's ring of roots has this many entries (default 0: all 512), so that parents beyond it - frontiers wider than the ring - come up on small inputs
+    int32_t chain_rn;                    // test hook (AASM_H2_SMALL_ROOT_RING): kb_heap_ord's ring of roots has this many entries (default 0: all 512), so that parents beyond it - frontiers wider than the ring - come up on small inputs
 };
 
 enum { CNT_RANGE_STEPS = 0, CNT_UNCONN, CNT_POOL, CNT_AR, CNT_CONVERTED, CNT_HEAPNODES, CNT_PATHS, CNT_OVF, CNT_ISPR_E, CNT_ISPR_V, CNT_PATH_E, CNT_OUT_E, CNT_PQ_PUSH, CNT_MW, CNT_MAXN, CNT_LONGSORT, CNT_MAXV, CNT_CHAIN, CNT_GB_S, CNT_GB_L, CNT_GB_REST, CNT_N };
@@ -2156,11 +2156,6 @@ AASM_DEV void kb_tnx(const KCtx &k, const WS &w) {                  // thread pe
     if (gv >= w.VT || in_chain_class(w, w.v_ctg[gv]) || in_graph_class(w, w.v_ctg[gv])) return;   // (the chain class: its prep wave, kb_chain; the small contigs of a sparse batch: kb_tnx16_wg)
     tnx_vertex(w, gv);
 }
-AASM_DEV void kb_sidetrack(const KCtx &k, const WS &w) {
-    const int64_t gv = k.bid * k.nthreads + k.tid;
-    if (gv >= w.VT || in_chain_class(w, w.v_ctg[gv])) return;
-    sidetrack_vertex(w, gv);
-}
 // The same for dense graphs (rows of tens to hundreds of edges): a wave takes AASM_WAVE consecutive rows - one contiguous run of
 // edges - in chunks of 64 edges, lanes = edges.  What is sequential per row becomes ballots: the tree edge is the lowest
 // candidate lane of the row's stretch of the chunk, unless an earlier chunk had it (seen[row]); a kept edge's place is the row's
@@ -2222,7 +2217,7 @@ AASM_DEV void kb_sidetrack_w(const KCtx &k, const WS &w) {          // wave per 
         wave_lds_sync();
     }
     for (int32_t t = k.lane; t < nrows; t += AASM_WAVE) w.st_n[row0 + t] = L->cnt[t];
-    if (bad) w.status[w.v_ctg[row0 + bad_row]] = -6;                 // must not happen (see kb_sidetrack)
+    if (bad) w.status[w.v_ctg[row0 + bad_row]] = -6;                 // must not happen (see sidetrack_vertex)
 }
 // K7 pre-pass 2, thread per vertex u: what the heap wave reads per vertex, 32 bytes:
 //   vhdr  = {so, #keys, #children, first child}          so = start of u's keys, relative to the contig's first edge
@@ -2259,7 +2254,7 @@ AASM_DEV void heap_hdr_vertex(const WS &w, int64_t gv, I4 &a, I4 &b, int32_t nch
         }
     }
 }
-// sixteen tree hops = four 4-hop records chained (kb_sidetrack wrote those; -1 past dest): what K9's recovery reads, one 64-byte
+// sixteen tree hops = four 4-hop records chained (tnx_vertex wrote those; -1 past dest): what K9's recovery reads, one 64-byte
 // record per sixteen tree edges.  It needs the 4-hop records of OTHER vertices, hence a launch of its own (side stream: only K9 waits for it)
 AASM_DEV void tnx16_vertex(const WS &w, int64_t gv) {
     const int64_t vb = w.voff[w.v_ctg[gv]];
@@ -2456,7 +2451,7 @@ AASM_DEV NodeQ heap_read(const HeapState &hs, int32_t a, HNode *slot = nullptr) 
     n = nodeq_load(src);
     return n;
 }
-// node.key < key (paf_data.hpp:142-159, CALC_SUM mode) for keys that are never max() (kb_sidetrack)
+// node.key < key (paf_data.hpp:142-159, CALC_SUM mode) for keys that are never max() (sidetrack_vertex)
 AASM_DEV bool nodeq_key_lt(const NodeQ &n, const Dist &key, int64_t ksum) {
     const Dist nk = nodeq_key(n);
     const int64_t nsum = nk.qry + nk.ref;
@@ -2647,7 +2642,7 @@ AASM_DEV void kb_heap(const KCtx &k, const WS &w, ChainSync *S = nullptr) {   //
     const int64_t vb = w.voff[c];
     int32_t *h = w.h_root + vb, *q = w.bq + vb;
     const I4 *vh = w.vhdr + vb, *vh2 = w.vhdr2 + vb;
-    const Dist *sk = w.st_cost + w.rowptr[vb];                      // the contig's compacted sidetrack keys (kb_sidetrack)
+    const Dist *sk = w.st_cost + w.rowptr[vb];                      // the contig's compacted sidetrack keys (sidetrack_vertex)
     HeapState hs;
     hs.nodes = w.hnodes + w.hoff[c]; hs.ring = L->ring; hs.rn = RING; hs.bounce = &L->bounce; hs.oldn = L->oldn; hs.alloc = 0; hs.flushed = 0; hs.ring_lo = 0; hs.ovf = false;
     hs.cap = (int32_t)(w.hoff[c + 1] - w.hoff[c]);
@@ -2809,7 +2804,7 @@ AASM_DEV void kb_heap(const KCtx &k, const WS &w, ChainSync *S = nullptr) {   //
 // classes of more than AASM_CHAIN_ORD_MAX contigs keep the three-role form, where wave 2 is the heap wave with its own queue):
 //   wave 0  the reverse sweep as before (kb_rev_sweep), which now also publishes how many vertices of rev_order are final;
 //   wave 1  the pre-pass, lanes over vertices, behind it: for the vertices that became final - their sidetrack keys (what
-//           kb_sidetrack does), then one count-down per out-edge on the head's `pend`; a vertex whose in-neighbours ALL have their
+//           sidetrack_vertex does), then one count-down per out-edge on the head's `pend`; a vertex whose in-neighbours ALL have their
 //           keys gets its child list and header (kb_children + kb_heap_hdr: the children of u are in-neighbours of u) - these
 //           go through a work list (cq) and are published by the header's two marker words turning from -1;
 //   wave 2  the BFS order of the tree: one record {vertex, parent's position, keys} per position (chain_order); it is the one that

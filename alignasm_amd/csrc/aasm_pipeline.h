@@ -23,7 +23,7 @@ namespace aasm {
 enum Kern {
     KN_CS_RANGES, KN_SORT, KN_SORT_RANK, KN_SORT_FIX, KN_GATHER_PARTS, KN_OV_COUNT, KN_OV_MERGE, KN_VCOUNT, KN_VFILL_REC, KN_VFILL_SLOT,
     KN_NSL, KN_ROW_COUNT, KN_ROW_FILL, KN_GRAPH, KN_GRAPH_L, KN_REV_FILL, KN_REV_FILL_W, KN_REV_FILL_ORD, KN_REV_FILL_ORD_S, KN_SORT_ROWS_REV, KN_REV_HDR, KN_REV_SWEEP, KN_FWD_SWEEP, KN_REV_SWEEP_G, KN_FWD_SWEEP_G,
-    KN_CHILDREN, KN_HEAP_CAP, KN_SIDETRACK, KN_SIDETRACK_W, KN_HEAP_HDR, KN_HEAP, KN_HEAP_MW, KN_HEAP_MW8, KN_HEAP_MW16, KN_MW_RANK, KN_ENUM, KN_ENUM_S, KN_ENUM_HEAP, KN_SELECT, KN_GATHER_OUT, KN_TOPO_COUNT, KN_TOPO_FILL,
+    KN_CHILDREN, KN_HEAP_CAP, KN_SIDETRACK_W, KN_HEAP_HDR, KN_HEAP, KN_HEAP_MW, KN_HEAP_MW8, KN_HEAP_MW16, KN_MW_RANK, KN_ENUM, KN_ENUM_S, KN_ENUM_HEAP, KN_SELECT, KN_GATHER_OUT, KN_TOPO_COUNT, KN_TOPO_FILL,
     KN_SEL_PLAN, KN_SEL_PLANFILL, KN_SEL_RECOVER, KN_SEL_CLASSIFY, KN_SEL_CONVERT, KN_SEL_FINAL, KN_CHAIN, KN_CHAIN3, KN_K7_PREP, KN_TNX, KN_TNX16, KN_TNX16_WG
 };
 
@@ -56,7 +56,6 @@ AASM_DEV void run_kernel_body(int kn, const KCtx &k, const WS &w) {
         case KN_FWD_SWEEP_G: kb_fwd_sweep<AASM_SWEEP_G>(k, w); break;
         case KN_CHILDREN: kb_children(k, w); break;
         case KN_HEAP_CAP: kb_heap_cap(k, w); break;
-        case KN_SIDETRACK: kb_sidetrack(k, w); break;
         case KN_SIDETRACK_W: kb_sidetrack_w(k, w); break;
         case KN_HEAP_HDR: kb_heap_hdr(k, w); break;
         case KN_HEAP: kb_heap<false, HEAP_RING_1W, HEAP_QN_1W>(k, w); break;
@@ -100,6 +99,60 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #endif
 struct PipelineSizes { int64_t C = 0, R = 0, S = 0, VT = 0, ET = 0, HT = 0, bad_record = -1; };
 
+// The test hooks of aasm_opts.reserved (AASM_H0_* / AASM_H2_*, include/alignasm_amd.h), decoded once; all zero in production.
+struct Hooks {
+    bool seq_select, enum_heap, enum_small, grid_order, graph_launches, chain_half, launch_failure, wrap_devices, dirty_scan, chain_own_queue;
+    int32_t heap_mw, chain, chain_test, root_ring, sort_depth;   // WS::mw_mode, chain_mode, chain_test, chain_rn, sort_depth_test
+    int32_t mw;                   // K7's several-waves kernel: AASM_H0_MW_INPUT_ORDER, or 4 / 8 / 16 waves per contig
+    int64_t range_limit;          // > 0: longer contig ranges "do not fit"
+};
+static inline Hooks decode_hooks(const aasm_opts &o) {
+    const int32_t h0 = o.reserved[0], h2 = o.reserved[2], ch = h0 & AASM_H0_CHAIN_MASK;
+    Hooks h;
+    h.seq_select = h0 & AASM_H0_SEQ_SELECT; h.enum_heap = h0 & AASM_H0_ENUM_HEAP; h.enum_small = h0 & AASM_H0_ENUM_SMALL;
+    h.grid_order = h0 & AASM_H0_GRID_ORDER; h.graph_launches = h0 & AASM_H0_GRAPH_LAUNCHES; h.chain_half = ch == AASM_H0_CHAIN_HALF;
+    h.heap_mw = (h0 & AASM_H0_HEAP_MW_ALL) ? 1 : (h0 & AASM_H0_HEAP_MW_NONE) ? 2 : 0;       // every contig / none / by graph density
+    h.chain = ch == AASM_H0_CHAIN_ALL ? 1 : ch == AASM_H0_CHAIN_NONE ? 2 : 0;              // every sparse contig / none / by batch shape
+    h.mw = (h0 & AASM_H0_MW_MASK) >> AASM_H0_MW_SHIFT; h.range_limit = o.reserved[1];
+    h.launch_failure = h2 & AASM_H2_LAUNCH_FAILURE; h.wrap_devices = h2 & AASM_H2_WRAP_DEVICES; h.dirty_scan = h2 & AASM_H2_DIRTY_SCAN;
+    h.chain_test = (h2 & AASM_H2_CHAIN_DONE_LOST) ? 2 : (h2 & AASM_H2_CHAIN_HDR_LOST) ? 1 : 0; h.chain_own_queue = h2 & AASM_H2_CHAIN_OWN_QUEUE;
+    h.root_ring = (h2 & AASM_H2_SMALL_ROOT_RING) ? 4 : 0; h.sort_depth = (h2 & AASM_H2_SORT_DEPTH_MASK) >> AASM_H2_SORT_DEPTH_SHIFT;
+    return h;
+}
+
+// The launch forms, from the sizes known once the edges are counted.  MAXV: most vertices of one contig; NCHAIN: contigs of the chain
+// class; HTM / NMW: provisional arena and contigs of K7's several-waves class; MAXN: most records of one contig.
+struct FormSizes { int64_t C, R, K, VT, ET, MAXV, NCHAIN, HTM, NMW, MAXN; };
+struct Forms {
+    bool grouped, dense, mw_ranked;   // sweeps two contigs per wave; mean degree > 6; K7's several-waves class by rank, largest node bound first
+    int rev_fill, chain, mw_kern, mw_waves, enum_kern;   // the kernels of the reversed CSR's fill, the chain class, K7's class, K8's queue
+};
+static inline Forms choose_forms(const FormSizes &s, const Hooks &h, bool host_emulation) {
+    Forms f;
+    f.dense = s.ET > 6 * s.VT;
+    // big sparse batches (mean degree <= 6, thousands of contigs: bound by instruction issue): two contigs per wave, AASM_SWEEP_G lanes
+    // each; dense ones and small batches (bound by the chain per contig): a wave per contig (the scalar-uniform variant has the shorter
+    // chain per pop)
+    f.grouped = !f.dense && s.C >= AASM_GROUPED_MIN;
+    // dense, no giant contig: the in-lists in order from one pass per contig (every contig of <= REV_ORD_MIDV vertices - C5's have 2 500 -:
+    // the launch with 6.7 KB of LDS counters instead of 25 KB, i.e. 6 waves per SIMD instead of 2); else dense: lanes over the edges of 64 rows
+    f.rev_fill = f.dense && s.MAXV <= REV_ORD_MAXV ? (s.MAXV <= REV_ORD_MIDV ? KN_REV_FILL_ORD_S : KN_REV_FILL_ORD) : f.dense ? KN_REV_FILL_W : KN_REV_FILL;
+    // the class's BFS order from a wave of its own while four waves a contig fit the chip beside the forward sweep (four workgroups per CU);
+    // beyond that the three-role kernel, where the heap wave keeps its own queue
+    f.chain = !h.chain_own_queue && s.NCHAIN <= AASM_CHAIN_ORD_MAX ? KN_CHAIN : KN_CHAIN3;
+    // 16, 8 or 4 waves a contig, by how many of them share the chip's ~8 k wave slots
+    f.mw_waves = (h.mw == 4 || h.mw == 8 || h.mw == 16) ? h.mw : s.NMW * 16 <= 6144 ? 16 : s.NMW * 8 <= 6144 ? 8 : 4;
+    f.mw_kern = f.mw_waves == 16 ? KN_HEAP_MW16 : f.mw_waves == 8 ? KN_HEAP_MW8 : KN_HEAP_MW;
+    f.mw_ranked = h.mw != AASM_H0_MW_INPUT_ORDER && s.NMW >= 2 && s.NMW <= 32768;   // (ranked by counting: NMW^2 compares)
+    // K8: sorted front + sorted runs (aasm_enum.h) unless a contig is too long for its packed ratio key; the d-ary heap is also what the
+    // 1-lane host emulation runs.  More contigs than the 64-entry front keeps resident (14 waves per CU = 3 584): the 40-entry front (20 per
+    // CU = 5 120) runs them in one residency round (round 4, with the far tier: 5 000 contigs 23.85 -> 23.1 ms; round 3, without it, the
+    // extra refills and flushes of the small front cost more than the second round: 30.2 vs 31.5 ms); beyond 5 120 both take a second round
+    const bool enum_heap = host_emulation || h.enum_heap || s.MAXN > AASM_ENUM_MAX_N;
+    f.enum_kern = enum_heap ? KN_ENUM_HEAP : ((s.C > 14 * 256 && s.C <= 20 * 256 && s.K > 21) || h.enum_small) ? KN_ENUM_S : KN_ENUM;
+    return f;
+}
+
 // Runs the pipeline for contigs [0, C) described by `in` (device pointers; ctg_rec_off
 // already offset to the chunk).  Leaves all intermediates in the backend's arena and
 // returns the filled WS (so fetch / debug can read them).
@@ -114,20 +167,19 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     w.C = C; w.R = R; w.R0 = R0;
     w.K = opts.max_paths > 0 ? opts.max_paths : 10000;
     w.nsl = opts.non_skip_linkable ? 1 : 0;
-    w.xcd_map = (opts.reserved[0] & 32) ? 0 : 1;                      // (bit 5, probes: blocks take work items in grid order)
-    w.sort_depth_test = (opts.reserved[2] >> 8) & 0xff;               // test hook: depth limit of kb_sort_fix's introsort
-    // the chain class (kb_chain: sweep, pre-pass and heaps of a contig beside each other).  reserved[0] bit 6: every sparse contig,
-    // bit 7: none; else by shape: every contig of a batch too small to fill the chip (its step is its slowest contig's chain), and
-    // the long tail of a big one (contigs of >= 4x the mean and >= 2048 records: each a chain many times the batch's own step)
-    // (both bits, tests: the contigs of at least the batch's mean size - a class that is part of the batch whatever its shape, so that
-    // the class's workgroups and the three launches of the others run beside each other)
-    w.chain_mode = (opts.reserved[0] & 192) == 192 ? 0 : (opts.reserved[0] & 64) ? 1 : (opts.reserved[0] & 128) ? 2 : 0;
-    w.chain_test = (opts.reserved[2] & 16) ? 2 : (opts.reserved[2] & 8) ? 1 : 0;
-    w.chain_rn = (opts.reserved[2] & 64) ? 4 : 0;                     // (bit 6, tests: a 4-entry ring of roots in the chain class's heap wave)
-    w.chain_ord = (opts.reserved[2] & 32) ? 0 : 1;                    // (bit 5: the heap wave of the chain class keeps its own BFS queue - probes, tests; decided below by the size of the class)
-    w.chain_all = ((opts.reserved[0] & 192) != 192 && C <= AASM_CHAIN_SMALL_BATCH) ? 1 : 0;
+    const Hooks h = decode_hooks(opts);
+    // the hooks' WS fields, and the inputs of the per-contig classes kb_heap_cap picks on the device
+    w.xcd_map = h.grid_order ? 0 : 1; w.sort_depth_test = h.sort_depth;
+    // the chain class (kb_chain: sweep, pre-pass and heaps of a contig beside each other), by shape: every contig of a batch too small
+    // to fill the chip (its step is its slowest contig's chain), and the long tail of a big one (contigs of >= 4x the mean and >= 2048
+    // records: each a chain many times the batch's own step).  AASM_H0_CHAIN_HALF: the contigs of at least the batch's mean size - a
+    // class that is part of the batch whatever its shape, so that the class's workgroups and the three launches of the others run
+    // beside each other
+    w.chain_mode = h.chain; w.chain_test = h.chain_test; w.chain_rn = h.root_ring;
+    w.chain_ord = h.chain_own_queue ? 0 : 1;                          // (decided below by the size of the class)
+    w.chain_all = (!h.chain_half && C <= AASM_CHAIN_SMALL_BATCH) ? 1 : 0;
     w.chain_minN = (int32_t)std::min<int64_t>(std::max<int64_t>(2048, 4 * (R / std::max<int64_t>(C, 1))), INT32_MAX);
-    if ((opts.reserved[0] & 192) == 192) w.chain_minN = (int32_t)std::min<int64_t>(std::max<int64_t>(1, cdiv(R, std::max<int64_t>(C, 1))), INT32_MAX);
+    if (h.chain_half) w.chain_minN = (int32_t)std::min<int64_t>(std::max<int64_t>(1, cdiv(R, std::max<int64_t>(C, 1))), INT32_MAX);
     w.rec_off = in.ctg_rec_off; w.in_qs = in.qry_str; w.in_qe = in.qry_end; w.in_rs = in.ref_str; w.in_re = in.ref_end;
     w.in_qt = in.qry_total; w.in_chr = in.ref_chr; w.in_fwd = in.aln_fwd; w.in_mq = in.map_qul;
     w.in_rng_off = in.rec_rng_off; w.rql = in.rng_qry_l; w.rqr = in.rng_qry_r; w.rrl = in.rng_ref_l; w.rng_stride = 1;
@@ -176,7 +228,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     A(s_qt, int64_t, R, "s_qt"); A(s_rb, int64_t, R, "s_rb"); A(s_rn, int32_t, R, "s_rn"); A(s_chr, int32_t, R, "s_chr");
     A(s_orig, int32_t, R, "s_orig"); A(s_ctg, int32_t, R, "s_ctg"); A(s_pid, int32_t, R, "s_pid"); A(s_fl, uint8_t, R, "s_fl");
     CHECK_ALLOC();
-    if (opts.reserved[2] & 1) be.launch(KN_SORT, C, 4096, w);       // test hook: an invalid launch configuration (block size > 1024)
+    if (h.launch_failure) be.launch(KN_SORT, C, 4096, w);           // an invalid launch configuration (block size > 1024)
     be.launch(KN_SORT, C, 256, w);
     be.launch(KN_SORT_RANK, cdiv(R, 256), 256, w);
     be.launch(KN_SORT_FIX, C, AASM_WAVE, w);
@@ -231,8 +283,8 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         A(hcap_cnt, int32_t, C, "hcap_cnt"); A(hoff, int64_t, C + 1, "hoff");
         A(mw_flag, int32_t, C, "mw_flag"); A(mw_lg, int32_t, C, "mw_lg"); A(mw_cap, int32_t, C, "mw_cap"); A(mw_off, int64_t, C + 1, "mw_off"); A(mw_list, int32_t, C, "mw_list"); A(mw_sorted, int32_t, C, "mw_sorted"); A(mw_key, int32_t, C, "mw_key");
         A(chain_flag, int32_t, C, "chain_flag"); A(chain_list, int32_t, C, "chain_list"); A(gb_flag, int32_t, C, "gb_flag");
-        w.gb_off = (opts.reserved[0] & 0x10000) ? 1 : 0;                 // (bit 16: every contig by the separate launches, for tests and probes)
-        w.mw_mode = (opts.reserved[0] & 2) ? 1 : (opts.reserved[0] & 4) ? 2 : 0;
+        w.gb_off = h.graph_launches ? 1 : 0;
+        w.mw_mode = h.heap_mw;
         w.mw_compact = opts.keep_debug ? 1 : 0;   // debug runs compare arena indices with the reference's allocation order
         CHECK_ALLOC();
         be.launch(KN_ROW_COUNT, cdiv(VT, 256), 256, w);
@@ -245,9 +297,9 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         const int64_t GB_S = et_mv[7], GB_L = et_mv[8], GB_REST = et_mv[9];   // contigs whose graph one workgroup builds (kb_graph_build, two forms) / the others
         const int64_t hh[4] = {et_mv[2], et_mv[3], et_mv[4], et_mv[5]};
         const int64_t NCHAIN = et_mv[6];
-        // the class's BFS order from a wave of its own while four waves a contig fit the chip beside the forward sweep (four workgroups per CU);
-        // beyond that the three-role kernel, where the heap wave keeps its own queue
-        if (NCHAIN > AASM_CHAIN_ORD_MAX) w.chain_ord = 0;
+        const int64_t HT = hh[0], HTM = hh[1], NMW = HTM > 0 ? hh[2] : 0;
+        const Forms f = choose_forms({C, R, w.K, VT, ET, MAXV, NCHAIN, HTM, NMW, hh[3]}, h, B::host_emulation);
+        w.chain_ord = f.chain == KN_CHAIN ? 1 : 0;
         w.ET = ET; sz.ET = ET;
         A(e_col, int32_t, ET, "csr_col"); A(e_wq, int64_t, ET, "csr_w_qry"); A(e_wr, int32_t, ET, "csr_w_ref"); A(e_fl, uint8_t, ET, "csr_w_flags");
         A(rptr, int64_t, VT + 1, "rptr"); A(r_pk, I4, ET, "r_pk");
@@ -276,11 +328,9 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         A(r_e, int32_t, ET, "r_e"); A(tmp_pk, I4, ET, "tmp_pk");
         CHECK_ALLOC();
         be.scan_i32(w.indeg, VT, w.rptr);
-        // dense, no giant contig: the in-lists in order from one pass per contig (every contig of <= REV_ORD_MIDV vertices - C5's have 2 500 -: the
-        // launch with 6.7 KB of LDS counters instead of 25 KB, i.e. 6 waves per SIMD instead of 2)
-        if (ET > 6 * VT && MAXV <= REV_ORD_MAXV) be.launch(MAXV <= REV_ORD_MIDV ? KN_REV_FILL_ORD_S : KN_REV_FILL_ORD, C, AASM_WAVE, w);
+        if (f.rev_fill == KN_REV_FILL_ORD_S || f.rev_fill == KN_REV_FILL_ORD) be.launch(f.rev_fill, C, AASM_WAVE, w);
         else {
-            if (ET > 6 * VT) be.launch(KN_REV_FILL_W, cdiv(VT, AASM_WAVE), AASM_WAVE, w);   // dense: lanes over the edges of 64 rows
+            if (f.rev_fill == KN_REV_FILL_W) be.launch(KN_REV_FILL_W, cdiv(VT, AASM_WAVE), AASM_WAVE, w);
             else be.launch(KN_REV_FILL, cdiv(VT, 256), 256, w);
             be.launch(KN_SORT_ROWS_REV, cdiv(VT, AASM_WAVE), AASM_WAVE, w);
         }
@@ -294,15 +344,12 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         A(tp_deg, int32_t, VT, "tp_deg"); A(tp_vj, int32_t, VT, "tp_vj"); A(tp_ptr, int64_t, VT + 1, "tp_ptr");
         A(te_pk, I4, ET, "te_pk");
         CHECK_ALLOC();
-        // big sparse batches (mean degree <= 6, thousands of contigs: bound by instruction issue): two contigs per wave,
-        // AASM_SWEEP_G lanes each; dense ones and small batches (bound by the chain per contig): a wave per contig
-        const bool grouped = ET <= 6 * VT && C >= AASM_GROUPED_MIN;            // (few contigs: a wave each - the scalar-uniform variant has the shorter chain per pop)
         const int64_t sweep_n = AASM_WAVE / AASM_SWEEP_G;
         auto side_work = [&]() {
             be.fork();                                               // side stream waits for everything enqueued so far
             be.use_side(true);
             be.phase_begin(AASM_PH_FWD);
-            if (grouped) be.launch(KN_FWD_SWEEP_G, cdiv(C, sweep_n), AASM_WAVE, w);
+            if (f.grouped) be.launch(KN_FWD_SWEEP_G, cdiv(C, sweep_n), AASM_WAVE, w);
             else be.launch(KN_FWD_SWEEP, C, AASM_WAVE, w);
             be.phase_end(AASM_PH_FWD);
             be.phase_begin(AASM_PH_TOPO);
@@ -318,7 +365,6 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         // ---- K7's arrays (the chain class fills them while its sweep still runs, so they exist before any sweep starts)
         A(ccnt, int32_t, VT, "ccnt"); A(cval, int32_t, ET, "cval");
         A(st_cost, Dist, ET, "st_cost"); A(st_n, int32_t, VT, "st_n"); A(vhdr, I4, VT, "vhdr"); A(vhdr2, I4, VT, "vhdr2"); A(cinfo, I4, ET, "cinfo"); A(tnx, I4, VT, "tnx"); A(tnx16, int32_t, 16 * VT, "tnx16");
-        const int64_t HT = hh[0], HTM = hh[1], NMW = HTM > 0 ? hh[2] : 0;
         sz.HT = HT;
         w.avg_sidetracks = (int32_t)std::min<int64_t>((ET - VT + C) / (C > 0 ? C : 1), INT32_MAX);
         A(hnodes, HNode, HT, "hnodes"); A(h_root, int32_t, VT, "h_root"); A(bq, int32_t, VT, "bq");
@@ -335,14 +381,14 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             be.fork2();
             be.use_side2(true);
             be.phase_begin(AASM_PH_CHAIN);
-            if (w.chain_ord) be.launch(KN_CHAIN, NCHAIN, AASM_WAVE * CHAIN_WAVES, w);
+            if (f.chain == KN_CHAIN) be.launch(KN_CHAIN, NCHAIN, AASM_WAVE * CHAIN_WAVES, w);
             else be.launch(KN_CHAIN3, NCHAIN, AASM_WAVE * (CHAIN_WAVES - 1), w);   // (no order wave: three waves a contig, five workgroups a CU; 1 250 contigs 4.6 ms where four-wave workgroups took 6.0)
             be.phase_end(AASM_PH_CHAIN);
             be.use_side2(false);
         }
         if (NCHAIN < C) {
         be.phase_begin(AASM_PH_SPTREE);
-        if (grouped) be.launch(KN_REV_SWEEP_G, cdiv(C, sweep_n), AASM_WAVE, w);
+        if (f.grouped) be.launch(KN_REV_SWEEP_G, cdiv(C, sweep_n), AASM_WAVE, w);
         else be.launch(KN_REV_SWEEP, C, AASM_WAVE, w);
         be.phase_end(AASM_PH_SPTREE);
 
@@ -358,7 +404,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         }
         be.use_side(false);
         be.phase_begin(AASM_PH_HEAP_PREP);
-        if (ET > 6 * VT) {
+        if (f.dense) {
             be.launch(KN_CHILDREN, cdiv(VT, 256), 256, w);
             be.launch(KN_SIDETRACK_W, cdiv(VT, AASM_WAVE), AASM_WAVE, w);   // dense: lanes over the edges of 64 rows
             be.launch(KN_HEAP_HDR, cdiv(VT, 256), 256, w);
@@ -370,24 +416,19 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         be.join();
         be.phase_begin(AASM_PH_HEAP);
         be.launch(KN_HEAP, C, AASM_WAVE, w);
-        // contigs of the wide-tree class (kb_heap skips them): 16, 8 or 4 waves each, by how many of them share the chip's ~8 k wave slots
+        // contigs of the wide-tree class (kb_heap skips them)
         w.mw_n = (int32_t)NMW; w.mw_base = -1;
         if (HTM > 0) {
-            const int hook = (opts.reserved[0] >> 8) & 0xff;         // probes: 1 = input order; 4 / 8 / 16 = that many waves per contig
-            const int mw = (hook == 4 || hook == 8 || hook == 16) ? hook : NMW * 16 <= 6144 ? 16 : NMW * 8 <= 6144 ? 8 : 4;
-            const int kn = mw == 16 ? KN_HEAP_MW16 : mw == 8 ? KN_HEAP_MW8 : KN_HEAP_MW;
             // One block per contig of the class, the contig with the largest node bound first: block times of a dense batch go with the
             // node count (C5 share: mean 25 ms, longest 42), and in input order the heavy ones land on the CUs as they come - clumps of them
             // share a CU's issue slots and the launch ends with such a clump.  Largest first deals every CU a spread of weights and
             // starts the longest chains first: C5 share 35.5 -> 30.0 ms, 700 contigs 27.3 -> 25.5, 400 x 1 500 records 25.1 -> 22.8.
-            // opts.reserved[0] bits 8-15 == 1 (probes): input order, a block per contig of the batch.
-            const bool by_list = hook != 1 && NMW >= 2 && NMW <= 32768;  // (ranked by counting: NMW^2 compares)
-            if (by_list) {
+            if (f.mw_ranked) {
                 be.launch(KN_MW_RANK, cdiv(NMW, 256), 256, w);
                 w.mw_base = 0;
-                { const int32_t xm = w.xcd_map; w.xcd_map = 0; be.launch(kn, NMW, AASM_WAVE * mw, w); w.xcd_map = xm; }   // (its order is its own)
+                { const int32_t xm = w.xcd_map; w.xcd_map = 0; be.launch(f.mw_kern, NMW, AASM_WAVE * f.mw_waves, w); w.xcd_map = xm; }   // (its order is its own)
                 w.mw_base = -1;
-            } else be.launch(kn, C, AASM_WAVE * mw, w);
+            } else be.launch(f.mw_kern, C, AASM_WAVE * f.mw_waves, w);
         }
         be.phase_end(AASM_PH_HEAP);
         }                                                            // (NCHAIN < C)
@@ -396,17 +437,11 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         // ---- K8 enumeration
         const int64_t K = w.K;
         A(kd, Dist, C * K, "kd"); A(klast, int32_t, C * K, "klast");
-        // queue form: sorted front + sorted runs (aasm_enum.h) unless a contig is too long for its packed ratio key; reserved[0] bit 3
-        // (tests) forces the d-ary heap form, which is also what the 1-lane host emulation runs
-        const bool enum_heap = B::host_emulation || (opts.reserved[0] & 8) != 0 || hh[3] > AASM_ENUM_MAX_N;
-        w.pq_stride = enum_heap ? 3 * K + 1 : enum_stride(K);
+        w.pq_stride = f.enum_kern == KN_ENUM_HEAP ? 3 * K + 1 : enum_stride(K);
         A(kcand, I4, 2 * C * (3 * K + 1), "kcand"); A(pq, PqK, C * w.pq_stride, "pq");
         CHECK_ALLOC();
         be.phase_begin(AASM_PH_ENUM);
-        // more contigs than the 64-entry front keeps resident (14 waves per CU = 3 584): the 40-entry front (20 per CU = 5 120) runs them
-        // in one residency round (round 4, with the far tier: 5 000 contigs 23.85 -> 23.1 ms; round 3, without it, the extra refills and
-        // flushes of the small front cost more than the second round: 30.2 vs 31.5 ms); beyond 5 120 both take a second round
-        be.launch(enum_heap ? KN_ENUM_HEAP : ((C > 14 * 256 && C <= 20 * 256 && K > 21) || (opts.reserved[0] & 16)) ? KN_ENUM_S : KN_ENUM, C, AASM_WAVE, w);
+        be.launch(f.enum_kern, C, AASM_WAVE, w);
         be.phase_end(AASM_PH_ENUM);
     }
 
@@ -414,12 +449,12 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     // ---- K9 selection (also emits the N == 1 contigs)
     // Default: plan -> one wave per converted path -> per-contig final pick.  Falls back to the
     // sequential one-wave-per-contig kernel when the per-conversion scratch would not fit
-    // (tie-heavy inputs at large K) or when opts.reserved[0] bit 0 asks for it (tests).
+    // (tie-heavy inputs at large K) or when AASM_H0_SEQ_SELECT asks for it (tests).
     A(mark_time, int32_t, R, "mark_time");
     A(conv_off, int64_t, C + 1, "conv_off"); A(plan_kk, int32_t, C * 2 * SEL_PLAN_KEEP, "plan_kk");
     CHECK_ALLOC();
     be.fill_byte(w.mark_time, 0x7F, sizeof(int32_t) * (size_t)R);
-    bool sequential = (opts.reserved[0] & 1) != 0;
+    bool sequential = h.seq_select;
     int64_t NCONV = 0, SR = 0, SV = 0;
     bool nm_ready = false;                                           // the output totals have been read with the pick's pool demand
     int64_t nm[2] = {0, 0};

@@ -86,34 +86,37 @@ typedef struct aasm_opts {
     int32_t device;            /* HIP device ordinal                                  */
     int32_t collect_timing;    /* 1: bracket every kernel with HIP events            */
     int32_t keep_debug;        /* 1: keep device intermediates for aasm_debug_fetch   */
-    int32_t reserved[3];       /* test hooks, 0 in production:
-                                * [0] bit 0: force the sequential selection kernel; bit 1: build every contig's heaps with the
-                                *            several-waves-per-contig kernel; bit 2: none of them (default: by graph density);
-                                *            bit 3: K8 on the d-ary heap queue (cross-check of the default sorted-front / sorted-runs queue);
-                                *            bit 4: K8 with the 40-entry front it takes for batches of more than 3 584 contigs
-                                *            bit 5: workgroups take their work items in grid order (default: XCD by XCD, aasm_gpu.hip)
-                                *            bit 6: every sparse contig in the chain class (aasm_k67_chain: sweep, pre-pass and heaps of a contig
-                                *            beside each other in one workgroup); bit 7: none; both: the contigs of at least the batch's mean size (default: small
-                                *            batches and the long tail of big ones)
-                                *            bits 8-15: 1 = the several-waves heap kernel launched in input order, a block per contig of
-                                *            the batch (default: a block per contig of its class, largest node bound first); 4 / 8 / 16 =
-                                *            that many waves per contig of the class (default: by how many contigs share the chip)
-                                *            bit 16: rows, reversed CSR and sweep headers by the separate launches even where every contig is small
-                                *            enough for one workgroup to build its graph (aasm_k46_graph)
-                                * [1] > 0:   pretend that contig ranges longer than this do not fit in device
-                                *            memory (exercises the range split of aasm_solve_batch)
-                                * [2] bit 0: inject one failing kernel launch (must surface as AASM_E_HIP);
-                                *     bit 1: aasm_solve_batch_multi wraps device ordinals around the devices that exist;
-                                *     bit 2: the next scan finds its ticket counter as an aborted launch would leave it (its look-back
-                                *            must give up after 10 s with AASM_E_HIP, and the next solve on the context must succeed);
-                                *     bit 3: the chain class's pre-pass wave of contig 0 never publishes the root's header (the contig must end with
-                                *            AASM_E_INTERNAL, nothing may hang); bit 4: ... and never reports that it is done (the heap wave gives up
-                                *            after 1 s instead of its 30 s);
-                                *     bit 5: the chain class's heap wave keeps its own BFS queue (default: the order comes from a wave of its
-                                *            own while the class has at most 896 contigs); bit 6: its ring of parents' roots has 4 entries, not 512;
-                                *     bits 8-15: d + 1 = the sort replay of duplicate-key contigs takes its heap sort
-                                *            fallback after d partition levels instead of 2 lg N                          */
+    int32_t reserved[3];       /* test hooks, 0 in production: see AASM_H0_* below  */
 } aasm_opts;
+
+/* Test hooks in aasm_opts.reserved: each forces one launch form (tests cross-check it against the default) or one fault path.
+ * A multi-bit field is (word & MASK) >> SHIFT.  Word 1 > 0: contig ranges longer than this "do not fit" (aasm_solve_batch's range split). */
+#define AASM_H0_SEQ_SELECT       0x1      /* K9 by the sequential selection kernel (default: plan-based)                     */
+#define AASM_H0_HEAP_MW_ALL      0x2      /* K7: every contig's heaps by the several-waves-per-contig kernel                 */
+#define AASM_H0_HEAP_MW_NONE     0x4      /* K7: none of them (default: by graph density)                                    */
+#define AASM_H0_ENUM_HEAP        0x8      /* K8 on the d-ary heap queue (default: sorted front + sorted runs)                */
+#define AASM_H0_ENUM_SMALL       0x10     /* K8 with the 40-entry front (default: for 14 * 256 < contigs <= 20 * 256, K > 21) */
+#define AASM_H0_GRID_ORDER       0x20     /* workgroups take their work items in grid order (default: XCD by XCD)            */
+#define AASM_H0_CHAIN_MASK       0xC0     /* the chain class (aasm_k67_chain; default: small batches, the long tail of big ones): */
+#define AASM_H0_CHAIN_ALL        0x40     /*   every sparse contig                                                           */
+#define AASM_H0_CHAIN_NONE       0x80     /*   none                                                                          */
+#define AASM_H0_CHAIN_HALF       0xC0     /*   the contigs of at least the batch's mean size                                 */
+#define AASM_H0_MW_MASK          0xFF00   /* K7's several-waves kernel (default: ranked, largest node bound first; waves per contig by
+                                             how many contigs share the chip): 4 / 8 / 16 waves per contig, or ...          */
+#define AASM_H0_MW_INPUT_ORDER   1        /*   input order, a block per contig of the batch                                  */
+#define AASM_H0_MW_SHIFT         8
+#define AASM_H0_GRAPH_LAUNCHES   0x10000  /* rows, reversed CSR and sweep headers by the separate launches (default: aasm_k46_graph
+                                             for the contigs small enough)                                                   */
+#define AASM_H2_LAUNCH_FAILURE   0x1      /* inject one failing kernel launch (must surface as AASM_E_HIP)                   */
+#define AASM_H2_WRAP_DEVICES     0x2      /* aasm_solve_batch_multi wraps device ordinals around the devices that exist      */
+#define AASM_H2_DIRTY_SCAN       0x4      /* the next scan's ticket counter as an aborted launch leaves it (AASM_E_HIP after 10 s) */
+#define AASM_H2_CHAIN_HDR_LOST   0x8      /* the chain class's pre-pass wave of contig 0 never publishes the root's header   */
+#define AASM_H2_CHAIN_DONE_LOST  0x10     /* ... nor that it is done (AASM_E_INTERNAL for the contig, nothing may hang)      */
+#define AASM_H2_CHAIN_OWN_QUEUE  0x20     /* the chain class's heap wave keeps its own BFS queue (default: the order from a wave of
+                                             its own while the class has at most AASM_CHAIN_ORD_MAX contigs)                 */
+#define AASM_H2_SMALL_ROOT_RING  0x40     /* that heap wave's ring of parents' roots has 4 entries, not 512                  */
+#define AASM_H2_SORT_DEPTH_MASK  0xFF00   /* d + 1: the sort replay takes its heap sort fallback after d partition levels    */
+#define AASM_H2_SORT_DEPTH_SHIFT 8
 
 /* ---- output ---------------------------------------------------------------------
  * One element == one PafOutputData (src/paf_data.hpp:90-105).                      */
@@ -268,7 +271,7 @@ int  aasm_debug_predicates(const int64_t *a, const int64_t *b, int64_t n, uint8_
 /* Test entry for hazard B1: K1's replay of libstdc++'s std::sort (paf_data.cpp:241-246 sorts with an unstable sort, so the
  * order of records with equal (qry_str, qry_end) is whatever that algorithm leaves) alone, on arbitrary keys.
  * rec_off[n_contigs + 1] starts at 0; perm_out[rec_off[c] + r] = the input index, relative to contig c, that ends at
- * sorted position r.  depth_test: 0, or d + 1 for a depth limit of d partition levels (as aasm_opts.reserved[2] bits 8-15). */
+ * sorted position r.  depth_test: 0, or d + 1 for a depth limit of d partition levels (as AASM_H2_SORT_DEPTH_MASK). */
 int  aasm_debug_sort_replay(const int64_t *rec_off, int64_t n_contigs, const int64_t *qs, const int64_t *qe, int32_t *perm_out,
                             int depth_test, int device);
 

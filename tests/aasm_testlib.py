@@ -10,11 +10,12 @@ and the PRODUCT through alignasm_amd.api (libalignasm_amd.so, C-ABI).
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
 
-from alignasm_amd._abi import BatchOut, HostBatch, Opts, unpack_out
+from alignasm_amd._abi import BatchOut, HostBatch, Opts, make_opts, unpack_out
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(ROOT, "oracle", "liboracle.so")
@@ -56,6 +57,7 @@ def emul():
         lib = C.CDLL(_ensure(EMUL_SO, os.path.join(ROOT, "tests", "host_emul")))
         lib.emul_debug_fetch.restype = C.c_int64
         lib.emul_last_bad_record.restype = C.c_int64
+        lib.emul_launch_log.restype = C.c_int64
         _cache["e"] = lib
     return _cache["e"]
 
@@ -300,10 +302,9 @@ def oracle_solve(hb: HostBatch, K=10000, nsl=False, threads=4):
         oracle().oracle_free_out(C.byref(out))
 
 
-def emul_solve(hb: HostBatch, K=10000, nsl=False, sequential_select=False, heap_waves="auto", heap_input_order=False, chain="auto", graph_launches=False, chain_own_queue=False, test_small_root_ring=False):
-    o = Opts(int(K), 1 if nsl else 0, 0, 0, 1)
-    o.reserved[0] = (1 if sequential_select else 0) | {"auto": 0, "all": 2, "none": 4}[heap_waves] | ((1 << 8) if heap_input_order else 0) | {"auto": 0, "all": 64, "none": 128, "half": 192}[chain] | ((1 << 16) if graph_launches else 0)
-    o.reserved[2] = (32 if chain_own_queue else 0) | (64 if test_small_root_ring else 0)
+def emul_solve(hb: HostBatch, K=10000, nsl=False, **hooks):
+    """The emulated solve (keep_debug on); hooks: alignasm_amd._abi.HOOKS."""
+    o = make_opts(K, nsl, 0, False, True, **hooks)
     out = BatchOut()
     rc = emul().emul_solve_batch(C.byref(hb.view), C.byref(o), C.byref(out))
     assert rc == 0, rc
@@ -311,6 +312,22 @@ def emul_solve(hb: HostBatch, K=10000, nsl=False, sequential_select=False, heap_
         return unpack_out(out)
     finally:
         emul().emul_free_out(C.byref(out))
+
+
+def kernel_ids():
+    """{"KN_...": id} of the pipeline's kernel enum (aasm_pipeline.h)."""
+    src = open(os.path.join(ROOT, "alignasm_amd", "csrc", "aasm_pipeline.h")).read()
+    body = re.search(r"enum Kern \{(.*?)\};", src, re.S).group(1)
+    return {name: i for i, name in enumerate(re.findall(r"\b(KN_\w+)", body))}
+
+
+def emul_launches():
+    """The last emulated solve's launches, in order: (kernel name, blocks, threads)."""
+    n = emul().emul_launch_log(None, C.c_int64(0))
+    buf = np.zeros(3 * n, np.int64)
+    emul().emul_launch_log(_P(buf), C.c_int64(len(buf)))
+    names = {i: name for name, i in kernel_ids().items()}
+    return [(names[int(k)], int(b), int(t)) for k, b, t in buf.reshape(-1, 3)]
 
 
 def k0_ranges(fetch):

@@ -22,6 +22,7 @@ struct EmuBackend {
     std::vector<void *> blocks;
     std::map<std::string, std::pair<void *, size_t>> named;
     bool fail = false;
+    std::vector<int64_t> launches;                 // (kernel id, blocks, threads) of every launch, in order
     ~EmuBackend() { for (void *p : blocks) free(p); }
     void *alloc(const char *name, size_t bytes) {
         void *p = malloc(bytes + 64);
@@ -38,6 +39,7 @@ struct EmuBackend {
     void fill_ff(void *p, size_t n) { memset(p, 0xFF, n); }
     void fill_byte(void *p, int v, size_t n) { memset(p, v, n); }
     void launch(int kn, int64_t nblocks, int nthreads, const WS &w) {
+        launches.insert(launches.end(), {kn, nblocks, nthreads});
         if (nthreads > 1024) return;                // (the injected bad launch of the GPU tests: nothing to emulate)
         for (int64_t b = 0; b < nblocks; b++) {
             // one logical thread per block slot: bodies index with bid*nthreads+tid
@@ -97,6 +99,17 @@ int emul_solve_batch(const aasm_batch_in *in, const aasm_opts *opts, aasm_batch_
     g_bad_record = sz.bad_record;
     if (rc != AASM_OK) return rc;
     return fetch_results(*g_be, g_ws, sz, out);
+}
+// the last solve's launch log: 3 int64 per launch (kernel id, blocks, threads); returns the launch count
+int64_t emul_launch_log(int64_t *dst, int64_t cap) {
+    if (!g_be) return 0;
+    const std::vector<int64_t> &l = g_be->launches;
+    if (dst) memcpy(dst, l.data(), sizeof(int64_t) * std::min<size_t>((size_t)cap, l.size()));
+    return (int64_t)l.size() / 3;
+}
+// K8's queue as run_pipeline picks it for a device (choose_forms, host_emulation off): the kernel id
+int emul_k8_form(int64_t C, int64_t K, int64_t max_records, const aasm_opts *opts) {
+    return choose_forms({C, C, K, 1, 1, 1, 0, 0, 0, max_records}, decode_hooks(*opts), false).enum_kern;
 }
 void emul_free_out(aasm_batch_out *out) {
     if (!out) return;

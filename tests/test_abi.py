@@ -88,3 +88,37 @@ def test_range_solve_and_writer_session_reject_misuse(T, tmp_path):
         assert open(a, "rb").read() == open(b, "rb").read()
     assert sorted(p.name for p in tmp_path.iterdir()) == ["a.paf", "a1.paf", "l.paf", "l1.paf", "m.paf", "m1.paf"]
     T.oracle().oracle_free_out(C.byref(sol))
+
+
+def test_hook_constants_match_header():
+    """The test hooks' names and values in include/alignasm_amd.h and in alignasm_amd/_abi.py are the same."""
+    from alignasm_amd import _abi
+    src = open(os.path.join(ROOT, "include", "alignasm_amd.h")).read()
+    hdr = {n: int(v, 0) for n, v in re.findall(r"#define\s+(AASM_H[0-9]_\w+)\s+(0x[0-9A-Fa-f]+|\d+)", src)}
+    assert len(hdr) == 23
+    assert hdr == _abi.HOOK_CONSTANTS
+
+
+def test_hook_encoder_rejects_unknown_hooks_and_values(T):
+    """make_opts packs hooks by name; an unknown name is a TypeError, an unknown value a ValueError, at every entry point."""
+    import types
+    from alignasm_amd import _abi
+    api = T.api()
+    o = _abi.make_opts(16, chain="half", heap_input_order=True, test_max_contigs=7, test_chain_lost=2, sort_depth_test=3, graph_launches=True)
+    assert list(o.reserved) == [0xC0 | 1 << 8 | 0x10000, 7, 0x10 | 3 << 8]
+    assert list(_abi.make_opts(heap_block_waves=8, enum_small=True).reserved) == [8 << 8 | 0x10, 0, 0]
+    assert list(_abi.make_opts().reserved) == [0, 0, 0]
+    with pytest.raises(TypeError):
+        _abi.make_opts(no_such_hook=True)
+    for bad in (dict(chain="foo"), dict(heap_waves="some"), dict(heap_block_waves=2), dict(test_chain_lost=3), dict(sort_depth_test=256),
+                dict(heap_input_order=True, heap_block_waves=4)):
+        with pytest.raises(ValueError):
+            _abi.make_opts(**bad)
+    hb = T.synth(2, 20, 1)
+    with pytest.raises(TypeError):
+        api.solve_batch(hb, max_paths=4, no_such_hook=True)
+    with pytest.raises(ValueError):
+        api.solve_batch(hb, max_paths=4, chain="foo")
+    for name in ("test_max_contigs", "wrap_devices"):                # (aasm_solve_device never reads them)
+        with pytest.raises(TypeError):
+            api.DeviceBatch.solve(types.SimpleNamespace(device=0), max_paths=4, **{name: 1})

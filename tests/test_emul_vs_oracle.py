@@ -73,7 +73,7 @@ def test_chain_class_forms(T, case, chain):
     nc, nr, seed, K, dense, dup, shuf, heavy, nsl = case
     hb = T.synth(nc, nr, seed, dense=dense, dup_every=dup, shuffle=shuf, heavy_tail=heavy)
     want = T.oracle_solve(hb, K, nsl)
-    got = T.emul_solve(hb, K, nsl, chain=chain, chain_own_queue=True)   # the heap wave with its own BFS queue (the form for classes of more than 896 contigs)
+    got = T.emul_solve(hb, K, nsl, chain=chain, chain_own_queue=True)   # the heap wave with its own BFS queue (the form for classes of more than AASM_CHAIN_ORD_MAX contigs)
     assert T.diff_outputs(want, got) == []
     assert T.diff_intermediates(hb, T.emul_debug, K, nsl) == []
     got = T.emul_solve(hb, K, nsl, chain=chain)                          # the order from a wave of its own (default)
@@ -134,3 +134,54 @@ def test_all_pool_overflow_reruns_the_pick(T):
     want = T.oracle_solve(hb, 10000)
     assert len(want["all"]) > len(hb.arrays["qry_str"]) + 1024
     assert T.diff_outputs(want, T.emul_solve(hb, 10000)) == []
+
+
+def test_hooks_select_the_forms_they_name(T):
+    """Each hook launches the form it names, and the batch shapes at the thresholds pick theirs (the emulation's launch log:
+    kernel, blocks, threads, in launch order)."""
+    def kernels(hb, K=16, **hooks):
+        T.emul_solve(hb, K, **hooks)
+        return [name for name, _, _ in T.emul_launches()]
+    hb = T.synth(10, 100, 1)
+    ks = kernels(hb)
+    assert "KN_CHAIN" in ks and "KN_SEL_PLAN" in ks and "KN_SELECT" not in ks
+    assert "KN_CHAIN" in kernels(hb, chain="all")
+    assert not {"KN_CHAIN", "KN_CHAIN3"} & set(kernels(hb, chain="none"))
+    ks = kernels(hb, chain_own_queue=True)
+    assert "KN_CHAIN3" in ks and "KN_CHAIN" not in ks
+    ks = kernels(hb, graph_launches=True)
+    assert "KN_ROW_FILL" in ks and not [k for k in ks if k.startswith("KN_GRAPH")]
+    assert "KN_GRAPH" in kernels(hb)
+    ks = kernels(hb, heap_waves="all")
+    assert [k for k in ks if k.startswith("KN_HEAP_MW")] and "KN_MW_RANK" in ks
+    ks = kernels(hb, heap_waves="all", heap_input_order=True)
+    assert [k for k in ks if k.startswith("KN_HEAP_MW")] and "KN_MW_RANK" not in ks
+    ks = kernels(hb, sequential_select=True)
+    assert "KN_SELECT" in ks and not [k for k in ks if k.startswith("KN_SEL_")]
+    # a class of 1 025 - 1 536 small contigs: the chain kernel without the order wave (AASM_CHAIN_ORD_MAX = 1 024)
+    ks = kernels(T.synth(1100, 12, 5), 4)
+    assert "KN_CHAIN3" in ks and "KN_CHAIN" not in ks
+    # tiny sparse contigs: the grouped sweeps from AASM_GROUPED_MIN = 2 560 contigs on
+    ks = kernels(T.synth(2560, 3, 7), 4)
+    assert "KN_REV_SWEEP_G" in ks and "KN_FWD_SWEEP_G" in ks
+    ks = kernels(T.synth(2559, 3, 7), 4)
+    assert not {"KN_REV_SWEEP_G", "KN_FWD_SWEEP_G"} & set(ks) and "KN_REV_SWEEP" in ks and "KN_FWD_SWEEP" in ks
+
+
+def test_k8_queue_form_table(T):
+    """K8's queue as the pipeline picks it for a device (the emulation itself always runs the d-ary heap): the 40-entry front for
+    14 * 256 < contigs <= 20 * 256 at K > 21, and the two K8 hooks."""
+    import ctypes as C
+    from alignasm_amd._abi import make_opts
+    ids = T.kernel_ids()
+    F, S, H = ids["KN_ENUM"], ids["KN_ENUM_S"], ids["KN_ENUM_HEAP"]
+
+    def form(c, k, max_records=100, **hooks):
+        return T.emul().emul_k8_form(C.c_int64(c), C.c_int64(k), C.c_int64(max_records), C.byref(make_opts(k, **hooks)))
+    edges = (14 * 256, 14 * 256 + 1, 20 * 256, 20 * 256 + 1)
+    assert [form(c, 22) for c in edges] == [F, S, S, F]
+    assert [form(c, 21) for c in edges] == [F, F, F, F]
+    assert [form(c, 21, enum_small=True) for c in edges] == [S, S, S, S]
+    assert [form(c, 22, enum_heap=True) for c in edges] == [H, H, H, H]
+    assert form(4000, 22, enum_heap=True, enum_small=True) == H
+    assert form(4000, 22, max_records=(1 << 20) - 1) == H                # longer than the packed ratio key allows (AASM_ENUM_MAX_N)

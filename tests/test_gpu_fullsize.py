@@ -220,7 +220,7 @@ def _mixed_file(T):
 def test_in_process_multi_device_path_on_the_devices_that_exist(T, n_dev):
     """aasm_solve_batch_multi with n_devices > 1 (alignasm.cpp:351-359: one task per contig -> one thread + stream per device
     block): the thread-per-shard path, the cost-balanced cuts and the concatenation, with device ordinals wrapped around the
-    devices of this box (opts.reserved[2] bit 1), against the oracle on a heavy-tailed + mixed dense / sparse file."""
+    devices of this box (AASM_H2_WRAP_DEVICES), against the oracle on a heavy-tailed + mixed dense / sparse file."""
     api = T.api()
     hb = _mixed_file(T)
     want = T.oracle_solve(hb, 16)

@@ -126,7 +126,7 @@ def test_chain_class_forms_leave_the_same_intermediates(T, case, chain):
     api = T.api()
     hb = T.synth(nc, nr, seed, dense=dense, dup_every=dup, shuffle=shuf, heavy_tail=heavy)
     db = api.DeviceBatch(hb)
-    for own_queue in (True, False):                                 # the heap wave with its own BFS queue / the order from a wave of its own (default up to 896 contigs)
+    for own_queue in (True, False):                                 # the heap wave with its own BFS queue / the order from a wave of its own (default up to AASM_CHAIN_ORD_MAX contigs)
         res = db.solve(max_paths=K, non_skip_linkable=nsl, keep_debug=True, chain=chain, chain_own_queue=own_queue)
         assert T.diff_intermediates(hb, res.debug, K, nsl) == []
         res.close()
@@ -156,7 +156,7 @@ def test_chain_class_beyond_one_residency_round_and_as_the_long_tail(T):
 @pytest.mark.parametrize("own_queue", [False, True], ids=["order_wave", "own_queue"])
 @pytest.mark.parametrize("how", [1, 2], ids=["header_never_comes", "prep_wave_never_reports"])
 def test_chain_class_waits_end_in_an_error_not_a_hang(T, how, own_queue):
-    """Every wait of aasm_k67_chain has an exit every wave reaches.  Test hooks (opts.reserved[2] bits 3 / 4): the pre-pass wave of
+    """Every wait of aasm_k67_chain has an exit every wave reaches.  Test hooks (AASM_H2_CHAIN_HDR_LOST / AASM_H2_CHAIN_DONE_LOST): the pre-pass wave of
     contig 0 never publishes the root's header - the heap wave learns from `prep_done` that it will not come; or it does not even
     report that it is done - the heap wave's own patience (1 s under the hook, 30 s otherwise) ends the wait.  Either way contig 0
     ends with AASM_E_INTERNAL, every other contig with the oracle's result, the launch drains, and the next solve is clean."""
@@ -198,7 +198,7 @@ def test_repeat_solve_is_deterministic(T):
 
 def test_out_of_memory_ranges_are_split_and_concatenated(T):
     """A contig range that does not fit is halved recursively (contigs are independent); the
-    concatenated result must equal the unsplit one.  opts.reserved[1] simulates the
+    concatenated result must equal the unsplit one.  The range-limit hook simulates the
     out-of-memory hipMalloc."""
     api = T.api()
     hb = T.synth(23, 70, 41, heavy_tail=True, dup_every=6)
@@ -227,7 +227,7 @@ def test_hip_failure_is_reported_not_retried_as_out_of_memory(T):
 
 def test_stalled_scan_look_back_ends_in_an_error_not_a_hang(T):
     """aasm_scan_chain's look-back waits for predecessors that took their ticket earlier; a ticket counter left behind by an
-    aborted launch (test hook: opts.reserved[2] bit 2 dirties it ahead of the first scan) means a predecessor that never
+    aborted launch (test hook: AASM_H2_DIRTY_SCAN dirties it ahead of the first scan) means a predecessor that never
     publishes.  The lanes give up after SCAN_STALL_S seconds, raise a host-visible flag, the launch drains, the solve
     returns AASM_E_HIP before anything is sized by the scan - and the context is clean for the next solve."""
     import time
