@@ -109,6 +109,17 @@ class BatchOut(C.Structure):
     ]
 
 
+class OutSizes(C.Structure):
+    """aasm_out_sizes: the sizes of a result's arrays (aasm_result_sizes)."""
+    _fields_ = [(n, C.c_int64) for n in ("n_contigs", "n_main", "n_alt", "n_all_paths", "n_all_elems")]
+
+
+class DevOut(C.Structure):
+    """aasm_dev_out: caller-owned DEVICE arrays a result is exported into (aasm_result_export)."""
+    _fields_ = [(n, C.c_void_p) for n in ("main_off", "alt_off", "all_path_off", "all_elem_off", "main_elems", "alt_elems",
+                                          "all_elems", "ctg_status")]
+
+
 class SynthCfg(C.Structure):
     _fields_ = [
         ("n_contigs", C.c_int64), ("recs_per_contig", C.c_int64), ("seed", C.c_uint64), ("dense", C.c_int32),

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_OK, BatchIn, BatchOut, HostBatch, Opts, Stats, SynthCfg, make_opts, unpack_out)
+from ._abi import (AASM_E_INVAL, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, Opts, OutSizes, Stats, SynthCfg, make_opts, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AASM_LIB_OVERRIDE") or os.path.join(_HERE, "libalignasm_amd.so")   # override: diagnostic builds (tools/)
@@ -26,7 +26,33 @@ class AlignasmError(RuntimeError):
         self.code = code
 
 
+def _torch_hip_runtime():
+    """Path of the HIP runtime torch bundles (torch/lib/libamdhip64.so), or None; torch itself is not imported."""
+    import importlib.util
+    try:
+        spec = importlib.util.find_spec("torch")
+    except (ImportError, ValueError):
+        return None
+    for d in (spec.submodule_search_locations or []) if spec else []:
+        p = os.path.join(d, "lib", "libamdhip64.so")
+        if os.path.exists(p):
+            return p
+    return None
+
+
 def _load():
+    # ONE HIP runtime per process, by decision: where torch is installed, the library runs on the HIP runtime torch bundles, not
+    # on the ROCm install's it was linked against (both are soname libamdhip64.so.7; the bundled one may be an older minor
+    # version - torch 2.10.0+rocm7.0 ships HIP 7.0 beside ROCm 7.2 - which runs the gfx950 code objects unchanged).  The library
+    # needs libamdhip64.so.7; torch's libraries need "libamdhip64.so" from their own directory, a name the loader does not match
+    # against the soname of a runtime already loaded from the ROCm install, so loading this library first would give a process
+    # that later imports torch a second runtime, whose pointers and streams the first does not know.  Loading torch's copy
+    # first (by path, global symbols, torch itself not imported) makes it serve both: its soname satisfies the library, and
+    # torch's later load of the same file finds it mapped.  torch imported first: the runtime it loaded already serves the
+    # library.  No torch installed: the ROCm install's runtime.  INTEGRATION.md, "results on the device".
+    rt = _torch_hip_runtime()
+    if rt:
+        C.CDLL(rt, mode=C.RTLD_GLOBAL)
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"{LIB_PATH} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
@@ -50,6 +76,7 @@ EXPORTED = [
     "aasm_result_stats", "aasm_result_fetch", "aasm_result_free", "aasm_free_out", "aasm_upload_batch", "aasm_upload_free",
     "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
+    "aasm_result_sizes", "aasm_result_export",
 ]
 
 
@@ -227,7 +254,7 @@ class DeviceBatch:
         res = C.c_void_p()
         opts = make_opts(max_paths, non_skip_linkable, self.device, timing, keep_debug, **hooks)
         _check(LIB.aasm_solve_device(C.byref(self.dev_view), C.byref(opts), C.c_void_p(stream or 0), C.byref(res)))
-        return DeviceResult(res)
+        return DeviceResult(res, self.device)
 
     def close(self):
         if self._up:
@@ -242,8 +269,9 @@ class DeviceBatch:
 
 
 class DeviceResult:
-    def __init__(self, handle):
+    def __init__(self, handle, device=0):
         self._h = handle
+        self.device = device
 
     def stats(self):
         st = Stats()
@@ -263,6 +291,45 @@ class DeviceResult:
         _check(LIB.aasm_result_fetch(self._h, C.byref(out)))
         return out
 
+    def sizes(self):
+        """aasm_result_sizes: {n_contigs, n_main, n_alt, n_all_paths, n_all_elems} (counts the .all paths on the device; one small
+        read-back and a wait on the result's stream)."""
+        sz = OutSizes()
+        _check(LIB.aasm_result_sizes(self._h, C.byref(sz)))
+        return {n: int(getattr(sz, n)) for n, _ in OutSizes._fields_}
+
+    def export_raw(self, sizes: OutSizes, dst: DevOut, stream=0):
+        """aasm_result_export as is: returns the C-ABI code (0 = enqueued on `stream`, a hipStream_t handle or 0)."""
+        return int(LIB.aasm_result_export(self._h, C.byref(sizes), C.byref(dst), C.c_void_p(stream or 0)))
+
+    def to_torch(self, stream=None):
+        """The result in torch tensors on its device, packed there (aasm_result_export): the keys of unpack_out() without
+        `stats`; element lists are int64 [n, 5] tensors holding the 40-byte rows (column 4 is ctg_index / is_alt as two int32:
+        `.view(torch.int32)`).  Asynchronous on `stream` (default: the device's current torch stream); the tensors outlive the
+        next solve on the device."""
+        import torch
+        _check_one_hip_runtime()
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        sz = self.sizes()
+        c, npth = sz["n_contigs"], sz["n_all_paths"]
+        with torch.cuda.device(dev):
+            i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)   # noqa: E731
+            el = lambda n: torch.empty((n, 5), dtype=torch.int64, device=dev)   # noqa: E731
+            d = {"main_off": i64(c + 1), "alt_off": i64(c + 1), "all_path_off": i64(c + 1), "all_elem_off": i64(npth + 1),
+                 "main": el(sz["n_main"]), "alt": el(sz["n_alt"]), "all": el(sz["n_all_elems"]),
+                 "status": torch.empty(c, dtype=torch.int32, device=dev)}
+        # the caching allocator hands these blocks to other work once they are freed: tie them to the export's stream
+        for t in d.values():
+            t.record_stream(stream)
+        ptr = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
+        dst = DevOut(ptr(d["main_off"]), ptr(d["alt_off"]), ptr(d["all_path_off"]), ptr(d["all_elem_off"]), ptr(d["main"]),
+                     ptr(d["alt"]), ptr(d["all"]), ptr(d["status"]))
+        _check(self.export_raw(OutSizes(*(sz[n] for n, _ in OutSizes._fields_)), dst, stream.cuda_stream))
+        d["n_contigs"] = c
+        return d
+
     def debug(self, name, dtype):
         n = LIB.aasm_debug_fetch(self._h, name.encode(), None, C.c_int64(0))
         if n < 0:
@@ -281,3 +348,34 @@ class DeviceResult:
             self.close()
         except Exception:
             pass
+
+
+_ONE_RUNTIME = False
+
+
+def _check_one_hip_runtime():
+    """Torch's tensors and streams mean something to this library only when both use the same HIP runtime (see _load)."""
+    global _ONE_RUNTIME
+    if _ONE_RUNTIME:
+        return
+    try:
+        with open("/proc/self/maps") as f:
+            maps = set(line.split()[-1] for line in f if "libamdhip64" in line)
+    except OSError:
+        return
+    if len(maps) > 1:
+        raise AlignasmError(AASM_E_INVAL, "this process has two HIP runtimes mapped (%s): torch's tensors and streams cannot be "
+                            "handed to alignasm_amd; load the same libamdhip64 for both (INTEGRATION.md)" % ", ".join(sorted(maps)))
+    _ONE_RUNTIME = True
+
+
+def torch_to_numpy(d):
+    """DeviceResult.to_torch()'s dict -> unpack_out()'s numpy form (without `stats`).  The copies to the host are ordered on
+    the device's current torch stream: export on another stream, and that stream has to be waited for first."""
+    out = {"n_contigs": int(d["n_contigs"])}
+    for k in ("main_off", "alt_off", "all_path_off", "all_elem_off", "status"):
+        out[k] = d[k].cpu().numpy()
+    for k in ("main", "alt", "all"):
+        t = d[k].contiguous().cpu().numpy()
+        out[k] = np.ascontiguousarray(t).view(OUT_ELEM_DTYPE).reshape(-1) if t.size else np.zeros(0, OUT_ELEM_DTYPE)
+    return out

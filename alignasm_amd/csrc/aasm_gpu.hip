@@ -84,7 +84,7 @@ AASM_DEF_KERNEL(aasm_k9_tnx16, KN_TNX16, 256)
 AASM_DEF_KERNEL_LDS(aasm_k9_tnx16_wg, KN_TNX16_WG, TNX_TPB, AASM_TNXWG_LDS_BYTES, 4)   // the 16-hop jump records of a small contig from its tree in LDS
 AASM_DEF_KERNEL_LDS(aasm_k7_heap, KN_HEAP, 64, AASM_HEAP_LDS_BYTES, 5)
 AASM_DEF_KERNEL_LDS(aasm_k67_chain, KN_CHAIN, 64 * CHAIN_WAVES, AASM_CHAIN_LDS_BYTES, 5)   // sweep + pre-pass + BFS order + heaps of one contig, a wave each (96 VGPRs, 19 spilled: worth it for the fifth wave slot per SIMD)
-AASM_DEF_KERNEL_LDS(aasm_k67_chain3, KN_CHAIN3, 64 * (CHAIN_WAVES - 1), AASM_CHAIN_LDS_BYTES, 5)   // ... without the order wave (the heap wave keeps its own queue): classes of more than AASM_CHAIN_ORD_MAX contigs
+AASM_DEF_KERNEL_LDS(aasm_k67_chain3, KN_CHAIN3, 64 * (CHAIN_WAVES - 1), AASM_CHAIN_LDS_BYTES, 5)   // ... without the order wave (the heap wave keeps its own queue): classes of more than AASM_CHAIN_ORD_MAX (1 024) contigs
 AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw, KN_HEAP_MW, 256, AASM_MW_LDS_BYTES(4), 4)
 AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw8, KN_HEAP_MW8, 512, AASM_MW_LDS_BYTES(8), 4)
 AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw16, KN_HEAP_MW16, 1024, AASM_MW_LDS_BYTES(16), 4)
@@ -102,6 +102,16 @@ AASM_DEF_KERNEL(aasm_k9_sel_final, KN_SEL_FINAL, 64)
 AASM_DEF_KERNEL(aasm_k9_topo_count, KN_TOPO_COUNT, 256)
 AASM_DEF_KERNEL(aasm_k9_topo_fill, KN_TOPO_FILL, 64)
 AASM_DEF_KERNEL(aasm_k9_gather_out, KN_GATHER_OUT, 64)
+// the device-side export of a result (aasm_result_sizes / aasm_result_export; bodies kb_pack_*)
+#define AASM_DEF_PACK_KERNEL(name, KP)                                                        \
+    __global__ void __launch_bounds__(256) name(PackArgs a) {                                 \
+        KCtx k{(int)threadIdx.x, (int)blockDim.x, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr};   \
+        run_pack_body(KP, k, a);                                                              \
+    }
+AASM_DEF_PACK_KERNEL(aasm_pack_count, KP_COUNT)
+AASM_DEF_PACK_KERNEL(aasm_pack_place, KP_PLACE)
+AASM_DEF_PACK_KERNEL(aasm_pack_flat, KP_FLAT)
+AASM_DEF_PACK_KERNEL(aasm_pack_all, KP_ALL)
 
 // ---- T1 truth tables on the device (test entry aasm_debug_predicates) ------------------
 // One thread per pair (a, b) of 5-int64 PafDistance tuples {qry, ref, anom, qul_nonzero, qul_total}.
@@ -509,7 +519,14 @@ struct DevCtx {
     hipEvent_t *timing_event(int i) { return i < AASM_N_PHASES ? &ev_b[i] : i < 2 * AASM_N_PHASES ? &ev_e[i - AASM_N_PHASES] : i == 2 * AASM_N_PHASES ? &ev_t0 : &ev_t1; }
     bool events = false;
     size_t peak_bytes = 0;
+    std::vector<hipEvent_t> export_events;   // recorded behind each export in flight: the next reuse of the arena waits for them
 };
+
+// wait for the exports in flight (they read the arena); under cx.mu
+static void drain_exports(DevCtx &cx) {
+    for (hipEvent_t e : cx.export_events) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    cx.export_events.clear();
+}
 static DevCtx g_ctx[16];
 static std::mutex g_init_mu;
 static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0};
@@ -582,9 +599,13 @@ struct GpuBackend {
     size_t cur_block = 0, bytes = 0;
     std::map<std::string, std::pair<void *, size_t>> named;
     GpuBackend(DevCtx &c, hipStream_t s, bool t) : cx(c), stream(s), main_stream(s), timing(t) {
+        drain_exports(cx);
         for (auto &b : cx.blocks) b.used = 0;
         cx.generation++;
     }
+    // a backend on the CURRENT result's workspace (the export): allocates behind the solve's arrays, keeps the generation
+    struct Attach {};
+    GpuBackend(DevCtx &c, hipStream_t s, Attach) : cx(c), stream(s), main_stream(s), timing(false) {}
     void hip_fail(const char *what, hipError_t e) { if (!fail) set_last_error(hip_err(what, e)); fail = true; }
     void *alloc(const char *name, size_t n) {
         n = (n + 255) & ~(size_t)255;
@@ -691,6 +712,20 @@ struct GpuBackend {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) hip_fail("kernel launch", e);
     }
+    void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) {
+        flush_zero();
+        if (fail || nblocks <= 0) return;
+        dim3 g((unsigned)nblocks), b((unsigned)nthreads);
+        switch (kp) {
+            case KP_COUNT: hipLaunchKernelGGL(aasm_pack_count, g, b, 0, stream, a); break;
+            case KP_PLACE: hipLaunchKernelGGL(aasm_pack_place, g, b, 0, stream, a); break;
+            case KP_FLAT: hipLaunchKernelGGL(aasm_pack_flat, g, b, 0, stream, a); break;
+            case KP_ALL: hipLaunchKernelGGL(aasm_pack_all, g, b, 0, stream, a); break;
+            default: break;
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) hip_fail("kernel launch", e);
+    }
     template <class T> void scan_t(const T *in, int64_t n, int64_t *out) {
         flush_zero();
         if (fail) return;
@@ -791,6 +826,7 @@ struct aasm_result {
     aasm_stats stats;
     std::map<std::string, std::pair<void *, size_t>> named;
     hipStream_t stream;
+    PackWS pk;                           // scratch + sizes of the device-side export
 };
 
 // record (index in the batch handed to the failing solve) whose cs tag the device rejected
@@ -806,6 +842,7 @@ static int solve_on_device(DevCtx &cx, const aasm_batch_in &dev_in, const aasm_o
     if (timing) hipEventRecord(cx.ev_t0, stream);
     be->test_dirty_scan = decode_hooks(opts).dirty_scan;            // test hook: the next scan finds a ticket counter an aborted launch left behind
     int rc = run_pipeline(*be, dev_in, opts, res->w, res->sz);
+    if (rc == AASM_OK) rc = pack_alloc(*be, res->w, res->pk);       // the scratch of a later device-side export
     be->flush_zero();
     if (timing) hipEventRecord(cx.ev_t1, stream);
     be->join();
@@ -950,6 +987,72 @@ int aasm_result_fetch(aasm_result *res, aasm_batch_out *out) {
     st.total_ms = res->stats.total_ms; st.device_bytes = res->stats.device_bytes;
     std::memcpy(st.reserved_f, res->stats.reserved_f, sizeof(st.reserved_f));
     out->stats = st;
+    return AASM_OK;
+}
+
+// ---- results on the device (aasm_result_sizes / aasm_result_export) ----
+int aasm_result_sizes(aasm_result *res, aasm_out_sizes *sz) {
+    if (!res || !sz) return AASM_E_INVAL;
+    DevCtx &cx = g_ctx[res->device];
+    std::lock_guard<std::mutex> lk(cx.mu);
+    if (res->generation != cx.generation) { set_last_error("result was invalidated by a later solve on the same device"); return AASM_E_INVAL; }
+    hipSetDevice(res->device);
+    GpuBackend be(cx, res->stream, GpuBackend::Attach{});
+    const int rc = pack_sizes(be, res->w, res->pk);                 // (the first call ends in one read-back: a wait on the result's stream)
+    if (rc != AASM_OK) { if (rc == AASM_E_OVERFLOW) set_last_error("result too large for the device-side export"); return rc; }
+    sz->n_contigs = res->pk.sizes[0]; sz->n_main = res->pk.sizes[1]; sz->n_alt = res->pk.sizes[2];
+    sz->n_all_paths = res->pk.sizes[3]; sz->n_all_elems = res->pk.sizes[4];
+    return AASM_OK;
+}
+
+// a non-empty destination array: device memory of `device`, aligned to `align`
+static bool dev_buffer_ok(const void *p, int64_t n, size_t align, int device) {
+    if (n <= 0) return true;
+    if (!p || ((uintptr_t)p % align) != 0) return false;
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (unregistered host memory)
+    return at.type == hipMemoryTypeDevice && at.device == device;
+}
+
+int aasm_result_export(aasm_result *res, const aasm_out_sizes *sz, const aasm_dev_out *dst, void *stream) {
+    if (!res || !sz || !dst) return AASM_E_INVAL;
+    DevCtx &cx = g_ctx[res->device];
+    std::lock_guard<std::mutex> lk(cx.mu);
+    if (res->generation != cx.generation) { set_last_error("result was invalidated by a later solve on the same device"); return AASM_E_INVAL; }
+    const int64_t *k = res->pk.sizes;
+    if (!res->pk.sized || sz->n_contigs != k[0] || sz->n_main != k[1] || sz->n_alt != k[2] || sz->n_all_paths != k[3] || sz->n_all_elems != k[4]) {
+        set_last_error("sizes are not what aasm_result_sizes returned for this result");
+        return AASM_E_INVAL;
+    }
+    hipSetDevice(res->device);
+    const int dv = res->device;
+    const int64_t C = k[0];
+    if (!dev_buffer_ok(dst->main_off, C + 1, 8, dv) || !dev_buffer_ok(dst->alt_off, C + 1, 8, dv) || !dev_buffer_ok(dst->all_path_off, C + 1, 8, dv) ||
+        !dev_buffer_ok(dst->all_elem_off, k[3] + 1, 8, dv) || !dev_buffer_ok(dst->main_elems, k[1], 8, dv) || !dev_buffer_ok(dst->alt_elems, k[2], 8, dv) ||
+        !dev_buffer_ok(dst->all_elems, k[4], 8, dv) || !dev_buffer_ok(dst->ctg_status, C, 4, dv)) {
+        set_last_error("a destination array is NULL, not device memory of the result's device, or misaligned");
+        return AASM_E_INVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    {   // forget the exports that have finished (a caller may export one result many times between two solves)
+        size_t j = 0;
+        for (hipEvent_t ev : cx.export_events) { if (hipEventQuery(ev) == hipSuccess) (void)hipEventDestroy(ev); else cx.export_events[j++] = ev; }
+        cx.export_events.resize(j);
+        (void)hipGetLastError();
+    }
+    // after the solve's work (aasm_result_sizes has waited for it already; the event keeps the order explicit), and the next
+    // solve on the device waits for this export before it reuses the arena (drain_exports)
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    hipError_t e = hipEventCreateWithFlags(&ev_in, hipEventDisableTiming);
+    if (e == hipSuccess) { cx.export_events.push_back(ev_in); e = hipEventCreateWithFlags(&ev_out, hipEventDisableTiming); }
+    if (e == hipSuccess) { cx.export_events.push_back(ev_out); e = hipEventRecord(ev_in, res->stream); }
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, ev_in, 0);
+    if (e != hipSuccess) { set_last_error(hip_err("export ordering", e)); return AASM_E_HIP; }
+    GpuBackend be(cx, s, GpuBackend::Attach{});
+    pack_export(be, res->w, res->pk, *dst);
+    if (be.failed()) return AASM_E_HIP;
+    if ((e = hipEventRecord(ev_out, s)) != hipSuccess) { set_last_error(hip_err("hipEventRecord", e)); return AASM_E_HIP; }
     return AASM_OK;
 }
 
@@ -1371,6 +1474,7 @@ static void ctx_release_arena(int device) {
     std::lock_guard<std::mutex> lk(cx.mu);
     hipSetDevice(device);
     hipStreamSynchronize(cx.stream);
+    drain_exports(cx);
     for (auto &b : cx.blocks) hipFree(b.p);
     cx.blocks.clear();
     cx.generation++;

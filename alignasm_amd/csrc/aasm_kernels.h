@@ -19,6 +19,7 @@
 #pragma once
 #include <cstddef>
 #include "aasm_dev.h"
+#include "../../include/alignasm_amd.h"
 
 namespace aasm {
 
@@ -4649,6 +4650,86 @@ AASM_DEV void kb_gather_out(const KCtx &k, const WS &w) {
     const int64_t nm = w.main_len[c], na = w.alt_len[c], om = w.main_off[c], oa = w.alt_off[c];
     for (int64_t t = k.lane; t < nm; t += AASM_WAVE) w.main_c[om + t] = w.main_out[b + t];
     for (int64_t t = k.lane; t < na; t += AASM_WAVE) w.alt_c[oa + t] = w.alt_out[b + t];
+}
+
+
+// ---- device-side export of a result (aasm_result_sizes / aasm_result_export) -----------------------------------------------
+// What fetch_results (aasm_pipeline.h) builds on the host, built on the device into caller-owned buffers.  main / alt are already
+// compact (main_c / alt_c); .all is the record list sel_all_append leaves: a record is kept when its contig is in range, its
+// generation is the contig's last one and its elements lie inside the pool, and the kept records of a contig go in seq order.
+// Rank without a sort: a contig's records are appended by ONE wave at a time, all_seq[c] counts every append and is never reset
+// inside a run (the overflow re-runs zero it together with the record counter), and all_gen[c] rises at each clear
+// (sequential selection only; the plan-based pick never clears).  So the n kept records of contig c are the last n appends, with
+// the seqs all_seq[c] - n .. all_seq[c] - 1.  The place kernel checks this: a rank outside [0, n) or a slot taken twice marks the
+// contig AASM_E_INTERNAL in the export's status copy and writes nothing for that record.
+struct PackArgs {
+    int64_t C, ar_cap, pool_cap;
+    const int64_t *counters;
+    const int32_t *ar_ctg, *ar_gen, *ar_seq, *ar_len, *all_gen, *all_seq, *status;
+    const int64_t *ar_off, *main_off, *alt_off;
+    const OutElem *pool, *main_c, *alt_c;
+    int32_t *np, *st, *prec, *plen;           // scratch: kept paths per contig, status copy, record of output path p, its length
+    int64_t *poff, *eoff;                     // [C + 1] path offsets, [ar_cap + 1] element offsets (the first NP + 1 are the output's)
+    int64_t NM, NA, NP, NE;                   // export only: the sizes aasm_result_sizes returned
+    int64_t *d_main_off, *d_alt_off, *d_path_off, *d_elem_off;
+    OutElem *d_main, *d_alt, *d_all;
+    int32_t *d_status;
+};
+
+AASM_DEV int32_t pack_kept(const PackArgs &a, int64_t r) {          // contig of record r when the record is kept, else -1
+    const int64_t nar = a.counters[CNT_AR] < a.ar_cap ? a.counters[CNT_AR] : a.ar_cap;
+    const int64_t npool = a.counters[CNT_POOL] < a.pool_cap ? a.counters[CNT_POOL] : a.pool_cap;
+    if (r >= nar) return -1;
+    const int32_t c = a.ar_ctg[r];
+    if (c < 0 || c >= a.C || a.ar_gen[r] != a.all_gen[c]) return -1;
+    return a.ar_off[r] + a.ar_len[r] <= npool ? c : -1;
+}
+
+// one thread per record (and per contig: the status copy)
+AASM_DEV void kb_pack_count(const KCtx &k, const PackArgs &a) {
+    const int64_t i = k.bid * k.nthreads + k.tid;
+    if (i < a.C) a.st[i] = a.status[i];
+    if (i >= a.ar_cap) return;
+    const int32_t c = pack_kept(a, i);
+    if (c >= 0) atomic_add(&a.np[c], (int32_t)1);
+}
+
+// one thread per record: its output slot poff[c] + rank
+AASM_DEV void kb_pack_place(const KCtx &k, const PackArgs &a) {
+    const int64_t r = k.bid * k.nthreads + k.tid;
+    if (r >= a.ar_cap) return;
+    const int32_t c = pack_kept(a, r);
+    if (c < 0) return;
+    const int64_t n = a.np[c], rank = (int64_t)a.ar_seq[r] - ((int64_t)a.all_seq[c] - n);
+    if (rank < 0 || rank >= n) { a.st[c] = AASM_E_INTERNAL; return; }
+    const int64_t p = a.poff[c] + rank;
+    if (atomic_cas_i32(&a.prec[p], -1, (int32_t)r) != -1) { a.st[c] = AASM_E_INTERNAL; return; }
+    a.plen[p] = a.ar_len[r];
+}
+
+// grid-stride copies of the offsets, the status and the compact main / alt elements (8-byte words: 40 is not a multiple of 16)
+AASM_DEV void kb_pack_flat(const KCtx &k, const PackArgs &a) {
+    const int64_t g = k.bid * k.nthreads + k.tid, G = k.nblocks * k.nthreads;
+    for (int64_t i = g; i <= a.C; i += G) { a.d_main_off[i] = a.main_off[i]; a.d_alt_off[i] = a.alt_off[i]; a.d_path_off[i] = a.poff[i]; }
+    for (int64_t i = g; i < a.C; i += G) a.d_status[i] = a.st[i];
+    for (int64_t i = g; i <= a.NP; i += G) a.d_elem_off[i] = a.eoff[i];
+    const int64_t *ms = (const int64_t *)a.main_c, *as = (const int64_t *)a.alt_c;
+    int64_t *md = (int64_t *)a.d_main, *ad = (int64_t *)a.d_alt;
+    for (int64_t i = g; i < 5 * a.NM; i += G) md[i] = ms[i];
+    for (int64_t i = g; i < 5 * a.NA; i += G) ad[i] = as[i];
+}
+
+// a wave per output path, grid-stride over the paths: the path's 5 * len words from the pool, lanes over the words
+AASM_DEV void kb_pack_all(const KCtx &k, const PackArgs &a) {
+    const int64_t nw = k.nblocks * k.nthreads / AASM_WAVE;
+    for (int64_t p = (k.bid * k.nthreads + k.tid) / AASM_WAVE; p < a.NP; p += nw) {
+        const int32_t r = a.prec[p];
+        if (r < 0) continue;                                        // (a slot left empty: the contig is marked AASM_E_INTERNAL)
+        const int64_t *src = (const int64_t *)(a.pool + a.ar_off[r]);
+        int64_t *dst = (int64_t *)(a.d_all + a.eoff[p]);
+        const int64_t n = 5 * (int64_t)a.plen[p];
+        for (int64_t t = k.lane; t < n; t += AASM_WAVE) dst[t] = src[t];
+    }
 }
 
 }  // namespace aasm

@@ -634,4 +634,93 @@ int fetch_results(B &be, const WS &w, const PipelineSizes &sz, aasm_batch_out *o
     return AASM_OK;
 }
 
+
+// ---- device-side export (aasm_result_sizes / aasm_result_export): fetch_results' arrays built on the device ----------------
+// Backends provide alloc / zero / fill_ff / scan_i32 / read_i64s as for the pipeline, and launch_pack(kernel, blocks, threads,
+// PackArgs).  The scratch is carved out of the result's workspace when the result is made (pack_alloc, behind run_pipeline);
+// sizes = count -> scan -> place -> scan -> ONE read-back, run once per result: exports in flight read that scratch, so a later
+// sizes call answers from the cached sizes and never rebuilds it; export = two launches, no read-back.
+enum PackKern { KP_COUNT, KP_PLACE, KP_FLAT, KP_ALL };
+AASM_DEV void run_pack_body(int kn, const KCtx &k, const PackArgs &a) {
+    switch (kn) {
+        case KP_COUNT: kb_pack_count(k, a); break;
+        case KP_PLACE: kb_pack_place(k, a); break;
+        case KP_FLAT: kb_pack_flat(k, a); break;
+        case KP_ALL: kb_pack_all(k, a); break;
+        default: break;
+    }
+}
+#define AASM_PACK_MAX_BLOCKS 2048   // 256-thread blocks of the copies: 8 waves per CU of the 256 (grid-stride beyond)
+
+struct PackWS {
+    bool ready = false;               // scratch carved
+    bool sized = false;               // sizes[] holds the last aasm_result_sizes answer
+    int32_t *np = nullptr, *st = nullptr, *prec = nullptr, *plen = nullptr;
+    int64_t *poff = nullptr, *eoff = nullptr;
+    int64_t sizes[5] = {0, 0, 0, 0, 0};   // n_contigs, n_main, n_alt, n_all_paths, n_all_elems
+};
+
+static inline PackArgs pack_args(const WS &w, const PackWS &p) {
+    PackArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.C = w.C; a.ar_cap = w.ar_cap; a.pool_cap = w.pool_cap; a.counters = w.counters;
+    a.ar_ctg = w.ar_ctg; a.ar_gen = w.ar_gen; a.ar_seq = w.ar_seq; a.ar_len = w.ar_len; a.all_gen = w.all_gen; a.all_seq = w.all_seq;
+    a.status = w.status; a.ar_off = w.ar_off; a.main_off = w.main_off; a.alt_off = w.alt_off;
+    a.pool = w.pool; a.main_c = w.main_c; a.alt_c = w.alt_c;
+    a.np = p.np; a.st = p.st; a.prec = p.prec; a.plen = p.plen; a.poff = p.poff; a.eoff = p.eoff;
+    return a;
+}
+
+template <class B>
+int pack_alloc(B &be, const WS &w, PackWS &p) {
+    const int64_t C = w.C, AR = w.ar_cap;
+    if (C <= 0 || AR > INT32_MAX) return AASM_OK;                   // (no export for such a result: pack_sizes reports it)
+    if (!p.ready) {
+        p.np = (int32_t *)be.alloc("pack_np", sizeof(int32_t) * (size_t)C);
+        p.st = (int32_t *)be.alloc("pack_st", sizeof(int32_t) * (size_t)C);
+        p.poff = (int64_t *)be.alloc("pack_poff", sizeof(int64_t) * (size_t)(C + 1));
+        p.prec = (int32_t *)be.alloc("pack_prec", sizeof(int32_t) * (size_t)AR);
+        p.plen = (int32_t *)be.alloc("pack_plen", sizeof(int32_t) * (size_t)AR);
+        p.eoff = (int64_t *)be.alloc("pack_eoff", sizeof(int64_t) * (size_t)(AR + 1));
+        if (be.failed()) return be.oom() ? AASM_E_NOMEM : AASM_E_HIP;
+        p.ready = true;
+    }
+    return AASM_OK;
+}
+
+template <class B>
+int pack_sizes(B &be, const WS &w, PackWS &p) {
+    const int64_t C = w.C, AR = w.ar_cap;
+    if (C <= 0) return AASM_E_INVAL;
+    if (AR > INT32_MAX) return AASM_E_OVERFLOW;                     // (record ids are int32 in prec)
+    if (p.sized) return AASM_OK;                                     // (a result's sizes do not change; its scratch may be in use)
+    if (!p.ready) return AASM_E_INTERNAL;
+    const PackArgs a = pack_args(w, p);
+    be.zero(p.np, sizeof(int32_t) * (size_t)C);
+    be.fill_ff(p.prec, sizeof(int32_t) * (size_t)AR);
+    be.zero(p.plen, sizeof(int32_t) * (size_t)AR);
+    be.launch_pack(KP_COUNT, cdiv(std::max(C, AR), 256), 256, a);
+    be.scan_i32(p.np, C, p.poff);
+    be.launch_pack(KP_PLACE, cdiv(AR, 256), 256, a);
+    be.scan_i32(p.plen, AR, p.eoff);                                 // (slots past the last path are 0: eoff[NP .. AR] = NE)
+    int64_t v[4];
+    be.read_i64s({p.poff + C, p.eoff + AR, w.main_off + C, w.alt_off + C}, v);
+    if (be.failed()) return AASM_E_HIP;
+    p.sizes[0] = C; p.sizes[1] = v[2]; p.sizes[2] = v[3]; p.sizes[3] = v[0]; p.sizes[4] = v[1];
+    p.sized = true;
+    return AASM_OK;
+}
+
+// dst arrays as aasm_dev_out; the caller has checked them and the sizes against p.sizes
+template <class B>
+void pack_export(B &be, const WS &w, const PackWS &p, const aasm_dev_out &d) {
+    PackArgs a = pack_args(w, p);
+    a.NM = p.sizes[1]; a.NA = p.sizes[2]; a.NP = p.sizes[3]; a.NE = p.sizes[4];
+    a.d_main_off = d.main_off; a.d_alt_off = d.alt_off; a.d_path_off = d.all_path_off; a.d_elem_off = d.all_elem_off;
+    a.d_main = (OutElem *)d.main_elems; a.d_alt = (OutElem *)d.alt_elems; a.d_all = (OutElem *)d.all_elems; a.d_status = d.ctg_status;
+    const int64_t words = std::max(std::max(w.C + 1, a.NP + 1), 5 * std::max(a.NM, a.NA));
+    be.launch_pack(KP_FLAT, std::min<int64_t>(cdiv(words, 256), AASM_PACK_MAX_BLOCKS), 256, a);
+    if (a.NP > 0) be.launch_pack(KP_ALL, std::min<int64_t>(cdiv(a.NP, 256 / AASM_WAVE), AASM_PACK_MAX_BLOCKS), 256, a);
+}
+
 }  // namespace aasm

@@ -113,7 +113,7 @@ typedef struct aasm_opts {
 #define AASM_H2_CHAIN_HDR_LOST   0x8      /* the chain class's pre-pass wave of contig 0 never publishes the root's header   */
 #define AASM_H2_CHAIN_DONE_LOST  0x10     /* ... nor that it is done (AASM_E_INTERNAL for the contig, nothing may hang)      */
 #define AASM_H2_CHAIN_OWN_QUEUE  0x20     /* the chain class's heap wave keeps its own BFS queue (default: the order from a wave of
-                                             its own while the class has at most AASM_CHAIN_ORD_MAX contigs)                 */
+                                             its own while the class has at most AASM_CHAIN_ORD_MAX = 1 024 contigs)         */
 #define AASM_H2_SMALL_ROOT_RING  0x40     /* that heap wave's ring of parents' roots has 4 entries, not 512                  */
 #define AASM_H2_SORT_DEPTH_MASK  0xFF00   /* d + 1: the sort replay takes its heap sort fallback after d partition levels    */
 #define AASM_H2_SORT_DEPTH_SHIFT 8
@@ -243,6 +243,38 @@ int  aasm_result_stats(const aasm_result *res, aasm_stats *stats);
 int  aasm_result_fetch(aasm_result *res, aasm_batch_out *out);   /* D2H + ragged pack */
 void aasm_result_free(aasm_result *res);
 void aasm_free_out(aasm_batch_out *out);
+
+/* ---- results on the device: the output path matching aasm_upload_batch -> aasm_solve_device ------------------------------
+ * The arrays of aasm_result_fetch, built on the device (ragged pack kernels) into buffers the CALLER owns, so that a batch goes
+ * from HBM to HBM and its answer outlives the next solve on the device (a result itself lives in the workspace arena, which the
+ * next solve reuses).  Use: aasm_result_sizes -> allocate on the result's device -> aasm_result_export.                       */
+typedef struct aasm_out_sizes {
+    int64_t n_contigs;
+    int64_t n_main;            /* main_elems entries (== main_off[n_contigs])          */
+    int64_t n_alt;             /* alt_elems entries                                    */
+    int64_t n_all_paths;       /* all_elem_off has n_all_paths + 1 entries            */
+    int64_t n_all_elems;       /* all_elems entries                                    */
+} aasm_out_sizes;
+/* DEVICE pointers owned by the caller; same fields and meaning as aasm_batch_out's arrays */
+typedef struct aasm_dev_out {
+    int64_t *main_off;         /* [n_contigs+1]   */
+    int64_t *alt_off;          /* [n_contigs+1]   */
+    int64_t *all_path_off;     /* [n_contigs+1]   */
+    int64_t *all_elem_off;     /* [n_all_paths+1] */
+    aasm_out_elem *main_elems; /* [n_main]        */
+    aasm_out_elem *alt_elems;  /* [n_alt]         */
+    aasm_out_elem *all_elems;  /* [n_all_elems]   */
+    int32_t *ctg_status;       /* [n_contigs]     */
+} aasm_dev_out;
+/* Counts and places the .all paths on the device and returns the five sizes.  NOT asynchronous: one small device->host copy
+ * and a wait on the result's stream.  The device-side offsets it computes are kept in the result for the export.          */
+int  aasm_result_sizes(aasm_result *res, aasm_out_sizes *sz);
+/* Asynchronous on `stream` (a hipStream_t on the result's device; NULL = the null stream), no host wait: once the stream gets
+ * there, dst holds exactly what aasm_result_fetch returns.  AASM_E_INVAL (nothing enqueued) when sz is not what
+ * aasm_result_sizes returned for this result, when a later solve invalidated the result, or when an array that is not
+ * empty is NULL, host memory, memory of another device or not 8-byte (ctg_status: 4-byte) aligned.  The next solve on the
+ * device waits for the exports in flight before it reuses the workspace; the caller's buffers are never touched again.  */
+int  aasm_result_export(aasm_result *res, const aasm_out_sizes *sz, const aasm_dev_out *dst, void *stream);
 
 /* Upload a host batch once and solve it repeatedly (benchmark path: inputs resident in
  * HBM before the timed region).  dev_view receives device pointers for aasm_solve_device. */
