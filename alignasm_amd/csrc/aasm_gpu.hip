@@ -118,6 +118,7 @@ AASM_DEF_PACK_KERNEL(aasm_pack_all, KP_ALL)
 // out bit 0: dist_lt<CALC_SUM>(a, b)   bit 1: dist_lt<QRY_SCORE>(a, b)   bit 2: dist_eq(a, b)
 //     bit 3: nodeq_key_lt (heap node holding key a, against key b; K7's descent test)
 //     bit 4: pq_full_less (a, b as priority-queue candidates with equal node / insertion index; K8)
+//     bit 5: qe_less on K8's default-queue entries built from a, b (sum = qry + ref, qe_key2, equal node / index)
 __global__ void __launch_bounds__(256) aasm_t1_predicates(const int64_t *a, const int64_t *b, int64_t n, uint8_t *out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -135,6 +136,10 @@ __global__ void __launch_bounds__(256) aasm_t1_predicates(const int64_t *a, cons
     r |= dist_eq(x, y) ? 4 : 0;
     r |= nodeq_key_lt(nd, y, y.qry + y.ref) ? 8 : 0;
     r |= pq_full_less(x, 7, 3, y, 7, 3) ? 16 : 0;
+    QE ea, eb;
+    ea.sum = (uint64_t)(x.qry + x.ref); ea.key2 = qe_key2(x.anom, x.qnz, x.qtot); ea.nc = ((uint64_t)7 << 32) | 3; ea.tag = 0;
+    eb.sum = (uint64_t)(y.qry + y.ref); eb.key2 = qe_key2(y.anom, y.qnz, y.qtot); eb.nc = ea.nc; eb.tag = 0;
+    r |= qe_less(ea, eb) ? 32 : 0;
     out[i] = r;
 }
 

@@ -298,7 +298,8 @@ int64_t aasm_debug_fetch(aasm_result *res, const char *name, void *dst, int64_t 
 int64_t aasm_debug_counter(const char *name);
 /* Test entry for row T1: the device's PafDistance predicates (paf_data.hpp:142-168) on n pairs of
  * {qry, ref, anom, qul_nonzero, qul_total} tuples.  out[i] bit 0: a < b in CALC_SUM mode, bit 1: a < b in
- * QRY_SCORE mode, bit 2: a == b, bit 3: K7's node-key test, bit 4: K8's queue order (equal node / index). */
+ * QRY_SCORE mode, bit 2: a == b, bit 3: K7's node-key test, bit 4: K8's queue order (equal node / index), bit 5: the
+ * same order as K8's default queue keeps it ({qry + ref, key2, node:index} words, aasm_enum.h qe_less / qe_key2). */
 int  aasm_debug_predicates(const int64_t *a, const int64_t *b, int64_t n, uint8_t *out, int device);
 /* Test entry for hazard B1: K1's replay of libstdc++'s std::sort (paf_data.cpp:241-246 sorts with an unstable sort, so the
  * order of records with equal (qry_str, qry_end) is whatever that algorithm leaves) alone, on arbitrary keys.

@@ -137,6 +137,7 @@ class RefPrefixVectors:
     def __init__(self, path=None):
         self.z = np.load(path or os.path.join(GOLDEN, "ref_prefix.npz"))
         self.tags = [str(t) for t in self.z["tags"]]
+        self._packed = {}
 
     def batch(self, tag):
         """-> (HostBatch, nsl, all 10 000 distances recorded?)"""
@@ -154,16 +155,35 @@ class RefPrefixVectors:
 
     def contig(self, tag, c):
         """The PREFIX_NAMES arrays of contig c (int64), + "kfound" = how many distances the reference found."""
+        if f"{tag}/p~n" in self.z.files:
+            return self._packed_contig(tag, c)
         out = {}
         pre = f"{tag}/c{c}/"
         for k in self.z.files:
             if k.startswith(pre):
-                name = k[len(pre):]
-                a = self.z[k].astype(np.int64)
-                if name.endswith("~b"):
-                    name, a = name[:-2], np.where(a > 0, np.arange(len(a)) - a, -1)
-                out[name] = a
+                out[k[len(pre):]] = self.z[k].astype(np.int64)
+        return self._unstore(out)
+
+    @staticmethod
+    def _unstore(stored):
+        out = {}
+        for name, a in stored.items():
+            if name.endswith("~b"):
+                name, a = name[:-2], np.where(a > 0, np.arange(len(a)) - a, -1)
+            out[name] = a
         return out
+
+    def _packed_contig(self, tag, c):
+        """make_ref_prefix.py's packed layout: {tag}/p/{name} holds the contigs' arrays back to back, {tag}/p~n their lengths."""
+        if tag not in self._packed:
+            cols = [str(n) for n in self.z["packed_cols"]]
+            lens = self.z[f"{tag}/p~n"].astype(np.int64)
+            starts = np.cumsum(np.maximum(lens, 0), axis=0) - np.maximum(lens, 0)
+            self._packed[tag] = (cols, lens, starts, {n: self.z[f"{tag}/p/{n}"].astype(np.int64) for n in cols})
+        cols, lens, starts, arrs = self._packed[tag]
+        if lens[c, 0] < 0:
+            return {}
+        return self._unstore({n: arrs[n][starts[c, j]:starts[c, j] + lens[c, j]] for j, n in enumerate(cols)})
 
 
 _cs_buf = {}

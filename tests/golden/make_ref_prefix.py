@@ -8,7 +8,9 @@ own statements computed from them - sorted order, part ids, every (i, j) cut, ve
 all weight fields, anom_dis[dest], d / best, both Kahn orders, every heap node and root, the k-walk distances
 (all 10 000 for the batches marked full, the first 64 otherwise) - the arrays of aasm_testlib.PREFIX_NAMES.
 
-    python tests/golden/make_ref_prefix.py
+    python tests/golden/make_ref_prefix.py          # ref_prefix.npz
+    python tests/golden/make_ref_prefix.py wide     # ref_prefix_wide.npz: the same from tests/wide_cases.py's batches
+                                                    # (coordinates, weights and score sums above 2^31 / 2^32, up to 2^40 - 1)
 """
 import os
 import sys
@@ -21,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import aasm_testlib as T   # noqa: E402
 from test_fuzz import make_batch   # noqa: E402
+import wide_cases as W   # noqa: E402
 
 KD = ("kd_qry", "kd_ref", "kd_anom", "kd_qnz", "kd_qtot")
 KD_SHORT = 64
@@ -47,26 +50,59 @@ BATCHES = [
 ]
 
 
-def main():
+
+def _shifted(base, oname):
+    if isinstance(base, str):
+        base = dict(W.narrow_bases(T))[base] if base != "crafted" else W.crafted()[1]
+    return W.shift(base, *W.offsets(base)[oname])
+
+
+# kept small (the file is ~0.4 MB): the synthetic batches are smaller than wide_cases.narrow_bases', and only the fuzz and
+# crafted batches with few distances keep all 10 000
+WIDE_BATCHES = [
+    ("wf33_0", lambda: make_batch(1000, 4, 20, W.WIDE_L[0], 0), False, False),
+    ("wf33_1", lambda: make_batch(1001, 4, 20, W.WIDE_L[0], 1), False, True),
+    ("wf33_2n", lambda: make_batch(1002, 4, 20, W.WIDE_L[0], 2), True, False),
+    ("wf39_0", lambda: make_batch(1003, 4, 20, W.WIDE_L[1], 0), False, False),
+    ("wf39_1n", lambda: make_batch(1004, 4, 20, W.WIDE_L[1], 1), True, False),
+    ("wf39_2", lambda: make_batch(1005, 4, 20, W.WIDE_L[1], 2), False, False),
+    ("crafted", lambda: W.crafted()[1], False, True),
+    ("crafted_n", lambda: W.crafted()[1], True, True),
+    ("crafted_top", lambda: W.crafted(top=True)[1], False, True),
+    ("crafted_x32", lambda: _shifted("crafted", "x32"), False, True),
+    ("fz0_x31", lambda: _shifted("fz0", "x31"), False, False),
+    ("fz2_x32", lambda: _shifted("fz2", "x32"), True, False),
+    ("syn_x32", lambda: _shifted(T.synth(1, 60, 5, dup_every=3), "x32"), False, False),
+    ("syn_top", lambda: _shifted(T.synth(1, 60, 9), "top"), False, False),
+    ("dense_5g", lambda: _shifted(T.synth(1, 50, 31, dense=True), "5g"), False, False),
+]
+
+
+def _narrow(a):
+    return a.astype(np.int32) if a.size and np.abs(a).max() < 2 ** 31 else a       # storage only; the loader widens again
+
+
+def main(batches=BATCHES, name="ref_prefix.npz", packed=False):
+    """packed: the per-contig arrays of a batch are stored back to back, one array per name ({tag}/p/{name}), with their
+    lengths in {tag}/p~n (contigs x names, -1 for a contig not recorded) - far fewer arrays in the file, and the same values
+    (aasm_testlib.RefPrefixVectors reads both layouts)."""
     assert T.ref_prefix(True) is not None, "build oracle/_ref first (make -C oracle)"
     out = {}
     tags = []
-    for tag, mk, nsl, full in BATCHES:
+    cols = [n + "~b" if n == "heap_right" else n for n in T.PREFIX_NAMES] + ["kfound"]
+    for tag, mk, nsl, full in batches:
         hb = mk()
         tags.append(tag)
         out[f"{tag}/nsl"] = np.array([1 if nsl else 0], np.int8)
         out[f"{tag}/full"] = np.array([1 if full else 0], np.int8)
         for k, a in hb.arrays.items():
             if k == "rng_qry_r":
-                out[f"{tag}/in/{k}~len"] = (a - hb.arrays["rng_qry_l"]).astype(np.int32)           # storage only: r - l
+                out[f"{tag}/in/{k}~len"] = _narrow(a - hb.arrays["rng_qry_l"])                     # storage only: r - l
                 continue
             if k.startswith("rng_"):
-                out[f"{tag}/in/{k}~d"] = np.diff(a.astype(np.int64), prepend=0).astype(np.int32)   # storage only: first differences
+                out[f"{tag}/in/{k}~d"] = _narrow(np.diff(a.astype(np.int64), prepend=0))           # storage only: first differences
                 continue
-            small = a
-            if a.dtype == np.int64 and a.size and np.abs(a).max() < 2 ** 31:
-                small = a.astype(np.int32)                                     # storage only; the loader widens again
-            out[f"{tag}/in/{k}"] = small
+            out[f"{tag}/in/{k}"] = _narrow(a) if a.dtype == np.int64 else a
         off = hb.arrays["ctg_rec_off"]
         for c in range(len(off) - 1):
             if off[c + 1] - off[c] <= 1:
@@ -81,16 +117,28 @@ def main():
                 if n == "heap_right":                           # storage only: distance back to the child (0 = none)
                     out[f"{tag}/c{c}/{n}~b"] = np.where(a >= 0, np.arange(len(a)) - a, 0).astype(np.int32)
                     continue
-                if a.size and np.abs(a).max() < 2 ** 31:
-                    a = a.astype(np.int32)
-                out[f"{tag}/c{c}/{n}"] = a
+                out[f"{tag}/c{c}/{n}"] = _narrow(a)
             out[f"{tag}/c{c}/kfound"] = np.array([len(r["kd_qry"])], np.int32)
+        if packed:
+            lens = np.full((len(off) - 1, len(cols)), -1, np.int32)
+            for c in range(len(off) - 1):
+                if f"{tag}/c{c}/kfound" in out:
+                    lens[c] = [len(out[f"{tag}/c{c}/{n}"]) for n in cols]
+            for j, n in enumerate(cols):
+                parts = [out.pop(f"{tag}/c{c}/{n}").astype(np.int64) for c in range(len(off) - 1) if lens[c, j] >= 0]
+                out[f"{tag}/p/{n}"] = _narrow(np.concatenate(parts) if parts else np.zeros(0, np.int64))
+            out[f"{tag}/p~n"] = lens
+    if packed:
+        out["packed_cols"] = np.array(cols)
     out["tags"] = np.array(tags)
     out["source"] = np.array(["reference paf_data.cpp:223-738 via oracle/_ref/libaasm_ref_prefix_mono.so (MAX_PATH_COUNT = 10000)"])
-    path = os.path.join(HERE, "ref_prefix.npz")
+    path = os.path.join(HERE, name)
     np.savez_compressed(path, **out)
     print("wrote %s: %d batches, %d arrays, %d bytes" % (path, len(tags), len(out), os.path.getsize(path)))
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["wide"]:
+        main(WIDE_BATCHES, "ref_prefix_wide.npz", packed=True)
+    else:
+        main()
