@@ -224,3 +224,51 @@ class HostBatch:
         for name in ("rng_qry_l", "rng_qry_r", "rng_ref_l"):
             out[name] = a[name][rng_idx]
         return HostBatch(out)
+
+
+# ---- k shortest walks on caller DAGs (aasm_k_shortest_walks) ----------------------------------------------------------------
+AASM_KSW_WALKS, AASM_KSW_TREE, AASM_KSW_HOOK_ARENA = 0x1, 0x2, 0x100
+
+
+class KswOut(C.Structure):
+    _fields_ = [("n_graphs", C.c_int64), ("k", C.c_int64)] + [
+        (name, C.c_void_p) for name in ("n_found", "dist5", "walk_off", "walk_edges", "d5", "best", "heap_nodes", "status",
+                                        "hook_arena", "hook_hroot")
+    ]
+
+
+def ksw_inputs(g_voff, rowptr, col, w, source, sink):
+    """Contiguous arrays in the C-ABI's types; w is [E, 5] or [E] (a scalar w becomes (w, 0, 0, 0, 1): it orders as w does)."""
+    g_voff = np.ascontiguousarray(g_voff, np.int64)
+    rowptr = np.ascontiguousarray(rowptr, np.int64)
+    col = np.ascontiguousarray(col, np.int32)
+    w = np.asarray(w, np.int64)
+    if w.ndim == 1:
+        w5 = np.zeros((len(w), 5), np.int64)
+        w5[:, 0] = w
+        w5[:, 4] = 1
+    else:
+        w5 = w.reshape(-1, 5)
+    w5 = np.ascontiguousarray(w5, np.int64).reshape(-1)
+    return g_voff, rowptr, col, w5, np.ascontiguousarray(source, np.int32), np.ascontiguousarray(sink, np.int32)
+
+
+def unpack_ksw(out: KswOut, vt, flags):
+    """KswOut -> dict of numpy arrays (copies; the C side can be freed afterwards)."""
+    g, k = int(out.n_graphs), int(out.k)
+    r = {
+        "n_found": _np_from(out.n_found, g, np.int64),
+        "dist": _np_from(out.dist5, g * k * 5, np.int64).reshape(g, k, 5),
+        "heap_nodes": _np_from(out.heap_nodes, g, np.int64),
+        "status": _np_from(out.status, g, np.int32),
+    }
+    if flags & AASM_KSW_WALKS:
+        r["walk_off"] = _np_from(out.walk_off, g * k + 1, np.int64)
+        r["walk_edges"] = _np_from(out.walk_edges, int(r["walk_off"][-1]), np.int64)
+    if flags & AASM_KSW_TREE:
+        r["d"] = _np_from(out.d5, vt * 5, np.int64).reshape(vt, 5)
+        r["best"] = _np_from(out.best, vt, np.int32)
+    if flags & AASM_KSW_HOOK_ARENA:
+        r["hook_arena"] = _np_from(out.hook_arena, int(r["heap_nodes"].sum()) * 10, np.int64).reshape(-1, 10)
+        r["hook_hroot"] = _np_from(out.hook_hroot, vt, np.int32)
+    return r

@@ -14,7 +14,8 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_E_INVAL, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, Opts, OutSizes, Stats, SynthCfg, make_opts, unpack_out)
+from ._abi import (AASM_E_INVAL, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, KswOut, Opts,
+                   OutSizes, Stats, SynthCfg, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AASM_LIB_OVERRIDE") or os.path.join(_HERE, "libalignasm_amd.so")   # override: diagnostic builds (tools/)
@@ -76,7 +77,7 @@ EXPORTED = [
     "aasm_result_stats", "aasm_result_fetch", "aasm_result_free", "aasm_free_out", "aasm_upload_batch", "aasm_upload_free",
     "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
-    "aasm_result_sizes", "aasm_result_export",
+    "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free",
 ]
 
 
@@ -105,6 +106,26 @@ def sssp_dijkstra(g_voff, rowptr, col, w5, src, device=0):
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     _check(LIB.aasm_sssp_dijkstra(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(src), P(d), P(prev), int(device)))
     return d, prev
+
+
+def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=False, device=0, _hooks=0):
+    """k_shortest_walks(source, sink, k) of the reference's solver with is_dag = true, and every walk recovered
+    (k_shortest_walks.hpp:177-290), on the GPU over a batch of DAGs in sssp_dijkstra's layout.  w: [E, 5] int64
+    {qry_score, ref_score, anom, qul_nonzero, qul_total} or [E] (scalar weights, taken as (w, 0, 0, 0, 1)).
+    Returns a dict of numpy arrays: n_found [G], dist [G, k, 5], status [G] (0, or AASM_E_INVAL for a graph with a cycle),
+    heap_nodes [G]; with walks, walk_off [G * k + 1] and walk_edges (caller CSR positions, source -> sink, walk g * k + i
+    at walk_edges[walk_off[g * k + i]:walk_off[g * k + i + 1]]); with tree, d [V, 5] and best [V] (local ids)."""
+    g_voff, rowptr, col, w5, source, sink = ksw_inputs(g_voff, rowptr, col, w, source, sink)
+    flags = (AASM_KSW_WALKS if walks else 0) | (AASM_KSW_TREE if tree else 0) | int(_hooks)
+    out = KswOut()
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = LIB.aasm_k_shortest_walks(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(source), P(sink), C.c_int64(int(k)),
+                                   int(flags), int(device), C.byref(out))
+    _check(rc)
+    try:
+        return unpack_ksw(out, int(g_voff[-1]), flags)
+    finally:
+        LIB.aasm_ksw_free(C.byref(out))
 
 
 def sssp_dial(g_voff, rowptr, col, cost, src, lim=2, device=0):

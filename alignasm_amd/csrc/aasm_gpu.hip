@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "aasm_pipeline.h"
+#include "aasm_ksw.h"
 #include "aasm_paf.hpp"
 
 namespace aasm {
@@ -223,6 +224,18 @@ __global__ void __launch_bounds__(64) aasm_sssp_dijkstra_kernel(int64_t n_graphs
     }
     if (over && lane == 0) pg[s] = -2;                               // reported by the host entry
 }
+
+// ---- k shortest walks on caller DAGs (row ★K): bodies in aasm_ksw.h, one 64-lane workgroup per graph of [g0, g0 + grid) --
+#define AASM_DEF_KSW_KERNEL(name, body)                                                                           \
+    __global__ void __launch_bounds__(64) name(int64_t g0, KswArgs a) {                                           \
+        KCtx k{(int)threadIdx.x, (int)blockDim.x, g0 + (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr}; \
+        body(k, a);                                                                                               \
+    }
+AASM_DEF_KSW_KERNEL(aasm_ksw_tree, kb_ksw_tree)
+AASM_DEF_KSW_KERNEL(aasm_ksw_heap, kb_ksw_heap)
+AASM_DEF_KSW_KERNEL(aasm_ksw_enum, kb_ksw_enum)
+AASM_DEF_KSW_KERNEL(aasm_ksw_count, kb_ksw_count)
+AASM_DEF_KSW_KERNEL(aasm_ksw_fill, kb_ksw_fill)
 
 // ---- Dial's bucketed BFS (k_weighted_bfs.hpp:16-37), one wave per graph -------------------------------------------------
 // The reference keeps lim + 1 circular buckets, each a LIFO stack, and walks d = 0, 1, ...: pop the top of bucket d mod (lim + 1),
@@ -1279,6 +1292,64 @@ int aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowpt
         if (pre[g_voff[g] + src[g]] == -2) { set_last_error("graph " + std::to_string(g) + ": bucket capacity exceeded (must not happen)"); return AASM_E_INTERNAL; }
     return AASM_OK;
 }
+
+// k shortest walks (k_shortest_walks.hpp:177-290, is_dag = true) over a batch of DAGs; host pointers in, library-allocated out
+namespace {
+struct KswGpu {
+    hipStream_t stream;
+    hipError_t e = hipSuccess;
+    std::vector<void *> blocks;
+    ~KswGpu() { for (void *p : blocks) hipFree(p); }
+    void *alloc(size_t n) {
+        void *p = nullptr;
+        if (e != hipSuccess) return nullptr;
+        if ((e = hipMalloc(&p, n)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        blocks.push_back(p);
+        return p;
+    }
+    size_t mark() const { return blocks.size(); }
+    void release(size_t m) { while (blocks.size() > m) { hipFree(blocks.back()); blocks.pop_back(); } }
+    bool h2d(void *d, const void *h, size_t n) { return e == hipSuccess && (e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)) == hipSuccess; }
+    bool d2h(void *h, const void *d, size_t n) {
+        if (e == hipSuccess) e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream);
+        return sync();
+    }
+    bool sync() { return e == hipSuccess && (e = hipStreamSynchronize(stream)) == hipSuccess; }
+    bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
+        if (e != hipSuccess) return false;
+        if (g1 <= g0) return true;
+        const dim3 grid((unsigned)(g1 - g0)), blk(64);
+        switch (kid) {
+            case KSW_K_TREE: hipLaunchKernelGGL(aasm_ksw_tree, grid, blk, 0, stream, g0, a); break;
+            case KSW_K_HEAP: hipLaunchKernelGGL(aasm_ksw_heap, grid, blk, 0, stream, g0, a); break;
+            case KSW_K_ENUM: hipLaunchKernelGGL(aasm_ksw_enum, grid, blk, 0, stream, g0, a); break;
+            case KSW_K_COUNT: hipLaunchKernelGGL(aasm_ksw_count, grid, blk, 0, stream, g0, a); break;
+            default: hipLaunchKernelGGL(aasm_ksw_fill, grid, blk, 0, stream, g0, a); break;
+        }
+        return (e = hipGetLastError()) == hipSuccess;
+    }
+    int err() {
+        if (e == hipSuccess) { set_last_error("aasm_k_shortest_walks: out of host memory"); return AASM_E_NOMEM; }
+        set_last_error(hip_err("aasm_k_shortest_walks", e));
+        return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP;
+    }
+};
+}  // namespace
+
+int aasm_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                          const int32_t *source, const int32_t *sink, int64_t k, int flags, int device, aasm_ksw_out *out) {
+    const char *why = "";
+    const int rc0 = ksw_check_args(n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, &why);
+    if (rc0 != AASM_OK) { set_last_error(std::string("aasm_k_shortest_walks: ") + why); return rc0; }
+    int rc = ctx_init(device);
+    if (rc != AASM_OK) return rc;
+    hipSetDevice(device);
+    KswGpu be;
+    be.stream = g_ctx[device].stream;
+    return ksw_run(be, n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, (int64_t)4 << 30);
+}
+
+void aasm_ksw_free(aasm_ksw_out *out) { ksw_free_out(out); }
 
 int64_t aasm_debug_counter(const char *name) {
     if (!name) return -1;

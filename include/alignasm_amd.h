@@ -233,6 +233,33 @@ int  aasm_sssp_dijkstra(int64_t n_graphs, const int64_t *g_voff, const int64_t *
 int  aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
                     const int32_t *src, int lim, int64_t *dist, int64_t *pre, int device);
 
+/* The solver's k shortest walks, k_shortest_walks(source, sink, k) with is_dag = true and kth_shortest_walk_recover()
+ * (src/k_shortest_walks.hpp:177-290), over a batch of DAGs in aasm_sssp_dijkstra's layout and weight domain (score sum >= 0,
+ * |scores| < 2^39, anom 0..2, qul counts 0..1), at most 2^20 vertices per graph, 1 <= k <= 2^24.  Results are the
+ * reference's with the monotonic allocator's queue ties (node arena index, then insertion index).  A walk is reported as
+ * caller CSR positions (global edge ids), source -> sink: a tree edge is the edge whose relaxation set best[], a sidetrack
+ * the edge its heap node was inserted for, so parallel edges stay apart.  A graph with a cycle gets status AASM_E_INVAL and
+ * no walks; the other graphs of the batch are solved.  Every array is allocated by the library: release with aasm_ksw_free. */
+#define AASM_KSW_WALKS      0x1     /* fill walk_off / walk_edges                                                     */
+#define AASM_KSW_TREE       0x2     /* fill d5 / best                                                                 */
+#define AASM_KSW_HOOK_ARENA 0x100   /* test hook, 0 in production: fill hook_arena / hook_hroot                       */
+typedef struct aasm_ksw_out {
+    int64_t  n_graphs, k;
+    int64_t *n_found;          /* [n_graphs] distances.size() of the reference (0 .. k)                              */
+    int64_t *dist5;            /* [n_graphs * k * 5] {qry, ref, anom, qnz, qtot} per walk (0 beyond n_found)         */
+    int64_t *walk_off;         /* [n_graphs * k + 1] into walk_edges (empty beyond n_found); AASM_KSW_WALKS          */
+    int64_t *walk_edges;       /* caller CSR positions, source -> sink; AASM_KSW_WALKS                               */
+    int64_t *d5;               /* [VT * 5] distance to the sink (PafDistance::max() where there is none); AASM_KSW_TREE */
+    int32_t *best;             /* [VT] next vertex towards the sink, local id (-1 = none); AASM_KSW_TREE              */
+    int64_t *heap_nodes;       /* [n_graphs] heap nodes the reference allocates                                     */
+    int32_t *status;           /* [n_graphs] 0, AASM_E_INVAL (cycle), AASM_E_OVERFLOW (heap or queue capacity)      */
+    int64_t *hook_arena;       /* AASM_KSW_HOOK_ARENA: {rank, key[5], u, v, left, right} per node, graph after graph */
+    int32_t *hook_hroot;       /* AASM_KSW_HOOK_ARENA: [VT] heap root as the graph's arena index (-1 = nullptr)      */
+} aasm_ksw_out;
+int  aasm_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                           const int32_t *source, const int32_t *sink, int64_t k, int flags, int device, aasm_ksw_out *out);
+void aasm_ksw_free(aasm_ksw_out *out);
+
 /* Same, with the batch already resident in device memory (in->pointers are device
  * pointers; in->ctg_rec_off / rec_rng_off too).  `stream` is a hipStream_t (or NULL).
  * The device result stays resident in an opaque handle until fetched/freed.          */

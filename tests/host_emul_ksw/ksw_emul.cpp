@@ -1,0 +1,60 @@
+// tests/host_emul_ksw/ksw_emul.cpp -- TEST INFRASTRUCTURE ONLY.
+//
+// The k-shortest-walks kernel bodies (alignasm_amd/csrc/aasm_ksw.h) and the host driver that sizes and launches them
+// (ksw_run), compiled for the HOST: a workgroup runs as its one working lane (nthreads = 1), device memory is poisoned host
+// memory.  The product library never links this file; its entry aasm_k_shortest_walks() needs a HIP device.
+#define AASM_HOST_EMUL 1
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../alignasm_amd/csrc/aasm_ksw.h"
+
+using namespace aasm;
+
+namespace {
+struct KswEmu {
+    std::vector<void *> blocks;
+    bool oom = false;
+    ~KswEmu() { for (void *p : blocks) free(p); }
+    void *alloc(size_t n) {
+        void *p = malloc(n);
+        if (!p) { oom = true; return nullptr; }
+        memset(p, 0xA5, n);                        // poison: catches reads of never-written cells
+        blocks.push_back(p);
+        return p;
+    }
+    size_t mark() const { return blocks.size(); }
+    void release(size_t m) { while (blocks.size() > m) { free(blocks.back()); blocks.pop_back(); } }
+    bool h2d(void *d, const void *h, size_t n) { memcpy(d, h, n); return true; }
+    bool d2h(void *h, const void *d, size_t n) { memcpy(h, d, n); return true; }
+    bool sync() { return true; }
+    bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
+        for (int64_t b = g0; b < g1; b++) {
+            KCtx k{0, 1, b, g1 - g0, 0, nullptr};
+            switch (kid) {
+                case KSW_K_TREE: kb_ksw_tree(k, a); break;
+                case KSW_K_HEAP: kb_ksw_heap(k, a); break;
+                case KSW_K_ENUM: kb_ksw_enum(k, a); break;
+                case KSW_K_COUNT: kb_ksw_count(k, a); break;
+                default: kb_ksw_fill(k, a); break;
+            }
+        }
+        return true;
+    }
+    int err() { return AASM_E_NOMEM; }
+};
+}  // namespace
+
+extern "C" {
+// aasm_k_shortest_walks() without a device; budget: bytes of "device" memory per chunk of graphs (<= 0: the product's 4 GiB)
+int emk_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                         const int32_t *source, const int32_t *sink, int64_t k, int flags, aasm_ksw_out *out, int64_t budget) {
+    const char *why = "";
+    const int rc = ksw_check_args(n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, &why);
+    if (rc != AASM_OK) return rc;
+    KswEmu be;
+    return ksw_run(be, n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, budget > 0 ? budget : (int64_t)4 << 30);
+}
+void emk_free(aasm_ksw_out *out) { ksw_free_out(out); }
+}
