@@ -237,20 +237,39 @@ class KswOut(C.Structure):
     ]
 
 
+def graph_inputs(g_voff, rowptr, col, source, sink=None, w5=None, cost=None, scalar_w=False):
+    """A graph batch (sssp_dijkstra's layout) as contiguous arrays in the C-ABI's types: (g_voff, rowptr, col, source, sink, w5, cost),
+    None for what was not given.  w5 is [E, 5] or flat; with scalar_w a 1-D w is [E] scalar weights, taken as (w, 0, 0, 0, 1),
+    which order as w does.  Raises ValueError when an array is shorter than the offsets say; the C side checks the rest."""
+    def flat(a, t):
+        return None if a is None else np.ascontiguousarray(a, t).reshape(-1)
+    g_voff, rowptr, col, source, sink, cost = (flat(g_voff, np.int64), flat(rowptr, np.int64), flat(col, np.int32), flat(source, np.int32),
+                                               flat(sink, np.int32), flat(cost, np.int32))
+    if w5 is not None:
+        w5 = np.asarray(w5, np.int64)
+        if scalar_w and w5.ndim == 1:
+            z = np.zeros_like(w5)
+            w5 = np.stack([w5, z, z, z, z + 1], 1)
+        w5 = flat(w5.reshape(-1, 5), np.int64)
+    # what the offsets ask for; offsets the C side refuses (not from 0, or decreasing) are left to it: it reads nothing through them
+    n_graphs = len(g_voff) - 1
+    need = {"source": (source, 1, n_graphs), "sink": (sink, 1, n_graphs)}
+    if n_graphs > 0 and g_voff[0] == 0 and (np.diff(g_voff) > 0).all():
+        n_vertices = int(g_voff[-1])
+        need["rowptr"] = (rowptr, 1, n_vertices + 1)
+        if len(rowptr) > n_vertices and rowptr[0] == 0 and (np.diff(rowptr[:n_vertices + 1]) >= 0).all():
+            n_edges = int(rowptr[n_vertices])
+            need.update(col=(col, 1, n_edges), w5=(w5, 5, n_edges), cost=(cost, 1, n_edges))
+    for name, (a, width, n) in need.items():
+        if a is not None and len(a) // width < n:
+            raise ValueError(f"{name}: {len(a) // width} rows, {n} needed")
+    return g_voff, rowptr, col, source, sink, w5, cost
+
+
 def ksw_inputs(g_voff, rowptr, col, w, source, sink):
-    """Contiguous arrays in the C-ABI's types; w is [E, 5] or [E] (a scalar w becomes (w, 0, 0, 0, 1): it orders as w does)."""
-    g_voff = np.ascontiguousarray(g_voff, np.int64)
-    rowptr = np.ascontiguousarray(rowptr, np.int64)
-    col = np.ascontiguousarray(col, np.int32)
-    w = np.asarray(w, np.int64)
-    if w.ndim == 1:
-        w5 = np.zeros((len(w), 5), np.int64)
-        w5[:, 0] = w
-        w5[:, 4] = 1
-    else:
-        w5 = w.reshape(-1, 5)
-    w5 = np.ascontiguousarray(w5, np.int64).reshape(-1)
-    return g_voff, rowptr, col, w5, np.ascontiguousarray(source, np.int32), np.ascontiguousarray(sink, np.int32)
+    """k_shortest_walks' arrays (graph_inputs with scalar weights allowed): g_voff, rowptr, col, w5, source, sink."""
+    g_voff, rowptr, col, source, sink, w5, _ = graph_inputs(g_voff, rowptr, col, source, sink, w5=w, scalar_w=True)
+    return g_voff, rowptr, col, w5, source, sink
 
 
 def unpack_ksw(out: KswOut, vt, flags):

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from ._abi import (AASM_E_INVAL, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, KswOut, Opts,
-                   OutSizes, Stats, SynthCfg, ksw_inputs, make_opts, unpack_ksw, unpack_out)
+                   OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AASM_LIB_OVERRIDE") or os.path.join(_HERE, "libalignasm_amd.so")   # override: diagnostic builds (tools/)
@@ -98,8 +98,7 @@ def device_count():
 def sssp_dijkstra(g_voff, rowptr, col, w5, src, device=0):
     """dijkstra() of the reference's solver (k_shortest_walks.hpp:69-87) on the GPU over a batch of graphs.
     Returns (d: [V, 5] int64, prev: [V] int32)."""
-    g_voff = np.ascontiguousarray(g_voff, np.int64); rowptr = np.ascontiguousarray(rowptr, np.int64)
-    col = np.ascontiguousarray(col, np.int32); w5 = np.ascontiguousarray(w5, np.int64).reshape(-1); src = np.ascontiguousarray(src, np.int32)
+    g_voff, rowptr, col, src, _, w5, _ = graph_inputs(g_voff, rowptr, col, src, w5=w5)
     VT = int(g_voff[-1])
     d = np.zeros((VT, 5), np.int64)
     prev = np.zeros(VT, np.int32)
@@ -131,8 +130,7 @@ def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=F
 def sssp_dial(g_voff, rowptr, col, cost, src, lim=2, device=0):
     """k_weighted_bfs() of the reference (Dial's bucketed BFS, k_weighted_bfs.hpp:16-37) on the GPU over a batch of digraphs.
     Returns (dist: [V] int64, -1 = unreachable; pre: [V] int64 local ids, -1 = none)."""
-    g_voff = np.ascontiguousarray(g_voff, np.int64); rowptr = np.ascontiguousarray(rowptr, np.int64)
-    col = np.ascontiguousarray(col, np.int32); cost = np.ascontiguousarray(cost, np.int32); src = np.ascontiguousarray(src, np.int32)
+    g_voff, rowptr, col, src, _, _, cost = graph_inputs(g_voff, rowptr, col, src, cost=cost)
     VT = int(g_voff[-1])
     dist, pre = np.zeros(VT, np.int64), np.zeros(VT, np.int64)
     P = lambda a: a.ctypes.data_as(C.c_void_p)

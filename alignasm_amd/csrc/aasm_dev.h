@@ -34,6 +34,12 @@ struct KCtx {
     char *lds;        // per-block LDS scratch (AASM_LDS_BYTES), 16-byte aligned
 };
 #define AASM_LDS_BYTES 6144   // 6 KB per single-wave block -> 26 blocks per CU by LDS
+// typed views of k.lds: in the LDS address space on the device, so stores through them provably miss the wave's private arrays
+#if defined(AASM_HOST_EMUL)
+#define AASM_LDS_VIEW
+#else
+#define AASM_LDS_VIEW __attribute__((address_space(3)))
+#endif
 
 // ------------------------------------------------------------------------------------
 // wave primitives (wave64 on gfx950; trivial with one lane)
@@ -130,10 +136,13 @@ AASM_DEV int ffs64(uint64_t m) { return __ffsll((long long)m); }
 // Wave-uniform values made explicitly scalar: v_readfirstlane moves them to SGPRs, so the
 // arithmetic and the branches that follow run on the scalar unit instead of occupying all
 // 64 VALU lanes with identical work.  Only valid where every lane holds the same value.
+// wave_readlane: lane j's value (wave-uniform j) in every lane, by v_readlane (a ds_bpermute in wave_bcast)
 #if defined(AASM_HOST_EMUL)
 AASM_DEV int32_t uni(int32_t x) { return x; }
+AASM_DEV int32_t wave_readlane(int32_t x, int) { return x; }
 #else
 AASM_DEV int32_t uni(int32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+AASM_DEV int32_t wave_readlane(int32_t x, int j) { return __builtin_amdgcn_readlane(x, j); }
 #endif
 AASM_DEV int64_t uni(int64_t x) {
     return (int64_t)(((uint64_t)(uint32_t)uni((int32_t)((uint64_t)x >> 32)) << 32) | (uint32_t)uni((int32_t)(uint32_t)(uint64_t)x));

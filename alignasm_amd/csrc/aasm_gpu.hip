@@ -2,6 +2,8 @@
 //
 // * one named __global__ per pipeline kernel (bodies: aasm_kernels.h), so rocprofv3
 //   --kernel-trace shows `aasm_k6_rev_sweep` etc.;
+// * the generic graph entries (dijkstra, Dial, k shortest walks): bodies, argument checks and host drivers in aasm_sssp.h and
+//   aasm_ksw.h, run here through one backend (GraphGpu);
 // * exclusive scans (count -> offsets): ONE launch each, single pass with decoupled look-back (aasm_scan_chain);
 // * a per-device arena: device memory is carved by bump allocation out of a few large
 //   hipMalloc blocks that persist across solves (no hipMalloc in the steady state);
@@ -144,88 +146,17 @@ __global__ void __launch_bounds__(256) aasm_t1_predicates(const int64_t *a, cons
     out[i] = r;
 }
 
-// ---- generic SSSP: the solver's dijkstra() (k_shortest_walks.hpp:69-87) ------------------------------
-// The reference's CLI never reaches it (is_dag = true, paf_data.cpp:728: the shortest-path tree is the DAG
-// relaxation, K6), but the solver class offers it for graphs with cycles and BASELINE.json's north_star names it.
-// One wave per graph, wave-uniform control: a binary min-heap of (Distance, vertex) in global memory with the
-// reference's order (std::greater on std::pair: PafDistance operator< in CALC_SUM mode, then the vertex), lazy
-// deletion by `dv != d[v]` (operator==), strict `d[to] > dv + w` relaxation of the popped vertex's list in list
-// order (sequential: a list may name a vertex twice).  Results equal the reference's d[] and prev[] exactly.
-struct DjEnt { Dist d; int32_t v, p0, p1, p2; };
-__device__ __forceinline__ bool dj_ent_less(const DjEnt &a, const DjEnt &b) {       // std::pair<Distance, int64_t> operator<
-    if (dist_lt<CALC_SUM_MODE>(a.d, b.d)) return true;
-    if (dist_lt<CALC_SUM_MODE>(b.d, a.d)) return false;
-    return a.v < b.v;
+// ---- the generic graph entries: one 64-lane workgroup per graph; bodies in aasm_sssp.h (★J dijkstra, K5 Dial) and aasm_ksw.h (★K) --
+__global__ void __launch_bounds__(64) aasm_sssp_dijkstra_kernel(SsspArgs a) {
+    KCtx k{(int)threadIdx.x, (int)blockDim.x, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr};
+    kb_sssp_dijkstra(k, a);
 }
-__global__ void __launch_bounds__(64) aasm_sssp_dijkstra_kernel(int64_t n_graphs, const int64_t *voff, const int64_t *rowptr, const int32_t *col,
-                                                                const int64_t *w5, const int32_t *src, Dist *d, int32_t *prv, DjEnt *heap, const int64_t *hoff) {
-    const int64_t g = blockIdx.x;
-    if (g >= n_graphs) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t vb = voff[g], V = voff[g + 1] - vb;
-    Dist *dg = d + vb;
-    int32_t *pg = prv + vb;
-    DjEnt *H = heap + hoff[g];
-    for (int64_t v = lane; v < V; v += 64) { dg[v] = dist_max(); pg[v] = -1; }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    int64_t n = 0;
-    const int64_t cap = hoff[g + 1] - hoff[g];
-    bool over = false;
-    auto push = [&](const Dist &dd, int32_t v) {
-        DjEnt x; x.d = dd; x.v = v; x.p0 = x.p1 = x.p2 = 0;
-        if (n >= cap) { over = true; return; }                       // more relaxations than edges: a cycle keeps improving the order (the reference would not return)
-        int64_t i = n++;
-        while (i > 0) {
-            const int64_t p = (i - 1) >> 1;
-            const DjEnt pe = H[p];
-            if (!uni(dj_ent_less(x, pe))) break;
-            if (lane == 0) H[i] = pe;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            i = p;
-        }
-        if (lane == 0) H[i] = x;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    };
-    const int32_t s = src[g];
-    if (lane == 0) dg[s] = dist_zero();                              // IDENTITY_DISTANCE (:74)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    push(dist_zero(), s);
-    while (n > 0 && !over) {
-        const DjEnt top = H[0];
-        const DjEnt x = H[--n];
-        if (n > 0) {                                                 // pop: the last entry sinks from the root
-            int64_t i = 0;
-            while (true) {
-                int64_t c = 2 * i + 1;
-                if (c >= n) break;
-                DjEnt ce = H[c];
-                if (c + 1 < n) { const DjEnt ce2 = H[c + 1]; if (uni(dj_ent_less(ce2, ce))) { ce = ce2; c++; } }
-                if (!uni(dj_ent_less(ce, x))) break;
-                if (lane == 0) H[i] = ce;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                i = c;
-            }
-            if (lane == 0) H[i] = x;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
-        const int32_t v = uni(top.v);
-        const Dist dv = uni(top.d);
-        if (!uni(dist_eq(dv, dg[v]))) continue;                      // :79 (operator!=)
-        for (int64_t e = rowptr[vb + v]; e < rowptr[vb + v + 1]; e++) {
-            const int32_t to = uni(col[e]);
-            Dist wd; wd.qry = w5[5 * e]; wd.ref = w5[5 * e + 1]; wd.anom = (int32_t)w5[5 * e + 2]; wd.qnz = (int32_t)w5[5 * e + 3]; wd.qtot = (int32_t)w5[5 * e + 4]; wd.pad = 0;
-            const Dist cand = uni(dist_add(dv, wd));
-            if (uni(dist_lt<CALC_SUM_MODE>(cand, dg[to]))) {         // d_[to] > dv + w (:81)
-                if (lane == 0) { dg[to] = cand; pg[to] = v; }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                push(cand, to);
-            }
-        }
-    }
-    if (over && lane == 0) pg[s] = -2;                               // reported by the host entry
+__global__ void __launch_bounds__(64) aasm_sssp_dial_kernel(SsspArgs a) {
+    __shared__ DialLds L;
+    KCtx k{(int)threadIdx.x, (int)blockDim.x, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), (char *)&L};
+    kb_sssp_dial(k, a);
 }
-
-// ---- k shortest walks on caller DAGs (row ★K): bodies in aasm_ksw.h, one 64-lane workgroup per graph of [g0, g0 + grid) --
+// k-walks: the graphs [g0, g0 + grid)
 #define AASM_DEF_KSW_KERNEL(name, body)                                                                           \
     __global__ void __launch_bounds__(64) name(int64_t g0, KswArgs a) {                                           \
         KCtx k{(int)threadIdx.x, (int)blockDim.x, g0 + (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr}; \
@@ -236,122 +167,6 @@ AASM_DEF_KSW_KERNEL(aasm_ksw_heap, kb_ksw_heap)
 AASM_DEF_KSW_KERNEL(aasm_ksw_enum, kb_ksw_enum)
 AASM_DEF_KSW_KERNEL(aasm_ksw_count, kb_ksw_count)
 AASM_DEF_KSW_KERNEL(aasm_ksw_fill, kb_ksw_fill)
-
-// ---- Dial's bucketed BFS (k_weighted_bfs.hpp:16-37), one wave per graph -------------------------------------------------
-// The reference keeps lim + 1 circular buckets, each a LIFO stack, and walks d = 0, 1, ...: pop the top of bucket d mod (lim + 1),
-// skip it when its distance is stale, relax its out-edges in list order; a successful relaxation (dist[nxt] == -1 or > d + cost)
-// sets dist / pre and pushes nxt onto bucket (d + cost) mod (lim + 1).  dist is order-independent, pre is not: it names the FIRST
-// vertex, in the reference's pop order, that reached the final distance - so the pops stay sequential and the relaxations of ONE
-// popped row run on the lanes:
-//  * buckets staged in LDS: every stack's top DIAL_WIN entries live in an LDS ring (ring slot = stack position mod DIAL_WIN);
-//    a full ring spills its lower half to the stack's slice of global memory in one coalesced store, an empty one refills from it;
-//  * a row is relaxed 64 edges at a time; the lanes that succeed are compacted PER BUCKET by ballot + prefix count, so a chunk's
-//    pushes land on every stack in list order (what the LIFO pops then reverse, as in the reference);
-//  * a chunk that names a head twice (parallel edges) is relaxed edge by edge - the second edge must see the first one's result.
-// The solver drives it with lim = 2 on the anomaly weights and keeps one scalar (paf_data.cpp:704-715), which the pipeline folds
-// into its forward sweep; this entry is the algorithm itself, for any digraph (cycles allowed) and weights 0 .. lim <= 7.
-#define DIAL_WIN 256
-#define DIAL_MAXB 8
-struct DialLds { int32_t ring[DIAL_MAXB][DIAL_WIN]; };
-__global__ void __launch_bounds__(64) aasm_sssp_dial_kernel(int64_t n_graphs, const int64_t *voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
-                                                            const int32_t *src, int32_t nb, int64_t *dist, int64_t *pre, int32_t *spill, const int64_t *soff) {
-    __shared__ DialLds L;
-    const int64_t g = blockIdx.x;
-    if (g >= n_graphs) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t vb = voff[g], V = voff[g + 1] - vb;
-    int64_t *dg = dist + vb, *pg = pre + vb;
-    const int64_t cap = (soff[g + 1] - soff[g]) / nb;                // per bucket
-    int32_t *sp = spill + soff[g];
-    for (int64_t v = lane; v < V; v += 64) { dg[v] = -1; pg[v] = -1; }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    int32_t base[DIAL_MAXB], cnt[DIAL_MAXB];                        // stack b = global [0, base) + ring [base, base + cnt)
-#pragma unroll
-    for (int b = 0; b < DIAL_MAXB; b++) { base[b] = 0; cnt[b] = 0; }
-    bool over = false;
-    // room for m more entries on stack b (m <= 64): spill the lower half of a ring that would overflow
-    auto make_room = [&](int b, int32_t m) {
-#pragma unroll
-        for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b && cnt[bb] + m > DIAL_WIN) {
-            const int32_t n = DIAL_WIN / 2;
-            if ((int64_t)base[bb] + n > cap) { over = true; return; }
-            for (int32_t t = lane; t < n; t += 64) sp[(int64_t)bb * cap + base[bb] + t] = L.ring[bb][(base[bb] + t) & (DIAL_WIN - 1)];
-            base[bb] += n; cnt[bb] -= n;
-        }
-    };
-    auto push_lanes = [&](int b, bool mine, int32_t v) {             // the lanes with `mine` push v onto stack b, in lane order
-        const uint64_t m = __ballot(mine);
-        if (!m) return;
-        make_room(b, __popcll(m));
-        if (over) return;
-#pragma unroll
-        for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) {
-            if (mine) L.ring[bb][(base[bb] + cnt[bb] + __popcll(m & ((1ull << lane) - 1ull))) & (DIAL_WIN - 1)] = v;
-            cnt[bb] += __popcll(m);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    };
-    const int32_t s0 = src[g];
-    if (lane == 0) dg[s0] = 0;
-    push_lanes(0, lane == 0, s0);
-    int64_t maxd = 0;
-    for (int64_t d = 0; d <= maxd && !over; d++) {
-        const int b = (int)(d % nb);
-        while (!over) {
-            int32_t c_b = 0, b_b = 0;
-#pragma unroll
-            for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) { c_b = cnt[bb]; b_b = base[bb]; }
-            if (c_b == 0) {
-                if (b_b == 0) break;                                 // the bucket is empty
-                const int32_t n = b_b < DIAL_WIN / 2 ? b_b : DIAL_WIN / 2;   // refill the ring from the stack's global part
-                for (int32_t t = lane; t < n; t += 64) L.ring[b][(b_b - n + t) & (DIAL_WIN - 1)] = sp[(int64_t)b * cap + b_b - n + t];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#pragma unroll
-                for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) { base[bb] -= n; cnt[bb] += n; }
-                continue;
-            }
-            const int32_t cur = __builtin_amdgcn_readfirstlane(L.ring[b][(b_b + c_b - 1) & (DIAL_WIN - 1)]);   // q.back(); q.pop_back()
-#pragma unroll
-            for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) cnt[bb]--;
-            const int64_t dc = dg[cur];
-            if (__builtin_amdgcn_readfirstlane((int32_t)(dc != d))) continue;   // stale (:24)
-            const int64_t r0 = rowptr[vb + cur], r1 = rowptr[vb + cur + 1];
-            for (int64_t e0 = r0; e0 < r1 && !over; e0 += 64) {
-                const int64_t e = e0 + lane;
-                const bool act = e < r1;
-                const int32_t nxt = act ? col[e] : -1 - lane;
-                const int32_t cs = act ? cost[e] : 0;
-                // a head named twice in this chunk?  (lane i looks at the lanes below it)
-                bool dup = false;
-                const int32_t nlan = (int32_t)((r1 - e0 < 64) ? (r1 - e0) : 64);
-                for (int32_t j = 0; j + 1 < nlan; j++) dup |= (lane > j) && (__builtin_amdgcn_readlane(nxt, j) == nxt);
-                if (__ballot(dup)) {                                 // edge by edge, as the reference (:25-32)
-                    for (int32_t j = 0; j < nlan && !over; j++) {
-                        const int32_t nj = __builtin_amdgcn_readlane(nxt, j), cj = __builtin_amdgcn_readlane(cs, j);
-                        const int64_t nd = d + cj, dn = dg[nj];
-                        const bool ok = __builtin_amdgcn_readfirstlane((int32_t)(dn == -1 || dn > nd)) != 0;
-                        if (!ok) continue;
-                        if (lane == 0) { dg[nj] = nd; pg[nj] = cur; }
-                        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                        push_lanes((int)(nd % nb), lane == 0, nj);
-                        if (nd > maxd) maxd = nd;
-                    }
-                    continue;
-                }
-                const int64_t nd = d + cs;
-                bool ok = false;
-                if (act) { const int64_t dn = dg[nxt]; ok = dn == -1 || dn > nd; if (ok) { dg[nxt] = nd; pg[nxt] = cur; } }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                const int bk = (int)(nd % nb);
-                for (int bb = 0; bb < nb && !over; bb++) push_lanes(bb, ok && bk == bb, nxt);
-                int64_t mx = ok ? nd : 0;
-                for (int o = 32; o >= 1; o >>= 1) { const int64_t y = __shfl_xor(mx, o, 64); mx = y > mx ? y : mx; }
-                if (mx > maxd) maxd = mx;
-            }
-        }
-    }
-    if (over && lane == 0) pg[s0] = -2;                              // reported by the host entry
-}
 
 // ---- exclusive scan: T in -> int64 out[n+1] -----------------------------------------
 // ONE launch per scan (the pipeline runs ~14 per batch, most over 7-15 M entries): tiles take their number from a
@@ -831,6 +646,70 @@ struct GpuBackend {
     void phase_end(int ph) { flush_zero(); if (timing && !fail) { hipError_t e = hipEventRecord(cx.ev_e[ph], stream); if (e != hipSuccess) hip_fail("hipEventRecord", e); } }
 };
 
+// The backend of the generic graph entries (dijkstra_run, dial_run, ksw_run; contract in aasm_ksw.h) and of the debug entries:
+// plain hipMalloc blocks freed with it, copies and launches on the device's stream.  entry names the C-ABI entry in messages.
+struct GraphGpu {
+    hipStream_t stream;
+    const char *entry;
+    hipError_t e = hipSuccess;
+    std::vector<void *> blocks;
+    ~GraphGpu() { for (void *p : blocks) hipFree(p); }
+    void *alloc(size_t n) {
+        void *p = nullptr;
+        if (e != hipSuccess) return nullptr;
+        if ((e = hipMalloc(&p, n)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        blocks.push_back(p);
+        return p;
+    }
+    size_t mark() const { return blocks.size(); }
+    void release(size_t m) { while (blocks.size() > m) { hipFree(blocks.back()); blocks.pop_back(); } }
+    bool h2d(void *d, const void *h, size_t n) { return e == hipSuccess && (e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)) == hipSuccess; }
+    bool fill(void *d, int byte, size_t n) { return e == hipSuccess && (e = hipMemsetAsync(d, byte, n, stream)) == hipSuccess; }
+    bool d2h(void *h, const void *d, size_t n) {
+        if (e == hipSuccess) e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream);
+        return sync();
+    }
+    bool sync() { return e == hipSuccess && (e = hipStreamSynchronize(stream)) == hipSuccess; }
+    bool launched() { return e == hipSuccess && (e = hipGetLastError()) == hipSuccess; }
+    bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
+        if (e != hipSuccess) return false;
+        if (g1 <= g0) return true;
+        const dim3 grid((unsigned)(g1 - g0)), blk(64);
+        switch (kid) {
+            case KSW_K_TREE: hipLaunchKernelGGL(aasm_ksw_tree, grid, blk, 0, stream, g0, a); break;
+            case KSW_K_HEAP: hipLaunchKernelGGL(aasm_ksw_heap, grid, blk, 0, stream, g0, a); break;
+            case KSW_K_ENUM: hipLaunchKernelGGL(aasm_ksw_enum, grid, blk, 0, stream, g0, a); break;
+            case KSW_K_COUNT: hipLaunchKernelGGL(aasm_ksw_count, grid, blk, 0, stream, g0, a); break;
+            default: hipLaunchKernelGGL(aasm_ksw_fill, grid, blk, 0, stream, g0, a); break;
+        }
+        return launched();
+    }
+    bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
+        if (e != hipSuccess) return false;
+        const dim3 grid((unsigned)n_graphs), blk(64);
+        if (kid == SSSP_K_DIJKSTRA) hipLaunchKernelGGL(aasm_sssp_dijkstra_kernel, grid, blk, 0, stream, a);
+        else hipLaunchKernelGGL(aasm_sssp_dial_kernel, grid, blk, 0, stream, a);
+        return launched();
+    }
+    int err() {
+        if (e == hipSuccess) { set_last_error(std::string(entry) + ": out of host memory"); return AASM_E_NOMEM; }
+        set_last_error(hip_err(entry, e));
+        return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP;
+    }
+};
+
+// A generic graph entry after its argument checks (rc, with their message in why): the device, then run(GraphGpu &) - the driver,
+// which may set why too.  Nothing touches a device unless the checks pass.
+template <class Run> static int graph_entry(const char *entry, int rc, const char *const &why, int device, Run run) {
+    if (rc == AASM_OK && (rc = ctx_init(device)) == AASM_OK) {
+        hipSetDevice(device);
+        GraphGpu be{g_ctx[device].stream, entry};
+        rc = run(be);
+    }
+    if (*why) set_last_error(std::string(entry) + ": " + why);
+    return rc;
+}
+
 }  // namespace aasm
 
 using namespace aasm;
@@ -1089,21 +968,13 @@ int aasm_debug_predicates(const int64_t *a, const int64_t *b, int64_t n, uint8_t
     int rc = ctx_init(device);
     if (rc != AASM_OK) return rc;
     hipSetDevice(device);
-    int64_t *da = nullptr, *db = nullptr;
-    uint8_t *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&da, (size_t)n * 40);
-    if (e == hipSuccess) e = hipMalloc((void **)&db, (size_t)n * 40);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(da, a, (size_t)n * 40, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, b, (size_t)n * 40, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(aasm_t1_predicates, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, g_ctx[device].stream, da, db, n, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(g_ctx[device].stream);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n, hipMemcpyDeviceToHost);
-    hipFree(da); hipFree(db); hipFree(dout);
-    if (e != hipSuccess) { set_last_error(hip_err("aasm_debug_predicates", e)); return AASM_E_HIP; }
+    GraphGpu be{g_ctx[device].stream, "aasm_debug_predicates"};
+    DevMem<GraphGpu> m{be};
+    const int64_t *da = (const int64_t *)m.up(a, (size_t)n * 40), *db = (const int64_t *)m.up(b, (size_t)n * 40);
+    uint8_t *dout = (uint8_t *)m.alloc((size_t)n);
+    if (!m.ok) return be.err();
+    hipLaunchKernelGGL(aasm_t1_predicates, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, be.stream, da, db, n, dout);
+    if (!be.launched() || !be.d2h(out, dout, (size_t)n)) return be.err();
     return AASM_OK;
 }
 
@@ -1117,236 +988,60 @@ int aasm_debug_sort_replay(const int64_t *rec_off, int64_t n_contigs, const int6
     int rc = ctx_init(device);
     if (rc != AASM_OK) return rc;
     hipSetDevice(device);
-    std::vector<void *> dev;
-    hipError_t e = hipSuccess;
-    auto up = [&](const void *p, size_t bytes, int fill) -> void * {
-        void *q = nullptr;
-        if (e != hipSuccess) return nullptr;
-        if ((e = hipMalloc(&q, bytes ? bytes : 8)) != hipSuccess) return nullptr;
-        dev.push_back(q);
-        if (p) e = hipMemcpy(q, p, bytes, hipMemcpyHostToDevice);
-        else e = hipMemset(q, fill, bytes);
-        return q;
-    };
+    GraphGpu be{g_ctx[device].stream, "aasm_debug_sort_replay"};
+    DevMem<GraphGpu> m{be};
+    auto filled = [&](size_t bytes, int byte) { void *p = m.alloc(bytes); if (m.ok && !be.fill(p, byte, bytes)) m.ok = false; return p; };
     WS w;
     std::memset(&w, 0, sizeof(w));
     w.C = n_contigs; w.R = R; w.R0 = 0; w.sort_depth_test = depth_test;
-    w.rec_off = (const int64_t *)up(rec_off, (size_t)(n_contigs + 1) * 8, 0);
-    w.in_qs = (const int64_t *)up(qs, (size_t)R * 8, 0); w.in_qe = (const int64_t *)up(qe, (size_t)R * 8, 0);
-    w.s_qs = (int64_t *)up(nullptr, (size_t)R * 8, 0); w.s_qe = (int64_t *)up(nullptr, (size_t)R * 8, 0); w.s_orig = (int32_t *)up(nullptr, (size_t)R * 4, 0);
-    w.perm = (int32_t *)up(nullptr, (size_t)R * 4, 0xff);
+    w.rec_off = (const int64_t *)m.up(rec_off, (size_t)(n_contigs + 1) * 8);
+    w.in_qs = (const int64_t *)m.up(qs, (size_t)R * 8); w.in_qe = (const int64_t *)m.up(qe, (size_t)R * 8);
+    w.s_qs = (int64_t *)filled((size_t)R * 8, 0); w.s_qe = (int64_t *)filled((size_t)R * 8, 0); w.s_orig = (int32_t *)filled((size_t)R * 4, 0);
+    w.perm = (int32_t *)filled((size_t)R * 4, 0xff);
     std::vector<int32_t> ones((size_t)n_contigs, 1);
-    w.dupflag = (int32_t *)up(ones.data(), (size_t)n_contigs * 4, 0);
+    w.dupflag = (int32_t *)m.up(ones.data(), (size_t)n_contigs * 4);
 #if defined(AASM_KPROF)
-    w.prof_heap = (int64_t *)up(nullptr, (size_t)n_contigs * 64, 0);
+    w.prof_heap = (int64_t *)filled((size_t)n_contigs * 64, 0);
 #endif
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(aasm_k1_sort_fix, dim3((unsigned)n_contigs), dim3(64), 0, g_ctx[device].stream, w);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(g_ctx[device].stream);
-    if (e == hipSuccess) e = hipMemcpy(perm_out, w.perm, (size_t)R * 4, hipMemcpyDeviceToHost);
+    if (!m.ok) return be.err();
+    hipLaunchKernelGGL(aasm_k1_sort_fix, dim3((unsigned)n_contigs), dim3(64), 0, be.stream, w);
+    if (!be.launched() || !be.d2h(perm_out, w.perm, (size_t)R * 4)) return be.err();
 #if defined(AASM_KPROF)
-    if (e == hipSuccess) {                                           // diagnostic build: mean cycles per section over the contigs
+    {                                                                // diagnostic build: mean cycles per section over the contigs
         std::vector<int64_t> kp((size_t)n_contigs * 8);
-        hipMemcpy(kp.data(), w.prof_heap, kp.size() * 8, hipMemcpyDeviceToHost);
-        double m[8] = {0};
-        for (int64_t c = 0; c < n_contigs; c++) for (int i = 0; i < 8; i++) m[i] += (double)kp[(size_t)c * 8 + i] / (double)n_contigs;
-        fprintf(stderr, "sort_fix sections (mean cycles): load %.0f  A %.0f  B %.0f  C %.0f  global partitions %.0f  wave lifetime %.1f us\n", m[0], m[1], m[2], m[3], m[4], m[7] / 100.0);
+        be.d2h(kp.data(), w.prof_heap, kp.size() * 8);
+        double mean[8] = {0};
+        for (int64_t c = 0; c < n_contigs; c++) for (int i = 0; i < 8; i++) mean[i] += (double)kp[(size_t)c * 8 + i] / (double)n_contigs;
+        fprintf(stderr, "sort_fix sections (mean cycles): load %.0f  A %.0f  B %.0f  C %.0f  global partitions %.0f  wave lifetime %.1f us\n", mean[0], mean[1], mean[2], mean[3], mean[4], mean[7] / 100.0);
     }
 #endif
-    for (void *q : dev) hipFree(q);
-    if (e != hipSuccess) { set_last_error(hip_err("aasm_debug_sort_replay", e)); return AASM_E_HIP; }
     return AASM_OK;
 }
 
 // dijkstra (k_shortest_walks.hpp:69-87) over a batch of graphs; host pointers in and out
 int aasm_sssp_dijkstra(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
                        const int32_t *src, int64_t *d5, int32_t *prev, int device) {
-    if (n_graphs <= 0 || !g_voff || !rowptr || !col || !w5 || !src || !d5 || !prev) return AASM_E_INVAL;
-    int rc = ctx_init(device);
-    if (rc != AASM_OK) return rc;
-    hipSetDevice(device);
-    const int64_t VT = g_voff[n_graphs], ET = rowptr[VT];
-    if (VT <= 0 || g_voff[0] != 0 || rowptr[0] != 0) { set_last_error("inconsistent graph offsets"); return AASM_E_INVAL; }
-    std::vector<int64_t> hoff((size_t)n_graphs + 1, 0);
-    for (int64_t g = 0; g < n_graphs; g++) {
-        const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
-        if (v1 <= v0 || src[g] < 0 || src[g] >= v1 - v0) { set_last_error("graph " + std::to_string(g) + ": empty, or source outside it"); return AASM_E_INVAL; }
-        hoff[(size_t)g + 1] = hoff[(size_t)g] + (rowptr[v1] - rowptr[v0]) + 2;   // every successful relaxation pushes once: <= E + 1 entries
-        for (int64_t e = rowptr[v0]; e < rowptr[v1]; e++)
-            if (col[e] < 0 || col[e] >= v1 - v0) { set_last_error("graph " + std::to_string(g) + ": edge head outside the graph"); return AASM_E_INVAL; }
-    }
-    for (int64_t e = 0; e < ET; e++)
-        if (!(host_coord_ok(w5[5 * e] + AASM_COORD_LIMIT / 2) && host_coord_ok(w5[5 * e + 1] + AASM_COORD_LIMIT / 2)) || w5[5 * e + 2] < 0 || w5[5 * e + 2] > 2 || w5[5 * e + 3] < 0 || w5[5 * e + 3] > 1 ||
-            w5[5 * e + 4] < 0 || w5[5 * e + 4] > 1 || w5[5 * e] + w5[5 * e + 1] < 0) {
-            set_last_error("edge " + std::to_string(e) + ": weight outside the supported range (score sum >= 0, |scores| < 2^39, anom 0..2, mapq counts 0..1)");
-            return AASM_E_OVERFLOW;
-        }
-    std::vector<void *> dev;
-    bool ok = true;
-    hipError_t e = hipSuccess;
-    auto up = [&](const void *p, size_t bytes) -> void * {
-        void *q = nullptr;
-        if (!ok) return nullptr;
-        if ((e = hipMalloc(&q, bytes ? bytes : 8)) != hipSuccess) { ok = false; return nullptr; }
-        dev.push_back(q);
-        if (p && bytes && (e = hipMemcpy(q, p, bytes, hipMemcpyHostToDevice)) != hipSuccess) ok = false;
-        return q;
-    };
-    const int64_t *d_voff = (const int64_t *)up(g_voff, (size_t)(n_graphs + 1) * 8), *d_rowptr = (const int64_t *)up(rowptr, (size_t)(VT + 1) * 8);
-    const int32_t *d_col = (const int32_t *)up(col, (size_t)ET * 4), *d_src = (const int32_t *)up(src, (size_t)n_graphs * 4);
-    const int64_t *d_w = (const int64_t *)up(w5, (size_t)ET * 40);
-    Dist *d_d = (Dist *)up(nullptr, (size_t)VT * sizeof(Dist));
-    int32_t *d_prv = (int32_t *)up(nullptr, (size_t)VT * 4);
-    std::vector<Dist> hd((size_t)VT);
-    // Heap capacity.  With a monotone order every successful relaxation pushes once (<= E + 1 entries), but CALC_SUM's third
-    // key (the mapq ratio) is not monotone under addition and the reference re-expands a vertex whenever its distance
-    // improves, so stale entries of one edge can pile up: a graph whose heap overflows is run again with 4x, 16x, 64x the room.
-    int64_t overflowed = -1;
-    for (int64_t mult = 1; ok && mult <= 64; mult *= 4) {
-        std::vector<int64_t> ho((size_t)n_graphs + 1, 0);
-        for (int64_t g = 0; g < n_graphs; g++) ho[(size_t)g + 1] = ho[(size_t)g] + mult * (hoff[(size_t)g + 1] - hoff[(size_t)g]);
-        const size_t n_dev0 = dev.size();
-        const int64_t *d_hoff = (const int64_t *)up(ho.data(), (size_t)(n_graphs + 1) * 8);
-        DjEnt *d_heap = (DjEnt *)up(nullptr, (size_t)ho[(size_t)n_graphs] * sizeof(DjEnt));
-        if (ok) {
-            hipLaunchKernelGGL(aasm_sssp_dijkstra_kernel, dim3((unsigned)n_graphs), dim3(64), 0, g_ctx[device].stream, n_graphs, d_voff, d_rowptr, d_col, d_w, d_src, d_d, d_prv, d_heap, d_hoff);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(g_ctx[device].stream);
-            if (e == hipSuccess) e = hipMemcpy(hd.data(), d_d, (size_t)VT * sizeof(Dist), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(prev, d_prv, (size_t)VT * 4, hipMemcpyDeviceToHost);
-            ok = e == hipSuccess;
-        }
-        while (dev.size() > n_dev0) { hipFree(dev.back()); dev.pop_back(); }
-        overflowed = -1;
-        if (ok) for (int64_t g = 0; g < n_graphs; g++) if (prev[g_voff[g] + src[g]] == -2) { overflowed = g; break; }
-        if (overflowed < 0) break;
-    }
-    for (void *q : dev) hipFree(q);
-    if (!ok) { set_last_error(hip_err("aasm_sssp_dijkstra", e)); return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP; }
-    if (overflowed >= 0) { set_last_error("graph " + std::to_string(overflowed) + ": dijkstra heap capacity exceeded at 64 x (E + 2) entries"); return AASM_E_OVERFLOW; }
-    for (int64_t v = 0; v < VT; v++) { d5[5 * v] = hd[(size_t)v].qry; d5[5 * v + 1] = hd[(size_t)v].ref; d5[5 * v + 2] = hd[(size_t)v].anom; d5[5 * v + 3] = hd[(size_t)v].qnz; d5[5 * v + 4] = hd[(size_t)v].qtot; }
-    return AASM_OK;
+    const char *why = "";
+    const int rc = dijkstra_check_args(n_graphs, g_voff, rowptr, col, w5, src, d5, prev, &why);
+    return graph_entry("aasm_sssp_dijkstra", rc, why, device, [&](GraphGpu &be) { return dijkstra_run(be, n_graphs, g_voff, rowptr, col, w5, src, d5, prev, &why); });
 }
 
 // Dial's bucketed BFS (k_weighted_bfs.hpp:16-37) over a batch of graphs; host pointers in and out
 int aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
                    const int32_t *src, int lim, int64_t *dist, int64_t *pre, int device) {
-    if (n_graphs <= 0 || !g_voff || !rowptr || !col || !cost || !src || !dist || !pre) return AASM_E_INVAL;
-    if (lim < 0 || lim + 1 > DIAL_MAXB) { set_last_error("aasm_sssp_dial: lim outside 0 .. 7"); return AASM_E_INVAL; }
-    int rc = ctx_init(device);
-    if (rc != AASM_OK) return rc;
-    hipSetDevice(device);
-    const int nb = lim + 1;
-    // the offsets first, before anything is read THROUGH them: graph starts strictly increasing from 0, row pointers non-decreasing from 0
-    if (g_voff[0] != 0) { set_last_error("inconsistent graph offsets"); return AASM_E_INVAL; }
-    for (int64_t g = 0; g < n_graphs; g++)
-        if (g_voff[g + 1] <= g_voff[g]) { set_last_error("graph " + std::to_string(g) + ": empty, or graph offsets not increasing"); return AASM_E_INVAL; }
-    const int64_t VT = g_voff[n_graphs];
-    if (VT <= 0 || rowptr[0] != 0) { set_last_error("inconsistent graph offsets"); return AASM_E_INVAL; }
-    for (int64_t v = 0; v < VT; v++)
-        if (rowptr[v + 1] < rowptr[v]) { set_last_error("row pointers decrease at vertex " + std::to_string(v)); return AASM_E_INVAL; }
-    const int64_t ET = rowptr[VT];
-    std::vector<int64_t> soff((size_t)n_graphs + 1, 0);
-    for (int64_t g = 0; g < n_graphs; g++) {
-        const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
-        if (v1 <= v0 || src[g] < 0 || src[g] >= v1 - v0) { set_last_error("graph " + std::to_string(g) + ": empty, or source outside it"); return AASM_E_INVAL; }
-        for (int64_t e = rowptr[v0]; e < rowptr[v1]; e++) {
-            if (col[e] < 0 || col[e] >= v1 - v0) { set_last_error("graph " + std::to_string(g) + ": edge head outside the graph"); return AASM_E_INVAL; }
-            if (cost[e] < 0 || cost[e] > lim) { set_last_error("edge " + std::to_string(e) + ": cost outside 0 .. lim (the reference asserts it, k_weighted_bfs.hpp:27)"); return AASM_E_INVAL; }
-        }
-        // a vertex is pushed once per successful relaxation: its distance falls by at least one each time and by at most lim in all
-        // after the first (a later pop has d' >= d), so <= lim + 1 pushes per vertex - and never more than one per edge, plus the source
-        const int64_t E = rowptr[v1] - rowptr[v0], by_v = (v1 - v0) * (int64_t)nb;
-        const int64_t per = ((E + 1 < by_v ? E + 1 : by_v) + DIAL_WIN + 63) / 64 * 64;
-        soff[(size_t)g + 1] = soff[(size_t)g] + per * nb;
-    }
-    std::vector<void *> dev;
-    bool ok = true;
-    hipError_t e = hipSuccess;
-    auto up = [&](const void *p, size_t bytes) -> void * {
-        void *q = nullptr;
-        if (!ok) return nullptr;
-        if ((e = hipMalloc(&q, bytes ? bytes : 8)) != hipSuccess) { ok = false; return nullptr; }
-        dev.push_back(q);
-        if (p && bytes && (e = hipMemcpy(q, p, bytes, hipMemcpyHostToDevice)) != hipSuccess) ok = false;
-        return q;
-    };
-    const int64_t *d_voff = (const int64_t *)up(g_voff, (size_t)(n_graphs + 1) * 8), *d_rowptr = (const int64_t *)up(rowptr, (size_t)(VT + 1) * 8);
-    const int32_t *d_col = (const int32_t *)up(col, (size_t)ET * 4), *d_cost = (const int32_t *)up(cost, (size_t)ET * 4), *d_src = (const int32_t *)up(src, (size_t)n_graphs * 4);
-    const int64_t *d_soff = (const int64_t *)up(soff.data(), (size_t)(n_graphs + 1) * 8);
-    int64_t *d_dist = (int64_t *)up(nullptr, (size_t)VT * 8), *d_pre = (int64_t *)up(nullptr, (size_t)VT * 8);
-    int32_t *d_spill = (int32_t *)up(nullptr, (size_t)soff[(size_t)n_graphs] * 4);
-    if (ok) {
-        hipLaunchKernelGGL(aasm_sssp_dial_kernel, dim3((unsigned)n_graphs), dim3(64), 0, g_ctx[device].stream, n_graphs, d_voff, d_rowptr, d_col, d_cost, d_src, (int32_t)nb, d_dist, d_pre, d_spill, d_soff);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(g_ctx[device].stream);
-        if (e == hipSuccess) e = hipMemcpy(dist, d_dist, (size_t)VT * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(pre, d_pre, (size_t)VT * 8, hipMemcpyDeviceToHost);
-        ok = e == hipSuccess;
-    }
-    for (void *q : dev) hipFree(q);
-    if (!ok) { set_last_error(hip_err("aasm_sssp_dial", e)); return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP; }
-    for (int64_t g = 0; g < n_graphs; g++)
-        if (pre[g_voff[g] + src[g]] == -2) { set_last_error("graph " + std::to_string(g) + ": bucket capacity exceeded (must not happen)"); return AASM_E_INTERNAL; }
-    return AASM_OK;
+    const char *why = "";
+    const int rc = dial_check_args(n_graphs, g_voff, rowptr, col, cost, src, lim, dist, pre, &why);
+    return graph_entry("aasm_sssp_dial", rc, why, device, [&](GraphGpu &be) { return dial_run(be, n_graphs, g_voff, rowptr, col, cost, src, lim, dist, pre, &why); });
 }
 
 // k shortest walks (k_shortest_walks.hpp:177-290, is_dag = true) over a batch of DAGs; host pointers in, library-allocated out
-namespace {
-struct KswGpu {
-    hipStream_t stream;
-    hipError_t e = hipSuccess;
-    std::vector<void *> blocks;
-    ~KswGpu() { for (void *p : blocks) hipFree(p); }
-    void *alloc(size_t n) {
-        void *p = nullptr;
-        if (e != hipSuccess) return nullptr;
-        if ((e = hipMalloc(&p, n)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        blocks.push_back(p);
-        return p;
-    }
-    size_t mark() const { return blocks.size(); }
-    void release(size_t m) { while (blocks.size() > m) { hipFree(blocks.back()); blocks.pop_back(); } }
-    bool h2d(void *d, const void *h, size_t n) { return e == hipSuccess && (e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)) == hipSuccess; }
-    bool d2h(void *h, const void *d, size_t n) {
-        if (e == hipSuccess) e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream);
-        return sync();
-    }
-    bool sync() { return e == hipSuccess && (e = hipStreamSynchronize(stream)) == hipSuccess; }
-    bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
-        if (e != hipSuccess) return false;
-        if (g1 <= g0) return true;
-        const dim3 grid((unsigned)(g1 - g0)), blk(64);
-        switch (kid) {
-            case KSW_K_TREE: hipLaunchKernelGGL(aasm_ksw_tree, grid, blk, 0, stream, g0, a); break;
-            case KSW_K_HEAP: hipLaunchKernelGGL(aasm_ksw_heap, grid, blk, 0, stream, g0, a); break;
-            case KSW_K_ENUM: hipLaunchKernelGGL(aasm_ksw_enum, grid, blk, 0, stream, g0, a); break;
-            case KSW_K_COUNT: hipLaunchKernelGGL(aasm_ksw_count, grid, blk, 0, stream, g0, a); break;
-            default: hipLaunchKernelGGL(aasm_ksw_fill, grid, blk, 0, stream, g0, a); break;
-        }
-        return (e = hipGetLastError()) == hipSuccess;
-    }
-    int err() {
-        if (e == hipSuccess) { set_last_error("aasm_k_shortest_walks: out of host memory"); return AASM_E_NOMEM; }
-        set_last_error(hip_err("aasm_k_shortest_walks", e));
-        return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP;
-    }
-};
-}  // namespace
-
 int aasm_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
                           const int32_t *source, const int32_t *sink, int64_t k, int flags, int device, aasm_ksw_out *out) {
     const char *why = "";
-    const int rc0 = ksw_check_args(n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, &why);
-    if (rc0 != AASM_OK) { set_last_error(std::string("aasm_k_shortest_walks: ") + why); return rc0; }
-    int rc = ctx_init(device);
-    if (rc != AASM_OK) return rc;
-    hipSetDevice(device);
-    KswGpu be;
-    be.stream = g_ctx[device].stream;
-    return ksw_run(be, n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, (int64_t)4 << 30);
+    const int rc = ksw_check_args(n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, &why);
+    return graph_entry("aasm_k_shortest_walks", rc, why, device, [&](GraphGpu &be) {
+        return ksw_run(be, n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, (int64_t)4 << 30);
+    });
 }
 
 void aasm_ksw_free(aasm_ksw_out *out) { ksw_free_out(out); }

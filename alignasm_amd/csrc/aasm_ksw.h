@@ -1,7 +1,7 @@
 // aasm_ksw.h -- batched k shortest walks on caller-supplied DAGs (row ★K): the solver's k_shortest_walks() with
 // is_dag = true (k_shortest_walks.hpp:177-249) and kth_shortest_walk_recover() (:252-290), one workgroup per graph.
 //
-// Kernel bodies (KCtx style, so tests/host_emul_ksw compiles them for one lane on the host):
+// Kernel bodies (KCtx style, so tests/host_emul_graphs compiles them for one lane on the host):
 //   kb_ksw_tree   reversed CSR in the reference's list order (:180-183), Kahn order of the reversed graph (:132-156) fused
 //                 with the DAG relaxation to the sink (:160-175; strict `>` in CALC_SUM order), the best EDGE beside best,
 //                 cycle detection, the children of every tree vertex in ascending u (:191-194), the BFS from the sink, the
@@ -13,8 +13,7 @@
 // The sequential stages run on lane 0 of the graph's wave (the reference's order is sequential by definition); the
 // recovery runs one walk per lane.  Every loop is bounded by the graph's size or by a capacity checked before a write.
 #pragma once
-#include "aasm_dev.h"
-#include "../../include/alignasm_amd.h"
+#include "aasm_sssp.h"
 
 namespace aasm {
 
@@ -58,10 +57,6 @@ struct KswArgs {
     int64_t *woff, *wedges;
 };
 
-AASM_DEV Dist ksw_w(const int64_t *w5, int64_t e) {
-    Dist r; r.qry = w5[5 * e]; r.ref = w5[5 * e + 1]; r.anom = (int32_t)w5[5 * e + 2]; r.qnz = (int32_t)w5[5 * e + 3];
-    r.qtot = (int32_t)w5[5 * e + 4]; r.pad = 0; return r;
-}
 AASM_DEV bool ksw_is_ident(const Dist &c) { return dist_eq(c, dist_zero()); }
 
 // ---- stage 1-2: reversed CSR, Kahn order + DAG relaxation, tree children, BFS, bounds ------------------------------------
@@ -101,7 +96,7 @@ AASM_DEV void kb_ksw_tree(const KCtx &k, const KswArgs &a) {
         for (int64_t r = roff[v]; r < r1; r++) {
             const int32_t e = rev[r], to = etail[e];
             if (live) {
-                const Dist cand = dist_add(d[v], ksw_w(a.w5, eb + e));
+                const Dist cand = dist_add(d[v], edge_w5(a.w5, eb + e));
                 if (dist_lt<CALC_SUM_MODE>(cand, d[to])) { d[to] = cand; best[to] = v; bedge[to] = e; }   // d[to] > d[v] + w
                 const int64_t c = cnt[to] + cnt[v];
                 cnt[to] = c < a.k ? c : a.k;                          // walks to the sink, saturated at k
@@ -132,7 +127,7 @@ AASM_DEV void kb_ksw_tree(const KCtx &k, const KswArgs &a) {
         for (int64_t e = rp[u] - eb; e < rp[u + 1] - eb; e++) {
             const int32_t v = col[e];
             if (dist_is_max(d[v])) continue;
-            if (!seen_p && v == best[u] && ksw_is_ident(dist_sub(dist_add(ksw_w(a.w5, eb + e), d[v]), d[u]))) { seen_p = true; continue; }
+            if (!seen_p && v == best[u] && ksw_is_ident(dist_sub(dist_add(edge_w5(a.w5, eb + e), d[v]), d[u]))) { seen_p = true; continue; }
             ins++;
         }
         for (int32_t j = koff[u]; j < deg[u]; j++) { const int32_t p = kids[j]; depth[p] = depth[u] + 1; bfs[bt++] = p; }
@@ -188,7 +183,7 @@ AASM_DEV void kb_ksw_heap(const KCtx &k, const KswArgs &a) {
         for (int64_t e = rp[u] - eb; e < rp[u + 1] - eb && !over; e++) {
             const int32_t v = col[e];
             if (dist_is_max(d[v])) continue;
-            const Dist c = dist_sub(dist_add(ksw_w(a.w5, eb + e), d[v]), d[u]);
+            const Dist c = dist_sub(dist_add(edge_w5(a.w5, eb + e), d[v]), d[u]);
             if (!seen_p && v == best[u] && ksw_is_ident(c)) { seen_p = true; continue; }   // we can only skip once
             hu = ksw_insert(A, n, cap, hu, c, (int32_t)e, over);
         }
@@ -333,39 +328,21 @@ AASM_DEV void kb_ksw_fill(const KCtx &k, const KswArgs &a) {
 }
 
 // ---- host side: argument checks and the driver, shared by the product (aasm_gpu.hip) and the host emulation -----------
-}  // namespace aasm
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-namespace aasm {
-// Returns AASM_OK or the code, with a message in *why.  The same checks and weight domain as aasm_sssp_dijkstra.
+// Returns AASM_OK or the code, with a message in why: the graph-batch layout and the w5 weight domain of aasm_sssp.h, and k-walks' own
+// bounds.
 static inline int ksw_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
                                  const int32_t *source, const int32_t *sink, int64_t k, int flags, const aasm_ksw_out *out, const char **why) {
-    *why = "";
-    if (n_graphs <= 0 || !g_voff || !rowptr || !col || !w5 || !source || !sink || !out) { *why = "empty batch or NULL pointer"; return AASM_E_INVAL; }
-    if (k < 1 || k > AASM_KSW_MAX_K) { *why = "k outside 1 .. 2^24"; return AASM_E_INVAL; }
-    if (flags & ~(AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_HOOK_ARENA)) { *why = "unknown flag"; return AASM_E_INVAL; }
-    if (g_voff[0] != 0 || rowptr[0] != 0) { *why = "offsets do not start at 0"; return AASM_E_INVAL; }
+    int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, source, {w5, sink, out}, why);
+    if (rc != AASM_OK) return rc;
+    if (k < 1 || k > AASM_KSW_MAX_K) return check_fail(why, AASM_E_INVAL, "k outside 1 .. 2^24");
+    if (flags & ~(AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_HOOK_ARENA)) return check_fail(why, AASM_E_INVAL, "unknown flag");
     for (int64_t g = 0; g < n_graphs; g++) {
         const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
-        if (v1 <= v0) { *why = "a graph without vertices (g_voff not increasing)"; return AASM_E_INVAL; }
-        if (v1 - v0 > AASM_KSW_MAX_V) { *why = "a graph of more than 2^20 vertices"; return AASM_E_OVERFLOW; }
-        for (int64_t v = v0; v < v1; v++) if (rowptr[v + 1] < rowptr[v]) { *why = "rowptr decreasing"; return AASM_E_INVAL; }
-        if (rowptr[v1] - rowptr[v0] > INT32_MAX) { *why = "a graph of 2^31 edges or more"; return AASM_E_OVERFLOW; }
-        if (source[g] < 0 || source[g] >= v1 - v0 || sink[g] < 0 || sink[g] >= v1 - v0) { *why = "source or sink outside its graph"; return AASM_E_INVAL; }
-        for (int64_t e = rowptr[v0]; e < rowptr[v1]; e++)
-            if (col[e] < 0 || col[e] >= v1 - v0) { *why = "an edge head outside its graph"; return AASM_E_INVAL; }
+        if (sink[g] < 0 || sink[g] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": sink outside it");
+        if (v1 - v0 > AASM_KSW_MAX_V) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(g) + ": more than 2^20 vertices");
+        if (rowptr[v1] - rowptr[v0] > INT32_MAX) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(g) + ": 2^31 edges or more");
     }
-    const int64_t ET = rowptr[g_voff[n_graphs]];
-    const int64_t lim = (int64_t)1 << 39;
-    for (int64_t e = 0; e < ET; e++) {
-        const int64_t *w = w5 + 5 * e;
-        if (w[0] < -lim || w[0] >= lim || w[1] < -lim || w[1] >= lim || w[0] + w[1] < 0 || w[2] < 0 || w[2] > 2 || w[3] < 0 || w[3] > 1 || w[4] < 0 || w[4] > 1) {
-            *why = "a weight outside the supported range (score sum >= 0, |scores| < 2^39, anom 0..2, mapq counts 0..1)";
-            return AASM_E_OVERFLOW;
-        }
-    }
-    return AASM_OK;
+    return check_w5(w5, rowptr[g_voff[n_graphs]], why);
 }
 
 static inline void ksw_free_out(aasm_ksw_out *o) {
@@ -388,37 +365,26 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
     KswArgs a;
     memset(&a, 0, sizeof(a));
     a.n_graphs = G; a.k = k;
-    bool ok = true;
-    auto dev = [&](size_t bytes) -> void * {
-        if (!ok) return nullptr;
-        void *p = be.alloc(bytes ? bytes : 16);
-        if (!p) ok = false;
-        return p;
-    };
-    auto up = [&](const void *h, size_t bytes) -> void * {
-        void *p = dev(bytes);
-        if (ok && bytes && !be.h2d(p, h, bytes)) ok = false;
-        return p;
-    };
-    a.voff = (const int64_t *)up(g_voff, (size_t)(G + 1) * 8);
-    a.rowptr = (const int64_t *)up(rowptr, (size_t)(VT + 1) * 8);
-    a.col = (const int32_t *)up(col, (size_t)ET * 4);
-    a.w5 = (const int64_t *)up(w5, (size_t)ET * 40);
-    a.src = (const int32_t *)up(source, (size_t)G * 4);
-    a.sink = (const int32_t *)up(sink, (size_t)G * 4);
+    DevMem<BE> m{be};
+    a.voff = (const int64_t *)m.up(g_voff, (size_t)(G + 1) * 8);
+    a.rowptr = (const int64_t *)m.up(rowptr, (size_t)(VT + 1) * 8);
+    a.col = (const int32_t *)m.up(col, (size_t)ET * 4);
+    a.w5 = (const int64_t *)m.up(w5, (size_t)ET * 40);
+    a.src = (const int32_t *)m.up(source, (size_t)G * 4);
+    a.sink = (const int32_t *)m.up(sink, (size_t)G * 4);
     int32_t **v32[] = {&a.roff, &a.deg, &a.order, &a.best, &a.bedge, &a.koff, &a.kids, &a.bfs, &a.depth, &a.hroot};
-    for (int32_t **p : v32) *p = (int32_t *)dev((size_t)VT * 4);
-    a.d = (Dist *)dev((size_t)VT * sizeof(Dist));
-    a.cnt = (int64_t *)dev((size_t)VT * 8);
-    a.rev = (int32_t *)dev((size_t)ET * 4);
-    a.etail = (int32_t *)dev((size_t)ET * 4);
-    a.status = (int32_t *)dev((size_t)G * 4);
+    for (int32_t **p : v32) *p = (int32_t *)m.alloc((size_t)VT * 4);
+    a.d = (Dist *)m.alloc((size_t)VT * sizeof(Dist));
+    a.cnt = (int64_t *)m.alloc((size_t)VT * 8);
+    a.rev = (int32_t *)m.alloc((size_t)ET * 4);
+    a.etail = (int32_t *)m.alloc((size_t)ET * 4);
+    a.status = (int32_t *)m.alloc((size_t)G * 4);
     int64_t **g64[] = {&a.nbfs, &a.ins, &a.walks, &a.hcount, &a.nfound, &a.wtot};
-    for (int64_t **p : g64) *p = (int64_t *)dev((size_t)G * 8);
-    int64_t *d_aoff = (int64_t *)dev((size_t)G * 8), *d_acap = (int64_t *)dev((size_t)G * 8), *d_qoff = (int64_t *)dev((size_t)G * 8);
-    int64_t *d_qcap = (int64_t *)dev((size_t)G * 8), *d_rofs = (int64_t *)dev((size_t)G * 8), *d_wbase = (int64_t *)dev((size_t)G * 8);
+    for (int64_t **p : g64) *p = (int64_t *)m.alloc((size_t)G * 8);
+    int64_t *d_aoff = (int64_t *)m.alloc((size_t)G * 8), *d_acap = (int64_t *)m.alloc((size_t)G * 8), *d_qoff = (int64_t *)m.alloc((size_t)G * 8);
+    int64_t *d_qcap = (int64_t *)m.alloc((size_t)G * 8), *d_rofs = (int64_t *)m.alloc((size_t)G * 8), *d_wbase = (int64_t *)m.alloc((size_t)G * 8);
     a.aoff = d_aoff; a.acap = d_acap; a.qoff = d_qoff; a.qcap = d_qcap; a.rofs = d_rofs; a.wbase = d_wbase;
-    if (!ok) return be.err();
+    if (!m.ok) return be.err();
     if (!be.launch_from(KSW_K_TREE, 0, G, a)) return be.err();
     std::vector<int32_t> status((size_t)G);
     std::vector<int64_t> ins((size_t)G), walks((size_t)G);
@@ -463,12 +429,12 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
         for (int64_t g = g0; g < g1; g++) { cap_c[g] = acap[g]; qcap_c[g] = qcap[g]; }
         const size_t mark = be.mark();
         KswArgs c = a;
-        c.arena = (KswNode *)dev((size_t)na * sizeof(KswNode));
-        c.q = (KswQE *)dev((size_t)nq * sizeof(KswQE));
-        c.qnode = (int32_t *)dev((size_t)nq * 4); c.qprev = (int32_t *)dev((size_t)nq * 4);
-        c.rdist = (Dist *)dev((size_t)nr * sizeof(Dist)); c.rlast = (int32_t *)dev((size_t)nr * 4);
-        c.woff = (int64_t *)dev((size_t)nr * 8);
-        if (!ok) return fail(be.err());
+        c.arena = (KswNode *)m.alloc((size_t)na * sizeof(KswNode));
+        c.q = (KswQE *)m.alloc((size_t)nq * sizeof(KswQE));
+        c.qnode = (int32_t *)m.alloc((size_t)nq * 4); c.qprev = (int32_t *)m.alloc((size_t)nq * 4);
+        c.rdist = (Dist *)m.alloc((size_t)nr * sizeof(Dist)); c.rlast = (int32_t *)m.alloc((size_t)nr * 4);
+        c.woff = (int64_t *)m.alloc((size_t)nr * 8);
+        if (!m.ok) return fail(be.err());
         if (!be.h2d(d_aoff, aoff.data(), (size_t)G * 8) || !be.h2d(d_acap, cap_c.data(), (size_t)G * 8) || !be.h2d(d_qoff, qoff.data(), (size_t)G * 8) ||
             !be.h2d(d_qcap, qcap_c.data(), (size_t)G * 8) || !be.h2d(d_rofs, rofs.data(), (size_t)G * 8)) return fail(be.err());
         KswArgs cc = c;
@@ -482,11 +448,7 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
         for (int64_t g = g0; g < g1; g++) {
             const int64_t j = g - g0;
             out->n_found[g] = nfound[j]; out->heap_nodes[g] = hcount[j]; out->status[g] = st[j];
-            for (int64_t i = 0; i < nfound[j]; i++) {
-                const Dist &x = rd[(size_t)(rofs[g] + i)];
-                int64_t *o = out->dist5 + (g * k + i) * 5;
-                o[0] = x.qry; o[1] = x.ref; o[2] = x.anom; o[3] = x.qnz; o[4] = x.qtot;
-            }
+            for (int64_t i = 0; i < nfound[j]; i++) put_d5(out->dist5 + (g * k + i) * 5, rd[(size_t)(rofs[g] + i)]);
         }
         if (want_walks) {
             if (!be.launch_from(KSW_K_COUNT, g0, g1, cc)) return fail(be.err());
@@ -494,8 +456,8 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
             if (!be.sync() || !be.d2h(wtot.data(), a.wtot + g0, (size_t)ng * 8)) return fail(be.err());
             int64_t nw = 0;
             for (int64_t g = g0; g < g1; g++) { wbase[g] = nw; nw += wtot[g - g0]; }
-            cc.wedges = (int64_t *)dev((size_t)nw * 8);
-            if (!ok) return fail(be.err());
+            cc.wedges = (int64_t *)m.alloc((size_t)nw * 8);
+            if (!m.ok) return fail(be.err());
             if (!be.h2d(d_wbase, wbase.data(), (size_t)G * 8) || !be.launch_from(KSW_K_FILL, g0, g1, cc)) return fail(be.err());
             std::vector<int64_t> wo((size_t)nr);
             wedges.resize((size_t)(wdone + nw));
@@ -537,10 +499,7 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
     if (want_tree) {
         std::vector<Dist> hd((size_t)VT);
         if (!be.d2h(hd.data(), a.d, (size_t)VT * sizeof(Dist)) || !be.d2h(out->best, a.best, (size_t)VT * 4)) return fail(be.err());
-        for (int64_t v = 0; v < VT; v++) {
-            int64_t *o = out->d5 + 5 * v;
-            o[0] = hd[(size_t)v].qry; o[1] = hd[(size_t)v].ref; o[2] = hd[(size_t)v].anom; o[3] = hd[(size_t)v].qnz; o[4] = hd[(size_t)v].qtot;
-        }
+        for (int64_t v = 0; v < VT; v++) put_d5(out->d5 + 5 * v, hd[(size_t)v]);
     }
     return AASM_OK;
 }

@@ -1,0 +1,389 @@
+// aasm_sssp.h -- single-source shortest paths over a batch of caller graphs, and the checks of the layout that aasm_sssp_dijkstra,
+// aasm_sssp_dial and aasm_k_shortest_walks share (include/alignasm_amd.h), run on the host before a device is touched.
+// Kernel bodies in KCtx style, so tests/host_emul_graphs compiles them for one lane on the host: kb_sssp_dijkstra, the solver's
+// dijkstra() (row ★J), and kb_sssp_dial, Dial's bucketed BFS (row K5); host drivers dijkstra_run / dial_run as ksw_run (aasm_ksw.h).
+#pragma once
+#include "aasm_dev.h"
+#include "../../include/alignasm_amd.h"
+
+namespace aasm {
+
+struct DjEnt { Dist d; int32_t v, p0, p1, p2; };
+#define DIAL_WIN 256
+#define DIAL_MAXB 8
+struct DialLds { int32_t ring[DIAL_MAXB][DIAL_WIN]; };
+
+struct SsspArgs {
+    int64_t n_graphs;
+    const int64_t *voff, *rowptr;                       // caller layout (global vertex / edge ids)
+    const int32_t *col, *src;
+    const int64_t *w5, *hoff; Dist *d; int32_t *prv; DjEnt *heap;            // dijkstra: graph g's heap is [hoff[g], hoff[g + 1])
+    const int32_t *cost; int32_t nb; int64_t *dist, *pre; int32_t *spill;    // dial: nb = lim + 1 stacks in graph g's spill,
+    const int64_t *soff;                                                     //       [soff[g], soff[g + 1])
+};
+
+AASM_DEV Dist edge_w5(const int64_t *w5, int64_t e) {
+    Dist r; r.qry = w5[5 * e]; r.ref = w5[5 * e + 1]; r.anom = (int32_t)w5[5 * e + 2]; r.qnz = (int32_t)w5[5 * e + 3];
+    r.qtot = (int32_t)w5[5 * e + 4]; r.pad = 0; return r;
+}
+
+// ---- generic SSSP: the solver's dijkstra() (k_shortest_walks.hpp:69-87) ------------------------------
+// The reference's CLI never reaches it (is_dag = true, paf_data.cpp:728: the shortest-path tree is the DAG
+// relaxation, K6), but the solver class offers it for graphs with cycles and BASELINE.json's north_star names it.
+// One wave per graph, wave-uniform control: a binary min-heap of (Distance, vertex) in global memory with the
+// reference's order (std::greater on std::pair: PafDistance operator< in CALC_SUM mode, then the vertex), lazy
+// deletion by `dv != d[v]` (operator==), strict `d[to] > dv + w` relaxation of the popped vertex's list in list
+// order (sequential: a list may name a vertex twice).  Results equal the reference's d[] and prev[] exactly.
+AASM_DEV bool dj_ent_less(const DjEnt &a, const DjEnt &b) {         // std::pair<Distance, int64_t> operator<
+    if (dist_lt<CALC_SUM_MODE>(a.d, b.d)) return true;
+    if (dist_lt<CALC_SUM_MODE>(b.d, a.d)) return false;
+    return a.v < b.v;
+}
+AASM_DEV void kb_sssp_dijkstra(const KCtx &k, const SsspArgs &a) {
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs) return;
+    const int lane = k.lane;
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb;
+    Dist *dg = a.d + vb;
+    int32_t *pg = a.prv + vb;
+    DjEnt *H = a.heap + a.hoff[g];
+    for (int64_t v = lane; v < V; v += AASM_WAVE) { dg[v] = dist_max(); pg[v] = -1; }
+    wave_fence();
+    int64_t n = 0;
+    const int64_t cap = a.hoff[g + 1] - a.hoff[g];
+    bool over = false;
+    auto push = [&](const Dist &dd, int32_t v) {
+        DjEnt x; x.d = dd; x.v = v; x.p0 = x.p1 = x.p2 = 0;
+        if (n >= cap) { over = true; return; }                       // more relaxations than edges: a cycle keeps improving the order (the reference would not return)
+        int64_t i = n++;
+        while (i > 0) {
+            const int64_t p = (i - 1) >> 1;
+            const DjEnt pe = H[p];
+            if (!uni(dj_ent_less(x, pe))) break;
+            if (lane == 0) H[i] = pe;
+            wave_fence();
+            i = p;
+        }
+        if (lane == 0) H[i] = x;
+        wave_fence();
+    };
+    const int32_t s = a.src[g];
+    if (lane == 0) dg[s] = dist_zero();                              // IDENTITY_DISTANCE (:74)
+    wave_fence();
+    push(dist_zero(), s);
+    while (n > 0 && !over) {
+        const DjEnt top = H[0];
+        const DjEnt x = H[--n];
+        if (n > 0) {                                                 // pop: the last entry sinks from the root
+            int64_t i = 0;
+            while (true) {
+                int64_t c = 2 * i + 1;
+                if (c >= n) break;
+                DjEnt ce = H[c];
+                if (c + 1 < n) { const DjEnt ce2 = H[c + 1]; if (uni(dj_ent_less(ce2, ce))) { ce = ce2; c++; } }
+                if (!uni(dj_ent_less(ce, x))) break;
+                if (lane == 0) H[i] = ce;
+                wave_fence();
+                i = c;
+            }
+            if (lane == 0) H[i] = x;
+            wave_fence();
+        }
+        const int32_t v = uni(top.v);
+        const Dist dv = uni(top.d);
+        if (!uni(dist_eq(dv, dg[v]))) continue;                      // :79 (operator!=)
+        for (int64_t e = a.rowptr[vb + v]; e < a.rowptr[vb + v + 1]; e++) {
+            const int32_t to = uni(a.col[e]);
+            const Dist cand = uni(dist_add(dv, edge_w5(a.w5, e)));
+            if (uni(dist_lt<CALC_SUM_MODE>(cand, dg[to]))) {         // d_[to] > dv + w (:81)
+                if (lane == 0) { dg[to] = cand; pg[to] = v; }
+                wave_fence();
+                push(cand, to);
+            }
+        }
+    }
+    if (over && lane == 0) pg[s] = -2;                               // reported by the host driver
+}
+
+// ---- Dial's bucketed BFS (k_weighted_bfs.hpp:16-37), one wave per graph -------------------------------------------------
+// The reference keeps lim + 1 circular buckets, each a LIFO stack, and walks d = 0, 1, ...: pop the top of bucket d mod (lim + 1),
+// skip it when its distance is stale, relax its out-edges in list order; a successful relaxation (dist[nxt] == -1 or > d + cost)
+// sets dist / pre and pushes nxt onto bucket (d + cost) mod (lim + 1).  dist is order-independent, pre is not: it names the FIRST
+// vertex, in the reference's pop order, that reached the final distance - so the pops stay sequential and the relaxations of ONE
+// popped row run on the lanes:
+//  * buckets staged in LDS (k.lds, a DialLds): every stack's top DIAL_WIN entries live in an LDS ring (ring slot = stack position
+//    mod DIAL_WIN); a full ring spills its lower half to the stack's slice of global memory in one coalesced store, an empty one
+//    refills from it;
+//  * a row is relaxed a wave of edges at a time; the lanes that succeed are compacted PER BUCKET by ballot + prefix count, so a
+//    chunk's pushes land on every stack in list order (what the LIFO pops then reverse, as in the reference);
+//  * a chunk that names a head twice (parallel edges) is relaxed edge by edge - the second edge must see the first one's result.
+//    With one lane (the host emulation) a chunk is one edge, the reference's own order.
+// The solver drives it with lim = 2 on the anomaly weights and keeps one scalar (paf_data.cpp:704-715), which the pipeline folds
+// into its forward sweep; this entry is the algorithm itself, for any digraph (cycles allowed) and weights 0 .. lim <= 7.
+AASM_DEV void kb_sssp_dial(const KCtx &k, const SsspArgs &a) {
+    AASM_LDS_VIEW DialLds &L = *(AASM_LDS_VIEW DialLds *)k.lds;
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs) return;
+    const int lane = k.lane;
+    const int32_t nb = a.nb;
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb;
+    int64_t *dg = a.dist + vb, *pg = a.pre + vb;
+    const int64_t cap = (a.soff[g + 1] - a.soff[g]) / nb;            // per bucket
+    int32_t *sp = a.spill + a.soff[g];
+    for (int64_t v = lane; v < V; v += AASM_WAVE) { dg[v] = -1; pg[v] = -1; }
+    wave_fence();
+    int32_t base[DIAL_MAXB], cnt[DIAL_MAXB];                        // stack b = global [0, base) + ring [base, base + cnt)
+    AASM_UNROLL
+    for (int b = 0; b < DIAL_MAXB; b++) { base[b] = 0; cnt[b] = 0; }
+    bool over = false;
+    // room for m more entries on stack b (m <= AASM_WAVE): spill the lower half of a ring that would overflow
+    auto make_room = [&](int b, int32_t m) {
+        AASM_UNROLL
+        for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b && cnt[bb] + m > DIAL_WIN) {
+            const int32_t n = DIAL_WIN / 2;
+            if ((int64_t)base[bb] + n > cap) { over = true; return; }
+            for (int32_t t = lane; t < n; t += AASM_WAVE) sp[(int64_t)bb * cap + base[bb] + t] = L.ring[bb][(base[bb] + t) & (DIAL_WIN - 1)];
+            base[bb] += n; cnt[bb] -= n;
+        }
+    };
+    auto push_lanes = [&](int b, bool mine, int32_t v) {             // the lanes with `mine` push v onto stack b, in lane order
+        const uint64_t m = wave_ballot(mine);
+        if (!m) return;
+        make_room(b, popc64(m));
+        if (over) return;
+        AASM_UNROLL
+        for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) {
+            if (mine) L.ring[bb][(base[bb] + cnt[bb] + popc64(m & lanemask_lt(lane))) & (DIAL_WIN - 1)] = v;
+            cnt[bb] += popc64(m);
+        }
+        wave_fence();
+    };
+    const int32_t s0 = a.src[g];
+    if (lane == 0) dg[s0] = 0;
+    push_lanes(0, lane == 0, s0);
+    int64_t maxd = 0;
+    for (int64_t d = 0; d <= maxd && !over; d++) {
+        const int b = (int)(d % nb);
+        while (!over) {
+            int32_t c_b = 0, b_b = 0;
+            AASM_UNROLL
+            for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) { c_b = cnt[bb]; b_b = base[bb]; }
+            if (c_b == 0) {
+                if (b_b == 0) break;                                 // the bucket is empty
+                const int32_t n = b_b < DIAL_WIN / 2 ? b_b : DIAL_WIN / 2;   // refill the ring from the stack's global part
+                for (int32_t t = lane; t < n; t += AASM_WAVE) L.ring[b][(b_b - n + t) & (DIAL_WIN - 1)] = sp[(int64_t)b * cap + b_b - n + t];
+                wave_fence();
+                AASM_UNROLL
+                for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) { base[bb] -= n; cnt[bb] += n; }
+                continue;
+            }
+            const int32_t cur = uni(L.ring[b][(b_b + c_b - 1) & (DIAL_WIN - 1)]);   // q.back(); q.pop_back()
+            AASM_UNROLL
+            for (int bb = 0; bb < DIAL_MAXB; bb++) if (bb == b) cnt[bb]--;
+            const int64_t dc = dg[cur];
+            if (uni((int32_t)(dc != d))) continue;                   // stale (:24)
+            const int64_t r0 = a.rowptr[vb + cur], r1 = a.rowptr[vb + cur + 1];
+            for (int64_t e0 = r0; e0 < r1 && !over; e0 += AASM_WAVE) {
+                const int64_t e = e0 + lane;
+                const bool act = e < r1;
+                const int32_t nxt = act ? a.col[e] : -1 - lane;
+                const int32_t cs = act ? a.cost[e] : 0;
+                // a head named twice in this chunk?  (lane i looks at the lanes below it)
+                bool dup = false;
+                const int32_t nlan = (int32_t)((r1 - e0 < AASM_WAVE) ? (r1 - e0) : AASM_WAVE);
+                for (int32_t j = 0; j + 1 < nlan; j++) dup |= (lane > j) && (wave_readlane(nxt, j) == nxt);
+                if (wave_ballot(dup)) {                              // edge by edge, as the reference (:25-32)
+                    for (int32_t j = 0; j < nlan && !over; j++) {
+                        const int32_t nj = wave_readlane(nxt, j), cj = wave_readlane(cs, j);
+                        const int64_t nd = d + cj, dn = dg[nj];
+                        const bool ok = uni((int32_t)(dn == -1 || dn > nd)) != 0;
+                        if (!ok) continue;
+                        if (lane == 0) { dg[nj] = nd; pg[nj] = cur; }
+                        wave_fence();
+                        push_lanes((int)(nd % nb), lane == 0, nj);
+                        if (nd > maxd) maxd = nd;
+                    }
+                    continue;
+                }
+                const int64_t nd = d + cs;
+                bool ok = false;
+                if (act) { const int64_t dn = dg[nxt]; ok = dn == -1 || dn > nd; if (ok) { dg[nxt] = nd; pg[nxt] = cur; } }
+                wave_fence();
+                const int bk = (int)(nd % nb);
+                for (int bb = 0; bb < nb && !over; bb++) push_lanes(bb, ok && bk == bb, nxt);
+                int64_t mx = ok ? nd : 0;
+                for (int o = AASM_WAVE / 2; o >= 1; o >>= 1) { const int64_t y = wave_shfl_xor(mx, o); mx = y > mx ? y : mx; }
+                if (mx > maxd) maxd = mx;
+            }
+        }
+    }
+    if (over && lane == 0) pg[s0] = -2;                              // reported by the host driver
+}
+
+// ---- host side: argument checks and the drivers, shared by the product (aasm_gpu.hip) and the host emulation -----------
+}  // namespace aasm
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <vector>
+namespace aasm {
+
+// A failed check or driver run: code rc, and *why = msg (kept until this thread's next failure).
+static inline int check_fail(const char **why, int rc, const std::string &msg) {
+    static thread_local std::string last;
+    last = msg;
+    *why = last.c_str();
+    return rc;
+}
+
+// The common layout of a graph batch.  Returns AASM_OK, or AASM_E_INVAL with a message in *why.  The offsets are checked first
+// (g_voff from 0 and strictly increasing, then rowptr from 0 and non-decreasing), and only then is anything read through them.
+// more: the entry's other pointers, which must not be NULL either.
+static inline int check_graph_batch(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *src,
+                                    std::initializer_list<const void *> more, const char **why) {
+    bool null = !g_voff || !rowptr || !col || !src;
+    for (const void *p : more) null |= !p;
+    if (n_graphs <= 0 || null) return check_fail(why, AASM_E_INVAL, "empty batch or NULL pointer");
+    if (g_voff[0] != 0) return check_fail(why, AASM_E_INVAL, "graph offsets do not start at 0");
+    for (int64_t g = 0; g < n_graphs; g++)
+        if (g_voff[g + 1] <= g_voff[g]) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": empty, or graph offsets not increasing");
+    const int64_t VT = g_voff[n_graphs];
+    if (rowptr[0] != 0) return check_fail(why, AASM_E_INVAL, "row pointers do not start at 0");
+    for (int64_t v = 0; v < VT; v++)
+        if (rowptr[v + 1] < rowptr[v]) return check_fail(why, AASM_E_INVAL, "row pointers decrease at vertex " + std::to_string(v));
+    for (int64_t g = 0; g < n_graphs; g++) {
+        const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
+        if (src[g] < 0 || src[g] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": source outside it");
+        for (int64_t e = rowptr[v0]; e < rowptr[v1]; e++)
+            if (col[e] < 0 || col[e] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": edge head outside the graph");
+    }
+    return AASM_OK;
+}
+
+// a distance as the C-ABI's five int64 {qry, ref, anom, qnz, qtot}
+static inline void put_d5(int64_t *o, const Dist &x) { o[0] = x.qry; o[1] = x.ref; o[2] = x.anom; o[3] = x.qnz; o[4] = x.qtot; }
+
+// The w5 weight domain of dijkstra and k-walks.  AASM_OK, or AASM_E_OVERFLOW.
+static inline int check_w5(const int64_t *w5, int64_t n_edges, const char **why) {
+    const int64_t lim = (int64_t)1 << 39;
+    for (int64_t e = 0; e < n_edges; e++) {
+        const int64_t *w = w5 + 5 * e;
+        if (w[0] < -lim || w[0] >= lim || w[1] < -lim || w[1] >= lim || w[0] + w[1] < 0 || w[2] < 0 || w[2] > 2 || w[3] < 0 || w[3] > 1 || w[4] < 0 || w[4] > 1)
+            return check_fail(why, AASM_E_OVERFLOW, "edge " + std::to_string(e) + ": weight outside the supported range (score sum >= 0, |scores| < 2^39, anom 0..2, mapq counts 0..1)");
+    }
+    return AASM_OK;
+}
+
+// The entries' argument checks (shared by the product and the host emulation): AASM_OK, or the code with a message in why.
+static inline int dijkstra_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                                      const int32_t *src, const int64_t *d5, const int32_t *prev, const char **why) {
+    const int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, src, {w5, d5, prev}, why);
+    return rc != AASM_OK ? rc : check_w5(w5, rowptr[g_voff[n_graphs]], why);
+}
+static inline int dial_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
+                                  const int32_t *src, int lim, const int64_t *dist, const int64_t *pre, const char **why) {
+    const int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, src, {cost, dist, pre}, why);
+    if (rc != AASM_OK) return rc;
+    if (lim < 0 || lim + 1 > DIAL_MAXB) return check_fail(why, AASM_E_INVAL, "lim outside 0 .. 7");
+    for (int64_t e = 0; e < rowptr[g_voff[n_graphs]]; e++)
+        if (cost[e] < 0 || cost[e] > lim) return check_fail(why, AASM_E_INVAL, "edge " + std::to_string(e) + ": cost outside 0 .. lim (the reference asserts it, k_weighted_bfs.hpp:27)");
+    return AASM_OK;
+}
+
+// Device memory of one driver run through backend BE: after the first failure `ok` stays false and every later call returns
+// nullptr, so a driver allocates everything and tests once.
+template <class BE> struct DevMem {
+    BE &be;
+    bool ok = true;
+    void *alloc(size_t bytes) {
+        if (!ok) return nullptr;
+        void *p = be.alloc(bytes ? bytes : 16);
+        if (!p) ok = false;
+        return p;
+    }
+    void *up(const void *h, size_t bytes) {
+        void *p = alloc(bytes);
+        if (ok && bytes && !be.h2d(p, h, bytes)) ok = false;
+        return p;
+    }
+};
+
+enum { SSSP_K_DIJKSTRA = 0, SSSP_K_DIAL };
+
+// Backend BE: ksw_run's contract (aasm_ksw.h), with bool launch(kernel, n_graphs, SsspArgs) for the SSSP kernels (one block
+// per graph of the whole batch).  why: the message of a failure the driver itself finds.
+template <class BE>
+int dijkstra_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                 const int32_t *src, int64_t *d5, int32_t *prev, const char **why) {
+    const int64_t G = n_graphs, VT = g_voff[G], ET = rowptr[VT];
+    DevMem<BE> m{be};
+    SsspArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_graphs = G;
+    a.voff = (const int64_t *)m.up(g_voff, (size_t)(G + 1) * 8);
+    a.rowptr = (const int64_t *)m.up(rowptr, (size_t)(VT + 1) * 8);
+    a.col = (const int32_t *)m.up(col, (size_t)ET * 4);
+    a.src = (const int32_t *)m.up(src, (size_t)G * 4);
+    a.w5 = (const int64_t *)m.up(w5, (size_t)ET * 40);
+    a.d = (Dist *)m.alloc((size_t)VT * sizeof(Dist));
+    a.prv = (int32_t *)m.alloc((size_t)VT * 4);
+    if (!m.ok) return be.err();
+    std::vector<Dist> hd((size_t)VT);
+    // Heap capacity.  With a monotone order every successful relaxation pushes once (<= E + 1 entries), but CALC_SUM's third
+    // key (the mapq ratio) is not monotone under addition and the reference re-expands a vertex whenever its distance
+    // improves, so stale entries of one edge can pile up: a graph whose heap overflows is run again with 4x, 16x, 64x the room.
+    int64_t overflowed = -1;
+    for (int64_t mult = 1; mult <= 64; mult *= 4) {
+        std::vector<int64_t> ho((size_t)G + 1, 0);
+        for (int64_t g = 0; g < G; g++) ho[(size_t)g + 1] = ho[(size_t)g] + mult * (rowptr[g_voff[g + 1]] - rowptr[g_voff[g]] + 2);
+        const size_t mark = be.mark();
+        a.hoff = (const int64_t *)m.up(ho.data(), (size_t)(G + 1) * 8);
+        a.heap = (DjEnt *)m.alloc((size_t)ho[(size_t)G] * sizeof(DjEnt));
+        if (!m.ok || !be.launch(SSSP_K_DIJKSTRA, G, a) || !be.sync() || !be.d2h(hd.data(), a.d, (size_t)VT * sizeof(Dist)) ||
+            !be.d2h(prev, a.prv, (size_t)VT * 4)) return be.err();
+        be.release(mark);
+        overflowed = -1;
+        for (int64_t g = 0; g < G; g++) if (prev[g_voff[g] + src[g]] == -2) { overflowed = g; break; }
+        if (overflowed < 0) break;
+    }
+    if (overflowed >= 0) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(overflowed) + ": dijkstra heap capacity exceeded at 64 x (E + 2) entries");
+    for (int64_t v = 0; v < VT; v++) put_d5(d5 + 5 * v, hd[(size_t)v]);
+    return AASM_OK;
+}
+
+template <class BE>
+int dial_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
+             const int32_t *src, int lim, int64_t *dist, int64_t *pre, const char **why) {
+    const int64_t G = n_graphs, VT = g_voff[G], ET = rowptr[VT];
+    const int nb = lim + 1;
+    std::vector<int64_t> soff((size_t)G + 1, 0);
+    for (int64_t g = 0; g < G; g++) {
+        // a vertex is pushed once per successful relaxation: its distance falls by at least one each time and by at most lim in all
+        // after the first (a later pop has d' >= d), so <= lim + 1 pushes per vertex - and never more than one per edge, plus the source
+        const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
+        const int64_t E = rowptr[v1] - rowptr[v0], by_v = (v1 - v0) * (int64_t)nb;
+        const int64_t per = ((E + 1 < by_v ? E + 1 : by_v) + DIAL_WIN + 63) / 64 * 64;
+        soff[(size_t)g + 1] = soff[(size_t)g] + per * nb;
+    }
+    DevMem<BE> m{be};
+    SsspArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_graphs = G; a.nb = nb;
+    a.voff = (const int64_t *)m.up(g_voff, (size_t)(G + 1) * 8);
+    a.rowptr = (const int64_t *)m.up(rowptr, (size_t)(VT + 1) * 8);
+    a.col = (const int32_t *)m.up(col, (size_t)ET * 4);
+    a.cost = (const int32_t *)m.up(cost, (size_t)ET * 4);
+    a.src = (const int32_t *)m.up(src, (size_t)G * 4);
+    a.soff = (const int64_t *)m.up(soff.data(), (size_t)(G + 1) * 8);
+    a.dist = (int64_t *)m.alloc((size_t)VT * 8);
+    a.pre = (int64_t *)m.alloc((size_t)VT * 8);
+    a.spill = (int32_t *)m.alloc((size_t)soff[(size_t)G] * 4);
+    if (!m.ok || !be.launch(SSSP_K_DIAL, G, a) || !be.sync() || !be.d2h(dist, a.dist, (size_t)VT * 8) || !be.d2h(pre, a.pre, (size_t)VT * 8))
+        return be.err();
+    for (int64_t g = 0; g < G; g++)
+        if (pre[g_voff[g] + src[g]] == -2) return check_fail(why, AASM_E_INTERNAL, "graph " + std::to_string(g) + ": bucket capacity exceeded (must not happen)");
+    return AASM_OK;
+}
+
+}  // namespace aasm

@@ -1,11 +1,12 @@
-// tests/host_emul_ksw/ksw_emul.cpp -- TEST INFRASTRUCTURE ONLY.
+// tests/host_emul_graphs/graphs_emul.cpp -- TEST INFRASTRUCTURE ONLY.
 //
-// The k-shortest-walks kernel bodies (alignasm_amd/csrc/aasm_ksw.h) and the host driver that sizes and launches them
-// (ksw_run), compiled for the HOST: a workgroup runs as its one working lane (nthreads = 1), device memory is poisoned host
-// memory.  The product library never links this file; its entry aasm_k_shortest_walks() needs a HIP device.
+// The generic graph entries - dijkstra and Dial (alignasm_amd/csrc/aasm_sssp.h), k shortest walks (aasm_ksw.h) - with the
+// product's argument checks and host drivers, compiled for the HOST: a workgroup runs as its one working lane (nthreads = 1),
+// device memory and LDS are poisoned host memory.  The product library never links this file; its entries need a HIP device.
 #define AASM_HOST_EMUL 1
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../alignasm_amd/csrc/aasm_ksw.h"
@@ -13,13 +14,12 @@
 using namespace aasm;
 
 namespace {
-struct KswEmu {
+struct GraphEmu {
     std::vector<void *> blocks;
-    bool oom = false;
-    ~KswEmu() { for (void *p : blocks) free(p); }
+    ~GraphEmu() { for (void *p : blocks) free(p); }
     void *alloc(size_t n) {
         void *p = malloc(n);
-        if (!p) { oom = true; return nullptr; }
+        if (!p) return nullptr;
         memset(p, 0xA5, n);                        // poison: catches reads of never-written cells
         blocks.push_back(p);
         return p;
@@ -42,6 +42,15 @@ struct KswEmu {
         }
         return true;
     }
+    bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
+        for (int64_t b = 0; b < n_graphs; b++) {
+            std::vector<char> lds(sizeof(DialLds), (char)0xA5);     // a block's LDS, poisoned
+            KCtx k{0, 1, b, n_graphs, 0, lds.data()};
+            if (kid == SSSP_K_DIJKSTRA) kb_sssp_dijkstra(k, a);
+            else kb_sssp_dial(k, a);
+        }
+        return true;
+    }
     int err() { return AASM_E_NOMEM; }
 };
 }  // namespace
@@ -53,8 +62,28 @@ int emk_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_t 
     const char *why = "";
     const int rc = ksw_check_args(n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, &why);
     if (rc != AASM_OK) return rc;
-    KswEmu be;
+    GraphEmu be;
     return ksw_run(be, n_graphs, g_voff, rowptr, col, w5, source, sink, k, flags, out, budget > 0 ? budget : (int64_t)4 << 30);
 }
 void emk_free(aasm_ksw_out *out) { ksw_free_out(out); }
+
+// aasm_sssp_dijkstra() without a device
+int emk_sssp_dijkstra(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                      const int32_t *src, int64_t *d5, int32_t *prev) {
+    const char *why = "";
+    const int rc = dijkstra_check_args(n_graphs, g_voff, rowptr, col, w5, src, d5, prev, &why);
+    if (rc != AASM_OK) return rc;
+    GraphEmu be;
+    return dijkstra_run(be, n_graphs, g_voff, rowptr, col, w5, src, d5, prev, &why);
+}
+
+// aasm_sssp_dial() without a device
+int emk_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
+                  const int32_t *src, int lim, int64_t *dist, int64_t *pre) {
+    const char *why = "";
+    const int rc = dial_check_args(n_graphs, g_voff, rowptr, col, cost, src, lim, dist, pre, &why);
+    if (rc != AASM_OK) return rc;
+    GraphEmu be;
+    return dial_run(be, n_graphs, g_voff, rowptr, col, cost, src, lim, dist, pre, &why);
+}
 }

@@ -1,5 +1,5 @@
 """CPU tier of aasm_k_shortest_walks (row ★K): the C-ABI surface and its argument checks through the product library, and
-the kernels of alignasm_amd/csrc/aasm_ksw.h with their host driver (1-lane host emulation, tests/host_emul_ksw) against the
+the kernels of alignasm_amd/csrc/aasm_ksw.h with their host driver (1-lane host emulation, tests/host_emul_graphs) against the
 real reference's numbers in ref_algos.npz and against the oracle's restatement on random DAGs."""
 import ctypes as C
 import os
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def emk(tmp_path_factory):
-    return KC.build_emul(tmp_path_factory.mktemp("emul_ksw"))
+    return KC.build_emul(tmp_path_factory.mktemp("emul_graphs"))
 
 
 def test_header_declares_the_entry_and_abi_stays_3(T):
