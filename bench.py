@@ -24,7 +24,13 @@ aasm_partition_contigs cuts it into 8 cost-balanced pieces (a piece is what fits
 its ~59 GB workspace), rank r of N generates and solves pieces [r*8/N, (r+1)*8/N) one after the
 other, a step = every piece once; strong scaling, value = 10 000 contigs x steps / time.
 
-Extra keys of the N = 1 line: `step_with_fetch_ms` (the step plus the D2H + ragged pack of the
+A plain run does only what the headline needs: it generates and uploads the batch, runs the warm-up
+and the timed steps, writes --dump-outputs if asked, and prints the line (its roofline figures come
+from the timed steps and the committed profiles/, not from runs of their own).  Everything else it
+measures runs only with --full, after the timed steps: `step_with_fetch_ms`, `k10000`, the C3
+variants, `e2e`, `cpu_baseline` and, for N > 1, `weak`.
+
+Extra keys of the --full N = 1 line: `step_with_fetch_ms` (the step plus the D2H + ragged pack of the
 three result lists); `k10000` (the same hot path at the reference's shipped MAX_PATH_COUNT = 10000,
 paf_data.cpp:729, on the WHOLE batch, and on its first 1 000 contigs as in earlier rounds);
 `c3_heavy_tail` (SURVEY 8(d)'s variant: contig sizes log-normal(ln 600, 1) clipped to [1, 8000] and
@@ -41,8 +47,8 @@ roofline: the dominant kernel of the timed region (largest average HIP-event tim
 library's stream), its ALGORITHMIC bytes per launch (byte model: DESIGN.md "Byte model")
 and the HBM peak of /opt/skills/guides/MI355X_MICROARCH.md (8 TB/s).  `traffic` (PMC
 FETCH/WRITE bytes) is collected offline with rocprofv3 --pmc; see profiles/.
-cpu_baseline: the oracle (oracle/liboracle.so, a CPU restatement: kind "port") timed on
-this box's host cores over a bounded sample of the same workload, rank 0, N = 1 only.
+cpu_baseline (--full): the oracle (oracle/liboracle.so, a CPU restatement: kind "port") timed on
+the host's cores over a bounded sample of the same workload, rank 0, N = 1 only.
 """
 import argparse
 import glob
@@ -223,10 +229,12 @@ def main():
     ap.add_argument("--contigs", type=int, default=0, help="override contigs (exploration only)")
     ap.add_argument("--recs", type=int, default=0)
     ap.add_argument("--k", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip step_with_fetch / k10000 / weak (profiling runs)")
-    ap.add_argument("--cpu-sample", type=int, default=5000, help="contigs of the workload timed on the CPU oracle")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end command-line run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the extras (step_with_fetch, k10000, the C3 variants, e2e, weak) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip step_with_fetch / k10000 / the C3 variants / e2e / weak")
+    ap.add_argument("--cpu-sample", type=int, default=5000, help="with --full: contigs of the workload timed on the CPU oracle")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end command-line run")
     ap.add_argument("--allow-override", action="store_true", help="accept AASM_LIB_OVERRIDE (a diagnostic build of the library; the line names what it loaded)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0's contigs) as DIR/<name>.npy, float64, <= 64 MB in all")
@@ -350,7 +358,7 @@ def main():
     max_contigs = allreduce(my_contigs, dist.ReduceOp.MAX if dist else None)
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # the step plus the result fetch (D2H of the three ragged lists + host-side pack)
         barrier()
         t = time.perf_counter()
@@ -457,7 +465,7 @@ def main():
         pmc = pmc_traffic(args.workload, custom or world > 1, dom_name)
         if pmc:
             out["roofline"].update(pmc)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(paf, min(nc, paf.n_contigs), K, args.cpu_sample)
         print(json.dumps(out), flush=True)
     for d_ in dbs:
