@@ -1,8 +1,8 @@
 // aasm_dev.h -- execution context + wave64 primitives + the PafDistance arithmetic.
 //
 // Every kernel body in aasm_kernels.h is a function `kb_*(const KCtx&, const WS&)`.
-//  * Product build (hipcc, gfx950): `__global__` wrappers in aasm_gpu.hip call the body
-//    with the real thread/block ids; wave primitives are the CDNA4 64-lane ones
+//  * Product build (hipcc, gfx950): `__global__` wrappers in aasm_gpu.hip, generated from the kernel
+//    tables below, call the body with the real thread/block ids; wave primitives are the CDNA4 64-lane ones
 //    (__ballot -> 64-bit mask, __shfl over 64 lanes).
 //  * tests/host_emul (g++, AASM_HOST_EMUL): the SAME bodies run with nthreads = 1 so the
 //    arithmetic/indexing logic can be diffed against the oracle on a box without a GPU.
@@ -34,6 +34,21 @@ struct KCtx {
     char *lds;        // per-block LDS scratch (AASM_LDS_BYTES), 16-byte aligned
 };
 #define AASM_LDS_BYTES 6144   // 6 KB per single-wave block -> 26 blocks per CU by LDS
+
+// The kernel tables (AASM_PIPELINE_KERNELS, AASM_PACK_KERNELS, AASM_SSSP_KERNELS, AASM_KSW_KERNELS): one row per kernel, from which
+// the ids, the __global__ definitions and launches (aasm_gpu.hip) and the host emulation's launches are generated.  A row's lanes
+// are the threads of a block the host emulation runs: ALL_LANES (thread-per-item bodies), 1 (wave-per-item bodies: a wave is one
+// lane there) or one per wave.  A body that the emulation replaces is written AASM_EMUL_OR(host body, device body).
+#define AASM_ROW_ID(id, ...) id,
+#define AASM_ROW_BLOCK(id, sym, block, ...) block,
+constexpr int ALL_LANES = 0;
+constexpr int emul_lanes(int block, int lanes) { return lanes == ALL_LANES ? block : lanes; }
+#if defined(AASM_HOST_EMUL)
+#define AASM_EMUL_OR(host, device) host
+#else
+#define AASM_EMUL_OR(host, device) device
+#endif
+
 // typed views of k.lds: in the LDS address space on the device, so stores through them provably miss the wave's private arrays
 #if defined(AASM_HOST_EMUL)
 #define AASM_LDS_VIEW

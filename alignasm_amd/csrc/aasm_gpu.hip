@@ -1,7 +1,7 @@
 // aasm_gpu.hip -- gfx950 backend of the pipeline + the C-ABI entry points that touch the GPU.
 //
-// * one named __global__ per pipeline kernel (bodies: aasm_kernels.h), so rocprofv3
-//   --kernel-trace shows `aasm_k6_rev_sweep` etc.;
+// * one named __global__ per row of the kernel tables (aasm_pipeline.h, aasm_sssp.h, aasm_ksw.h; bodies: aasm_kernels.h), so
+//   rocprofv3 --kernel-trace shows `aasm_k6_rev_sweep` etc.;
 // * the generic graph entries (dijkstra, Dial, k shortest walks): bodies, argument checks and host drivers in aasm_sssp.h and
 //   aasm_ksw.h, run here through one backend (GraphGpu);
 // * exclusive scans (count -> offsets): ONE launch each, single pass with decoupled look-back (aasm_scan_chain);
@@ -36,85 +36,34 @@ __device__ inline int64_t xcd_bid(int64_t b, int64_t g, int on) {
     const int64_t g8 = g & ~(int64_t)7;
     return b < g8 ? (b & 7) * (g8 >> 3) + (b >> 3) : b;
 }
-#define AASM_DEF_KERNEL(name, KN, TPB)                                                        \
-    __global__ void __launch_bounds__(TPB) name(WS w) {                                       \
-        KCtx k{(int)threadIdx.x, (int)blockDim.x, xcd_bid((int64_t)blockIdx.x, (int64_t)gridDim.x, w.xcd_map), (int64_t)gridDim.x,    \
-               (int)(threadIdx.x & 63), nullptr};                                             \
-        run_kernel_body(KN, k, w);                                                            \
-    }
-// kernels whose wave keeps a working set in LDS (BYTES per 64-thread block); WAVES = waves per
-// SIMD the register budget is sized for (5: <= 96 VGPRs, 6: <= 80): residency per CU is
-// min(4 * WAVES, 160 KB / BYTES) blocks, and these kernels are latency-bound, so it is throughput
-#define AASM_DEF_KERNEL_LDS(name, KN, TPB, BYTES, WAVES)                                      \
-    __global__ void __launch_bounds__(TPB, WAVES) name(WS w) {                                    \
-        __shared__ __attribute__((aligned(16))) char smem[BYTES];                             \
-        KCtx k{(int)threadIdx.x, (int)blockDim.x, xcd_bid((int64_t)blockIdx.x, (int64_t)gridDim.x, w.xcd_map), (int64_t)gridDim.x,    \
-               (int)(threadIdx.x & 63), smem};                                                \
-        run_kernel_body(KN, k, w);                                                            \
-    }
-AASM_DEF_KERNEL(aasm_k0_cs_ranges, KN_CS_RANGES, 256)
-AASM_DEF_KERNEL_LDS(aasm_k1_sort, KN_SORT, 256, AASM_SORT_LDS_BYTES, 2)
-AASM_DEF_KERNEL(aasm_k1_sort_rank, KN_SORT_RANK, 256)
-AASM_DEF_KERNEL_LDS(aasm_k1_sort_fix, KN_SORT_FIX, 64, AASM_SORTFIX_LDS_BYTES, 1)
-AASM_DEF_KERNEL(aasm_k1_gather_parts, KN_GATHER_PARTS, 64)
-AASM_DEF_KERNEL(aasm_k2_ov_count, KN_OV_COUNT, 256)
-AASM_DEF_KERNEL(aasm_k2_ov_merge, KN_OV_MERGE, 256)
-AASM_DEF_KERNEL(aasm_k2_vcount, KN_VCOUNT, 256)
-AASM_DEF_KERNEL(aasm_k2_vfill_rec, KN_VFILL_REC, 256)
-AASM_DEF_KERNEL(aasm_k2_vfill_slot, KN_VFILL_SLOT, 256)
-AASM_DEF_KERNEL(aasm_k4_nsl, KN_NSL, 256)
-AASM_DEF_KERNEL(aasm_k4_row_count, KN_ROW_COUNT, 256)
-AASM_DEF_KERNEL(aasm_k4_row_fill, KN_ROW_FILL, 64)
-AASM_DEF_KERNEL_LDS(aasm_k46_graph, KN_GRAPH, GB_TPB, AASM_GB_LDS_BYTES, 5)   // rows + reversed CSR + sweep headers of one contig: 31.8 KB of LDS, 5 workgroups (20 waves) per CU
-AASM_DEF_KERNEL_LDS(aasm_k46_graph_l, KN_GRAPH_L, GB_TPB, AASM_GB_LDS_BYTES_T(GB_MAXV_L, GB_MAXE_L), 2)   // contigs of up to 3 584 vertices / 8 192 edges: 62 KB, two workgroups per CU
-AASM_DEF_KERNEL(aasm_k6_rev_fill, KN_REV_FILL, 256)
-AASM_DEF_KERNEL_LDS(aasm_k6_rev_fill_w, KN_REV_FILL_W, 64, AASM_REVF_LDS_BYTES, 8)
-AASM_DEF_KERNEL_LDS(aasm_k6_rev_fill_ord, KN_REV_FILL_ORD, 64, AASM_REVO_LDS_BYTES, 2)   // 25 KB of LDS per block: 6 blocks per CU, i.e. at most 2 waves per SIMD
-AASM_DEF_KERNEL_LDS(aasm_k6_rev_fill_ord_s, KN_REV_FILL_ORD_S, 64, AASM_REVO_LDS_BYTES_V(REV_ORD_MIDV), 6)   // contigs of <= 3 072 vertices: 6.7 KB
-AASM_DEF_KERNEL_LDS(aasm_k6_rev_place, KN_SORT_ROWS_REV, 64, AASM_REVP_LDS_BYTES, 4)
-AASM_DEF_KERNEL(aasm_k6_rev_hdr, KN_REV_HDR, 256)
-AASM_DEF_KERNEL_LDS(aasm_k6_rev_sweep, KN_REV_SWEEP, 64, AASM_REV_LDS_BYTES, 8)
-AASM_DEF_KERNEL_LDS(aasm_k5_fwd_sweep, KN_FWD_SWEEP, 64, AASM_FWD_LDS_BYTES, 8)
-AASM_DEF_KERNEL_LDS(aasm_k6_rev_sweep_g, KN_REV_SWEEP_G, 64, (AASM_WAVE / AASM_SWEEP_G) * AASM_REV_LDS_BYTES, 4)
-AASM_DEF_KERNEL_LDS(aasm_k5_fwd_sweep_g, KN_FWD_SWEEP_G, 64, (AASM_WAVE / AASM_SWEEP_G) * AASM_FWD_LDS_BYTES, 4)
-AASM_DEF_KERNEL(aasm_k7_children, KN_CHILDREN, 256)
-AASM_DEF_KERNEL(aasm_k7_heap_cap, KN_HEAP_CAP, 256)
-AASM_DEF_KERNEL_LDS(aasm_k7_sidetrack_w, KN_SIDETRACK_W, 64, AASM_SIDE_LDS_BYTES, 8)
-AASM_DEF_KERNEL(aasm_k7_heap_hdr, KN_HEAP_HDR, 256)
-AASM_DEF_KERNEL(aasm_k7_prep, KN_K7_PREP, 256)
-AASM_DEF_KERNEL(aasm_k9_tnx, KN_TNX, 256)
-AASM_DEF_KERNEL(aasm_k9_tnx16, KN_TNX16, 256)
-AASM_DEF_KERNEL_LDS(aasm_k9_tnx16_wg, KN_TNX16_WG, TNX_TPB, AASM_TNXWG_LDS_BYTES, 4)   // the 16-hop jump records of a small contig from its tree in LDS
-AASM_DEF_KERNEL_LDS(aasm_k7_heap, KN_HEAP, 64, AASM_HEAP_LDS_BYTES, 5)
-AASM_DEF_KERNEL_LDS(aasm_k67_chain, KN_CHAIN, 64 * CHAIN_WAVES, AASM_CHAIN_LDS_BYTES, 5)   // sweep + pre-pass + BFS order + heaps of one contig, a wave each (96 VGPRs, 19 spilled: worth it for the fifth wave slot per SIMD)
-AASM_DEF_KERNEL_LDS(aasm_k67_chain3, KN_CHAIN3, 64 * (CHAIN_WAVES - 1), AASM_CHAIN_LDS_BYTES, 5)   // ... without the order wave (the heap wave keeps its own queue): classes of more than AASM_CHAIN_ORD_MAX (1 024) contigs
-AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw, KN_HEAP_MW, 256, AASM_MW_LDS_BYTES(4), 4)
-AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw8, KN_HEAP_MW8, 512, AASM_MW_LDS_BYTES(8), 4)
-AASM_DEF_KERNEL_LDS(aasm_k7_heap_mw16, KN_HEAP_MW16, 1024, AASM_MW_LDS_BYTES(16), 4)
-AASM_DEF_KERNEL(aasm_k7_mw_rank, KN_MW_RANK, 256)
-AASM_DEF_KERNEL_LDS(aasm_k8_enum, KN_ENUM, 64, AASM_ENUM2_LDS_BYTES, 4)
-AASM_DEF_KERNEL_LDS(aasm_k8_enum_s, KN_ENUM_S, 64, AASM_ENUM2_LDS_BYTES_F(EQ_FSMALL), 5)
-AASM_DEF_KERNEL_LDS(aasm_k8_enum_heap, KN_ENUM_HEAP, 64, AASM_ENUM_LDS_BYTES, 2)
-AASM_DEF_KERNEL_LDS(aasm_k9_select, KN_SELECT, 64, AASM_SEL_LDS_BYTES, 5)
-AASM_DEF_KERNEL(aasm_k9_sel_plan, KN_SEL_PLAN, 64)
-AASM_DEF_KERNEL(aasm_k9_sel_planfill, KN_SEL_PLANFILL, 64)
-AASM_DEF_KERNEL_LDS(aasm_k9_sel_recover, KN_SEL_RECOVER, 64, AASM_SELREC_LDS_BYTES, 8)
-AASM_DEF_KERNEL(aasm_k9_sel_classify, KN_SEL_CLASSIFY, 256)
-AASM_DEF_KERNEL_LDS(aasm_k9_sel_convert, KN_SEL_CONVERT, 64, AASM_SEL_LDS_BYTES, 5)
-AASM_DEF_KERNEL(aasm_k9_sel_final, KN_SEL_FINAL, 64)
-AASM_DEF_KERNEL(aasm_k9_topo_count, KN_TOPO_COUNT, 256)
-AASM_DEF_KERNEL(aasm_k9_topo_fill, KN_TOPO_FILL, 64)
-AASM_DEF_KERNEL(aasm_k9_gather_out, KN_GATHER_OUT, 64)
-// the device-side export of a result (aasm_result_sizes / aasm_result_export; bodies kb_pack_*)
-#define AASM_DEF_PACK_KERNEL(name, KP)                                                        \
-    __global__ void __launch_bounds__(256) name(PackArgs a) {                                 \
-        KCtx k{(int)threadIdx.x, (int)blockDim.x, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr};   \
-        run_pack_body(KP, k, a);                                                              \
-    }
-AASM_DEF_PACK_KERNEL(aasm_pack_count, KP_COUNT)
-AASM_DEF_PACK_KERNEL(aasm_pack_place, KP_PLACE)
-AASM_DEF_PACK_KERNEL(aasm_pack_flat, KP_FLAT)
-AASM_DEF_PACK_KERNEL(aasm_pack_all, KP_ALL)
+// one __global__ per row of the kernel tables; k, its thread's KCtx: block `bid` of the launch's work, `lds` the block's LDS or nullptr
+#define AASM_KCTX(bid, lds) KCtx k{(int)threadIdx.x, (int)blockDim.x, bid, (int64_t)gridDim.x, (int)(threadIdx.x & 63), lds}
+#define AASM_SMEM(bytes) __shared__ __attribute__((aligned(16))) char smem[bytes]
+#define AASM_XCD_BID xcd_bid((int64_t)blockIdx.x, (int64_t)gridDim.x, w.xcd_map)
+#define K(id, sym, block, lanes, ...) \
+    __global__ void __launch_bounds__(block) sym(WS w) { AASM_KCTX(AASM_XCD_BID, nullptr); run_kernel_body(id, k, w); }
+#define KL(id, sym, block, lanes, lds, waves, ...) \
+    __global__ void __launch_bounds__(block, waves) sym(WS w) { AASM_SMEM(lds); AASM_KCTX(AASM_XCD_BID, smem); run_kernel_body(id, k, w); }
+AASM_PIPELINE_KERNELS(K, KL)
+#undef K
+#undef KL
+// the device-side export of a result (aasm_result_sizes / aasm_result_export)
+#define K(id, sym, block, lanes, ...) \
+    __global__ void __launch_bounds__(block) sym(PackArgs a) { AASM_KCTX((int64_t)blockIdx.x, nullptr); run_pack_body(id, k, a); }
+AASM_PACK_KERNELS(K)
+#undef K
+// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, K5 Dial) and aasm_ksw.h (★K: a launch covers the graphs [g0, g0 + grid))
+#define K(id, sym, block, lanes, ...) \
+    __global__ void __launch_bounds__(block) sym(SsspArgs a) { AASM_KCTX((int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
+#define KL(id, sym, block, lanes, lds, ...) \
+    __global__ void __launch_bounds__(block) sym(SsspArgs a) { AASM_SMEM(lds); AASM_KCTX((int64_t)blockIdx.x, smem); __VA_ARGS__(k, a); }
+AASM_SSSP_KERNELS(K, KL)
+#undef K
+#undef KL
+#define K(id, sym, block, lanes, ...) \
+    __global__ void __launch_bounds__(block) sym(int64_t g0, KswArgs a) { AASM_KCTX(g0 + (int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
+AASM_KSW_KERNELS(K)
+#undef K
 
 // ---- T1 truth tables on the device (test entry aasm_debug_predicates) ------------------
 // One thread per pair (a, b) of 5-int64 PafDistance tuples {qry, ref, anom, qul_nonzero, qul_total}.
@@ -145,28 +94,6 @@ __global__ void __launch_bounds__(256) aasm_t1_predicates(const int64_t *a, cons
     r |= qe_less(ea, eb) ? 32 : 0;
     out[i] = r;
 }
-
-// ---- the generic graph entries: one 64-lane workgroup per graph; bodies in aasm_sssp.h (★J dijkstra, K5 Dial) and aasm_ksw.h (★K) --
-__global__ void __launch_bounds__(64) aasm_sssp_dijkstra_kernel(SsspArgs a) {
-    KCtx k{(int)threadIdx.x, (int)blockDim.x, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr};
-    kb_sssp_dijkstra(k, a);
-}
-__global__ void __launch_bounds__(64) aasm_sssp_dial_kernel(SsspArgs a) {
-    __shared__ DialLds L;
-    KCtx k{(int)threadIdx.x, (int)blockDim.x, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), (char *)&L};
-    kb_sssp_dial(k, a);
-}
-// k-walks: the graphs [g0, g0 + grid)
-#define AASM_DEF_KSW_KERNEL(name, body)                                                                           \
-    __global__ void __launch_bounds__(64) name(int64_t g0, KswArgs a) {                                           \
-        KCtx k{(int)threadIdx.x, (int)blockDim.x, g0 + (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)(threadIdx.x & 63), nullptr}; \
-        body(k, a);                                                                                               \
-    }
-AASM_DEF_KSW_KERNEL(aasm_ksw_tree, kb_ksw_tree)
-AASM_DEF_KSW_KERNEL(aasm_ksw_heap, kb_ksw_heap)
-AASM_DEF_KSW_KERNEL(aasm_ksw_enum, kb_ksw_enum)
-AASM_DEF_KSW_KERNEL(aasm_ksw_count, kb_ksw_count)
-AASM_DEF_KSW_KERNEL(aasm_ksw_fill, kb_ksw_fill)
 
 // ---- exclusive scan: T in -> int64 out[n+1] -----------------------------------------
 // ONE launch per scan (the pipeline runs ~14 per batch, most over 7-15 M entries): tiles take their number from a
@@ -421,6 +348,15 @@ static int ctx_init(int device) {
     return AASM_OK;
 }
 
+// a pipeline kernel on stream s (the caller reads hipGetLastError)
+static void launch_kernel(int kn, int64_t nblocks, int nthreads, hipStream_t s, const WS &w) {
+    switch (kn) {
+#define K(id, sym, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, s, w); break;
+        AASM_PIPELINE_KERNELS(K, K)
+#undef K
+    }
+}
+
 struct GpuBackend {
     static constexpr bool host_emulation = false;
     DevCtx &cx;
@@ -526,35 +462,17 @@ struct GpuBackend {
     void launch(int kn, int64_t nblocks, int nthreads, const WS &w) {
         flush_zero();
         if (fail || nblocks <= 0) return;
-        dim3 g((unsigned)nblocks), b((unsigned)nthreads);
-        switch (kn) {
-#define L(KN, name) case KN: hipLaunchKernelGGL(name, g, b, 0, stream, w); break;
-            L(KN_CS_RANGES, aasm_k0_cs_ranges) L(KN_SORT, aasm_k1_sort) L(KN_SORT_RANK, aasm_k1_sort_rank) L(KN_SORT_FIX, aasm_k1_sort_fix) L(KN_GATHER_PARTS, aasm_k1_gather_parts)
-            L(KN_OV_COUNT, aasm_k2_ov_count) L(KN_OV_MERGE, aasm_k2_ov_merge) L(KN_VCOUNT, aasm_k2_vcount)
-            L(KN_VFILL_REC, aasm_k2_vfill_rec) L(KN_VFILL_SLOT, aasm_k2_vfill_slot) L(KN_NSL, aasm_k4_nsl)
-            L(KN_ROW_COUNT, aasm_k4_row_count) L(KN_ROW_FILL, aasm_k4_row_fill) L(KN_GRAPH, aasm_k46_graph) L(KN_GRAPH_L, aasm_k46_graph_l) L(KN_REV_FILL, aasm_k6_rev_fill) L(KN_REV_FILL_W, aasm_k6_rev_fill_w) L(KN_REV_FILL_ORD, aasm_k6_rev_fill_ord) L(KN_REV_FILL_ORD_S, aasm_k6_rev_fill_ord_s)
-            L(KN_SORT_ROWS_REV, aasm_k6_rev_place) L(KN_REV_HDR, aasm_k6_rev_hdr) L(KN_REV_SWEEP, aasm_k6_rev_sweep) L(KN_FWD_SWEEP, aasm_k5_fwd_sweep) L(KN_REV_SWEEP_G, aasm_k6_rev_sweep_g) L(KN_FWD_SWEEP_G, aasm_k5_fwd_sweep_g)
-            L(KN_CHILDREN, aasm_k7_children)
-            L(KN_HEAP_CAP, aasm_k7_heap_cap) L(KN_SIDETRACK_W, aasm_k7_sidetrack_w) L(KN_HEAP_HDR, aasm_k7_heap_hdr) L(KN_HEAP, aasm_k7_heap) L(KN_HEAP_MW, aasm_k7_heap_mw) L(KN_HEAP_MW8, aasm_k7_heap_mw8) L(KN_HEAP_MW16, aasm_k7_heap_mw16) L(KN_MW_RANK, aasm_k7_mw_rank) L(KN_ENUM, aasm_k8_enum) L(KN_ENUM_S, aasm_k8_enum_s) L(KN_ENUM_HEAP, aasm_k8_enum_heap) L(KN_SELECT, aasm_k9_select)
-            L(KN_GATHER_OUT, aasm_k9_gather_out) L(KN_TOPO_COUNT, aasm_k9_topo_count) L(KN_TOPO_FILL, aasm_k9_topo_fill)
-            L(KN_CHAIN, aasm_k67_chain) L(KN_CHAIN3, aasm_k67_chain3) L(KN_K7_PREP, aasm_k7_prep) L(KN_TNX, aasm_k9_tnx) L(KN_TNX16, aasm_k9_tnx16) L(KN_TNX16_WG, aasm_k9_tnx16_wg)
-            L(KN_SEL_PLAN, aasm_k9_sel_plan) L(KN_SEL_PLANFILL, aasm_k9_sel_planfill) L(KN_SEL_RECOVER, aasm_k9_sel_recover) L(KN_SEL_CLASSIFY, aasm_k9_sel_classify) L(KN_SEL_CONVERT, aasm_k9_sel_convert) L(KN_SEL_FINAL, aasm_k9_sel_final)
-#undef L
-            default: break;
-        }
+        launch_kernel(kn, nblocks, nthreads, stream, w);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) hip_fail("kernel launch", e);
     }
     void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) {
         flush_zero();
         if (fail || nblocks <= 0) return;
-        dim3 g((unsigned)nblocks), b((unsigned)nthreads);
         switch (kp) {
-            case KP_COUNT: hipLaunchKernelGGL(aasm_pack_count, g, b, 0, stream, a); break;
-            case KP_PLACE: hipLaunchKernelGGL(aasm_pack_place, g, b, 0, stream, a); break;
-            case KP_FLAT: hipLaunchKernelGGL(aasm_pack_flat, g, b, 0, stream, a); break;
-            case KP_ALL: hipLaunchKernelGGL(aasm_pack_all, g, b, 0, stream, a); break;
-            default: break;
+#define K(id, sym, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, stream, a); break;
+            AASM_PACK_KERNELS(K)
+#undef K
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) hip_fail("kernel launch", e);
@@ -674,21 +592,20 @@ struct GraphGpu {
     bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
         if (e != hipSuccess) return false;
         if (g1 <= g0) return true;
-        const dim3 grid((unsigned)(g1 - g0)), blk(64);
         switch (kid) {
-            case KSW_K_TREE: hipLaunchKernelGGL(aasm_ksw_tree, grid, blk, 0, stream, g0, a); break;
-            case KSW_K_HEAP: hipLaunchKernelGGL(aasm_ksw_heap, grid, blk, 0, stream, g0, a); break;
-            case KSW_K_ENUM: hipLaunchKernelGGL(aasm_ksw_enum, grid, blk, 0, stream, g0, a); break;
-            case KSW_K_COUNT: hipLaunchKernelGGL(aasm_ksw_count, grid, blk, 0, stream, g0, a); break;
-            default: hipLaunchKernelGGL(aasm_ksw_fill, grid, blk, 0, stream, g0, a); break;
+#define K(id, sym, block, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)(g1 - g0)), dim3(block), 0, stream, g0, a); break;
+            AASM_KSW_KERNELS(K)
+#undef K
         }
         return launched();
     }
     bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
         if (e != hipSuccess) return false;
-        const dim3 grid((unsigned)n_graphs), blk(64);
-        if (kid == SSSP_K_DIJKSTRA) hipLaunchKernelGGL(aasm_sssp_dijkstra_kernel, grid, blk, 0, stream, a);
-        else hipLaunchKernelGGL(aasm_sssp_dial_kernel, grid, blk, 0, stream, a);
+        switch (kid) {
+#define K(id, sym, block, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)n_graphs), dim3(block), 0, stream, a); break;
+            AASM_SSSP_KERNELS(K, K)
+#undef K
+        }
         return launched();
     }
     int err() {
@@ -1004,7 +921,7 @@ int aasm_debug_sort_replay(const int64_t *rec_off, int64_t n_contigs, const int6
     w.prof_heap = (int64_t *)filled((size_t)n_contigs * 64, 0);
 #endif
     if (!m.ok) return be.err();
-    hipLaunchKernelGGL(aasm_k1_sort_fix, dim3((unsigned)n_contigs), dim3(64), 0, be.stream, w);
+    launch_kernel(KN_SORT_FIX, n_contigs, kern_block[KN_SORT_FIX], be.stream, w);
     if (!be.launched() || !be.d2h(perm_out, w.perm, (size_t)R * 4)) return be.err();
 #if defined(AASM_KPROF)
     {                                                                // diagnostic build: mean cycles per section over the contigs

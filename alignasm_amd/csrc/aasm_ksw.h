@@ -352,7 +352,15 @@ static inline void ksw_free_out(aasm_ksw_out *o) {
     memset(o, 0, sizeof(*o));
 }
 
-enum { KSW_K_TREE = 0, KSW_K_HEAP, KSW_K_ENUM, KSW_K_COUNT, KSW_K_FILL };
+// The k-walk kernels, one 64-lane workgroup per graph of [g0, g1): K(id, symbol, block, lanes, body) as AASM_PIPELINE_KERNELS
+// (aasm_pipeline.h); body(k, a)
+#define AASM_KSW_KERNELS(K)                         \
+    K(KSW_K_TREE, aasm_ksw_tree, 64, 1, kb_ksw_tree)   \
+    K(KSW_K_HEAP, aasm_ksw_heap, 64, 1, kb_ksw_heap)   \
+    K(KSW_K_ENUM, aasm_ksw_enum, 64, 1, kb_ksw_enum)   \
+    K(KSW_K_COUNT, aasm_ksw_count, 64, 1, kb_ksw_count) \
+    K(KSW_K_FILL, aasm_ksw_fill, 64, 1, kb_ksw_fill)
+enum { AASM_KSW_KERNELS(AASM_ROW_ID) };
 
 // Backend BE: void *alloc(size_t) (nullptr = out of memory; freed with the backend), size_t mark() / release(mark) (free what
 // was allocated since), bool h2d(dst, src, n), bool d2h(dst, src, n), bool launch_from(kernel, g0, g1, args) (blocks for the

@@ -21,72 +21,93 @@
 namespace aasm {
 
 enum Kern {
-    KN_CS_RANGES, KN_SORT, KN_SORT_RANK, KN_SORT_FIX, KN_GATHER_PARTS, KN_OV_COUNT, KN_OV_MERGE, KN_VCOUNT, KN_VFILL_REC, KN_VFILL_SLOT,
-    KN_NSL, KN_ROW_COUNT, KN_ROW_FILL, KN_GRAPH, KN_GRAPH_L, KN_REV_FILL, KN_REV_FILL_W, KN_REV_FILL_ORD, KN_REV_FILL_ORD_S, KN_SORT_ROWS_REV, KN_REV_HDR, KN_REV_SWEEP, KN_FWD_SWEEP, KN_REV_SWEEP_G, KN_FWD_SWEEP_G,
-    KN_CHILDREN, KN_HEAP_CAP, KN_SIDETRACK_W, KN_HEAP_HDR, KN_HEAP, KN_HEAP_MW, KN_HEAP_MW8, KN_HEAP_MW16, KN_MW_RANK, KN_ENUM, KN_ENUM_S, KN_ENUM_HEAP, KN_SELECT, KN_GATHER_OUT, KN_TOPO_COUNT, KN_TOPO_FILL,
-    KN_SEL_PLAN, KN_SEL_PLANFILL, KN_SEL_RECOVER, KN_SEL_CLASSIFY, KN_SEL_CONVERT, KN_SEL_FINAL, KN_CHAIN, KN_CHAIN3, KN_K7_PREP, KN_TNX, KN_TNX16, KN_TNX16_WG
+// The pipeline's kernels, in id order: K(id, symbol, block, lanes, body) for a plain kernel, KL(id, symbol, block, lanes, LDS bytes,
+// waves, body) for one whose blocks keep a working set in LDS, with its registers budgeted for `waves` waves per SIMD (5: <= 96 VGPRs,
+// 6: <= 80): residency per CU is min(4 * waves, 160 KB / LDS bytes) blocks, and these kernels are latency-bound, so it is throughput.
+// block: the threads of every launch (and the kernel's __launch_bounds__); lanes: see aasm_dev.h; body: called as body(k, w).
+// (The table stands inside the enum of its ids, so that the enum's text still lists every id in order for readers of this header.)
+#define AASM_PIPELINE_KERNELS(K, KL)                                                                                                  \
+    K(KN_CS_RANGES, aasm_k0_cs_ranges, 256, ALL_LANES, kb_cs_ranges)                                                                  \
+    KL(KN_SORT, aasm_k1_sort, 256, 1, AASM_SORT_LDS_BYTES, 2, kb_sort)                                                                \
+    K(KN_SORT_RANK, aasm_k1_sort_rank, 256, ALL_LANES, kb_sort_rank)                                                                  \
+    KL(KN_SORT_FIX, aasm_k1_sort_fix, AASM_WAVE, 1, AASM_SORTFIX_LDS_BYTES, 1, kb_sort_fix)                                           \
+    K(KN_GATHER_PARTS, aasm_k1_gather_parts, AASM_WAVE, 1, kb_gather_parts)                                                           \
+    K(KN_OV_COUNT, aasm_k2_ov_count, 256, ALL_LANES, kb_ov_count)                                                                     \
+    K(KN_OV_MERGE, aasm_k2_ov_merge, 256, ALL_LANES, kb_ov_merge)                                                                     \
+    K(KN_VCOUNT, aasm_k2_vcount, 256, ALL_LANES, kb_vcount)                                                                           \
+    K(KN_VFILL_REC, aasm_k2_vfill_rec, 256, ALL_LANES, kb_vfill_rec)                                                                  \
+    K(KN_VFILL_SLOT, aasm_k2_vfill_slot, 256, ALL_LANES, kb_vfill_slot)                                                               \
+    K(KN_NSL, aasm_k4_nsl, 256, ALL_LANES, kb_nsl)                                                                                    \
+    K(KN_ROW_COUNT, aasm_k4_row_count, 256, ALL_LANES, kb_row_count)                                                                  \
+    K(KN_ROW_FILL, aasm_k4_row_fill, AASM_WAVE, 1, kb_row_fill)                                                                       \
+    /* rows + reversed CSR + sweep headers of one contig: 31.8 KB of LDS, 5 workgroups (20 waves) per CU */                           \
+    KL(KN_GRAPH, aasm_k46_graph, GB_TPB, 1, AASM_GB_LDS_BYTES, 5, kb_graph_build<GB_MAXV, GB_MAXE>)                                   \
+    /* contigs of up to 3 584 vertices / 8 192 edges: 62 KB, two workgroups per CU */                                                 \
+    KL(KN_GRAPH_L, aasm_k46_graph_l, GB_TPB, 1, AASM_GB_LDS_BYTES_T(GB_MAXV_L, GB_MAXE_L), 2, kb_graph_build<GB_MAXV_L, GB_MAXE_L>)   \
+    K(KN_REV_FILL, aasm_k6_rev_fill, 256, ALL_LANES, kb_rev_fill)                                                                     \
+    KL(KN_REV_FILL_W, aasm_k6_rev_fill_w, AASM_WAVE, 1, AASM_REVF_LDS_BYTES, 8, kb_rev_fill_w)                                        \
+    /* 25 KB of LDS per block: 6 blocks per CU, i.e. at most 2 waves per SIMD; contigs of <= 3 072 vertices: 6.7 KB */                \
+    KL(KN_REV_FILL_ORD, aasm_k6_rev_fill_ord, AASM_WAVE, 1, AASM_REVO_LDS_BYTES, 2, kb_rev_fill_ord)                                  \
+    KL(KN_REV_FILL_ORD_S, aasm_k6_rev_fill_ord_s, AASM_WAVE, 1, AASM_REVO_LDS_BYTES_V(REV_ORD_MIDV), 6, kb_rev_fill_ord)              \
+    KL(KN_SORT_ROWS_REV, aasm_k6_rev_place, AASM_WAVE, 1, AASM_REVP_LDS_BYTES, 4, kb_rev_place)                                       \
+    K(KN_REV_HDR, aasm_k6_rev_hdr, 256, ALL_LANES, kb_rev_hdr)                                                                        \
+    KL(KN_REV_SWEEP, aasm_k6_rev_sweep, AASM_WAVE, 1, AASM_REV_LDS_BYTES, 8, kb_rev_sweep<AASM_WAVE>)                                 \
+    KL(KN_FWD_SWEEP, aasm_k5_fwd_sweep, AASM_WAVE, 1, AASM_FWD_LDS_BYTES, 8, kb_fwd_sweep<AASM_WAVE>)                                 \
+    KL(KN_REV_SWEEP_G, aasm_k6_rev_sweep_g, AASM_WAVE, 1, (AASM_WAVE / AASM_SWEEP_G) * AASM_REV_LDS_BYTES, 4, kb_rev_sweep<AASM_SWEEP_G>) \
+    KL(KN_FWD_SWEEP_G, aasm_k5_fwd_sweep_g, AASM_WAVE, 1, (AASM_WAVE / AASM_SWEEP_G) * AASM_FWD_LDS_BYTES, 4, kb_fwd_sweep<AASM_SWEEP_G>) \
+    K(KN_CHILDREN, aasm_k7_children, 256, ALL_LANES, kb_children)                                                                     \
+    K(KN_HEAP_CAP, aasm_k7_heap_cap, 256, ALL_LANES, kb_heap_cap)                                                                     \
+    KL(KN_SIDETRACK_W, aasm_k7_sidetrack_w, AASM_WAVE, 1, AASM_SIDE_LDS_BYTES, 8, kb_sidetrack_w)                                     \
+    K(KN_HEAP_HDR, aasm_k7_heap_hdr, 256, ALL_LANES, kb_heap_hdr)                                                                     \
+    KL(KN_HEAP, aasm_k7_heap, AASM_WAVE, 1, AASM_HEAP_LDS_BYTES, 5, kb_heap<false, HEAP_RING_1W, HEAP_QN_1W>)                         \
+    KL(KN_HEAP_MW, aasm_k7_heap_mw, AASM_WAVE * 4, 1, AASM_MW_LDS_BYTES(4), 4, kb_heap_mw)                                            \
+    KL(KN_HEAP_MW8, aasm_k7_heap_mw8, AASM_WAVE * 8, 1, AASM_MW_LDS_BYTES(8), 4, kb_heap_mw)                                          \
+    KL(KN_HEAP_MW16, aasm_k7_heap_mw16, AASM_WAVE * 16, 1, AASM_MW_LDS_BYTES(16), 4, kb_heap_mw)                                      \
+    K(KN_MW_RANK, aasm_k7_mw_rank, 256, ALL_LANES, kb_mw_rank)                                                                        \
+    /* K8's LSM queues; the 1-lane host emulation runs the d-ary heap, with its LDS, in their place */                                \
+    KL(KN_ENUM, aasm_k8_enum, AASM_WAVE, 1, AASM_EMUL_OR(AASM_ENUM_LDS_BYTES, AASM_ENUM2_LDS_BYTES), 4,                               \
+       AASM_EMUL_OR(kb_enum_heap, kb_enum_lsm<64>))                                                                                   \
+    KL(KN_ENUM_S, aasm_k8_enum_s, AASM_WAVE, 1, AASM_EMUL_OR(AASM_ENUM_LDS_BYTES, AASM_ENUM2_LDS_BYTES_F(EQ_FSMALL)), 5,              \
+       AASM_EMUL_OR(kb_enum_heap, kb_enum_lsm<EQ_FSMALL>))                                                                            \
+    KL(KN_ENUM_HEAP, aasm_k8_enum_heap, AASM_WAVE, 1, AASM_ENUM_LDS_BYTES, 2, kb_enum_heap)                                           \
+    KL(KN_SELECT, aasm_k9_select, AASM_WAVE, 1, AASM_SEL_LDS_BYTES, 5, kb_select)                                                     \
+    K(KN_GATHER_OUT, aasm_k9_gather_out, AASM_WAVE, 1, kb_gather_out)                                                                 \
+    K(KN_TOPO_COUNT, aasm_k9_topo_count, 256, ALL_LANES, kb_topo_count)                                                               \
+    K(KN_TOPO_FILL, aasm_k9_topo_fill, AASM_WAVE, 1, kb_topo_fill)                                                                    \
+    K(KN_SEL_PLAN, aasm_k9_sel_plan, AASM_WAVE, 1, kb_sel_plan)                                                                       \
+    K(KN_SEL_PLANFILL, aasm_k9_sel_planfill, AASM_WAVE, 1, kb_sel_planfill)                                                           \
+    KL(KN_SEL_RECOVER, aasm_k9_sel_recover, AASM_WAVE, 1, AASM_SELREC_LDS_BYTES, 8, kb_sel_recover)                                   \
+    K(KN_SEL_CLASSIFY, aasm_k9_sel_classify, 256, ALL_LANES, kb_sel_classify)                                                         \
+    KL(KN_SEL_CONVERT, aasm_k9_sel_convert, AASM_WAVE, 1, AASM_SEL_LDS_BYTES, 5, kb_sel_convert)                                      \
+    K(KN_SEL_FINAL, aasm_k9_sel_final, AASM_WAVE, 1, kb_sel_final)                                                                    \
+    /* sweep + pre-pass + BFS order + heaps of one contig, a wave each (96 VGPRs, 19 spilled: worth it for the fifth wave slot per    \
+       SIMD); the emulation runs one lane per wave, in wave order: the sweep to its end, then the pre-pass, then the heaps */        \
+    KL(KN_CHAIN, aasm_k67_chain, AASM_WAVE * CHAIN_WAVES, CHAIN_WAVES, AASM_CHAIN_LDS_BYTES, 5, kb_chain<true>)                       \
+    /* ... without the order wave (the heap wave keeps its own queue): classes of more than AASM_CHAIN_ORD_MAX contigs */             \
+    KL(KN_CHAIN3, aasm_k67_chain3, AASM_WAVE * (CHAIN_WAVES - 1), CHAIN_WAVES - 1, AASM_CHAIN_LDS_BYTES, 5, kb_chain<false>)          \
+    K(KN_K7_PREP, aasm_k7_prep, 256, ALL_LANES, kb_k7_prep)                                                                           \
+    K(KN_TNX, aasm_k9_tnx, 256, ALL_LANES, kb_tnx)                                                                                    \
+    K(KN_TNX16, aasm_k9_tnx16, 256, ALL_LANES, kb_tnx16)                                                                              \
+    /* the 16-hop jump records of a small contig from its tree in LDS */                                                              \
+    KL(KN_TNX16_WG, aasm_k9_tnx16_wg, TNX_TPB, 1, AASM_TNXWG_LDS_BYTES, 4, kb_tnx16_wg)
+    AASM_PIPELINE_KERNELS(AASM_ROW_ID, AASM_ROW_ID)
 };
+constexpr int kern_block[] = {AASM_PIPELINE_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
 
-// dispatch a kernel body (used verbatim by both backends)
+// a kernel's body by id, for the host emulation and the __global__ kernels (called directly, 14 of the bodies inline into other code)
 AASM_DEV void run_kernel_body(int kn, const KCtx &k, const WS &w) {
     switch (kn) {
-        case KN_CS_RANGES: kb_cs_ranges(k, w); break;
-        case KN_SORT: kb_sort(k, w); break;
-        case KN_SORT_RANK: kb_sort_rank(k, w); break;
-        case KN_SORT_FIX: kb_sort_fix(k, w); break;
-        case KN_GATHER_PARTS: kb_gather_parts(k, w); break;
-        case KN_OV_COUNT: kb_ov_count(k, w); break;
-        case KN_OV_MERGE: kb_ov_merge(k, w); break;
-        case KN_VCOUNT: kb_vcount(k, w); break;
-        case KN_VFILL_REC: kb_vfill_rec(k, w); break;
-        case KN_VFILL_SLOT: kb_vfill_slot(k, w); break;
-        case KN_NSL: kb_nsl(k, w); break;
-        case KN_ROW_COUNT: kb_row_count(k, w); break;
-        case KN_ROW_FILL: kb_row_fill(k, w); break;
-        case KN_GRAPH: kb_graph_build<GB_MAXV, GB_MAXE>(k, w); break;
-        case KN_GRAPH_L: kb_graph_build<GB_MAXV_L, GB_MAXE_L>(k, w); break;
-        case KN_REV_FILL: kb_rev_fill(k, w); break;
-        case KN_REV_FILL_W: kb_rev_fill_w(k, w); break;
-        case KN_REV_FILL_ORD: case KN_REV_FILL_ORD_S: kb_rev_fill_ord(k, w); break;
-        case KN_SORT_ROWS_REV: kb_rev_place(k, w); break;
-        case KN_REV_HDR: kb_rev_hdr(k, w); break;
-        case KN_REV_SWEEP: kb_rev_sweep<AASM_WAVE>(k, w); break;
-        case KN_FWD_SWEEP: kb_fwd_sweep<AASM_WAVE>(k, w); break;
-        case KN_REV_SWEEP_G: kb_rev_sweep<AASM_SWEEP_G>(k, w); break;
-        case KN_FWD_SWEEP_G: kb_fwd_sweep<AASM_SWEEP_G>(k, w); break;
-        case KN_CHILDREN: kb_children(k, w); break;
-        case KN_HEAP_CAP: kb_heap_cap(k, w); break;
-        case KN_SIDETRACK_W: kb_sidetrack_w(k, w); break;
-        case KN_HEAP_HDR: kb_heap_hdr(k, w); break;
-        case KN_HEAP: kb_heap<false, HEAP_RING_1W, HEAP_QN_1W>(k, w); break;
-        case KN_HEAP_MW: case KN_HEAP_MW8: case KN_HEAP_MW16: kb_heap_mw(k, w); break;
-        case KN_MW_RANK: kb_mw_rank(k, w); break;
-#if defined(AASM_HOST_EMUL)
-        case KN_ENUM: case KN_ENUM_S: case KN_ENUM_HEAP: kb_enum_heap(k, w); break;
-#else
-        case KN_ENUM: kb_enum_lsm<64>(k, w); break;
-        case KN_ENUM_S: kb_enum_lsm<EQ_FSMALL>(k, w); break;
-        case KN_ENUM_HEAP: kb_enum_heap(k, w); break;
-#endif
-        case KN_SELECT: kb_select(k, w); break;
-        case KN_GATHER_OUT: kb_gather_out(k, w); break;
-        case KN_TOPO_COUNT: kb_topo_count(k, w); break;
-        case KN_TOPO_FILL: kb_topo_fill(k, w); break;
-        case KN_SEL_PLAN: kb_sel_plan(k, w); break;
-        case KN_SEL_PLANFILL: kb_sel_planfill(k, w); break;
-        case KN_SEL_RECOVER: kb_sel_recover(k, w); break;
-        case KN_SEL_CLASSIFY: kb_sel_classify(k, w); break;
-        case KN_SEL_CONVERT: kb_sel_convert(k, w); break;
-        case KN_SEL_FINAL: kb_sel_final(k, w); break;
-        case KN_CHAIN: kb_chain<true>(k, w); break;
-        case KN_CHAIN3: kb_chain<false>(k, w); break;
-        case KN_K7_PREP: kb_k7_prep(k, w); break;
-        case KN_TNX: kb_tnx(k, w); break;
-        case KN_TNX16: kb_tnx16(k, w); break;
-        case KN_TNX16_WG: kb_tnx16_wg(k, w); break;
-        default: break;
+#define K(id, sym, block, lanes, ...) case id: __VA_ARGS__(k, w); break;
+#define KL(id, sym, block, lanes, lds, waves, ...) case id: __VA_ARGS__(k, w); break;
+        AASM_PIPELINE_KERNELS(K, KL)
+#undef K
+#undef KL
     }
 }
+
+// A launch of `nblocks` blocks of the kernel's own size: backends take (kernel, blocks, threads, args), and every launch but
+// AASM_H2_LAUNCH_FAILURE's (run_pipeline) goes through here.
+template <class B> void launch(B &be, int kn, int64_t nblocks, const WS &w) { be.launch(kn, nblocks, kern_block[kn], w); }
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #ifndef AASM_CHAIN_ORD_MAX
@@ -125,7 +146,7 @@ static inline Hooks decode_hooks(const aasm_opts &o) {
 struct FormSizes { int64_t C, R, K, VT, ET, MAXV, NCHAIN, HTM, NMW, MAXN; };
 struct Forms {
     bool grouped, dense, mw_ranked;   // sweeps two contigs per wave; mean degree > 6; K7's several-waves class by rank, largest node bound first
-    int rev_fill, chain, mw_kern, mw_waves, enum_kern;   // the kernels of the reversed CSR's fill, the chain class, K7's class, K8's queue
+    int rev_fill, chain, mw_kern, enum_kern;   // the kernels of the reversed CSR's fill, the chain class, K7's class, K8's queue
 };
 static inline Forms choose_forms(const FormSizes &s, const Hooks &h, bool host_emulation) {
     Forms f;
@@ -141,8 +162,8 @@ static inline Forms choose_forms(const FormSizes &s, const Hooks &h, bool host_e
     // beyond that the three-role kernel, where the heap wave keeps its own queue
     f.chain = !h.chain_own_queue && s.NCHAIN <= AASM_CHAIN_ORD_MAX ? KN_CHAIN : KN_CHAIN3;
     // 16, 8 or 4 waves a contig, by how many of them share the chip's ~8 k wave slots
-    f.mw_waves = (h.mw == 4 || h.mw == 8 || h.mw == 16) ? h.mw : s.NMW * 16 <= 6144 ? 16 : s.NMW * 8 <= 6144 ? 8 : 4;
-    f.mw_kern = f.mw_waves == 16 ? KN_HEAP_MW16 : f.mw_waves == 8 ? KN_HEAP_MW8 : KN_HEAP_MW;
+    const int mw_waves = (h.mw == 4 || h.mw == 8 || h.mw == 16) ? h.mw : s.NMW * 16 <= 6144 ? 16 : s.NMW * 8 <= 6144 ? 8 : 4;
+    f.mw_kern = mw_waves == 16 ? KN_HEAP_MW16 : mw_waves == 8 ? KN_HEAP_MW8 : KN_HEAP_MW;
     f.mw_ranked = h.mw != AASM_H0_MW_INPUT_ORDER && s.NMW >= 2 && s.NMW <= 32768;   // (ranked by counting: NMW^2 compares)
     // K8: sorted front + sorted runs (aasm_enum.h) unless a contig is too long for its packed ratio key; the d-ary heap is also what the
     // 1-lane host emulation runs.  More contigs than the 64-entry front keeps resident (14 waves per CU = 3 584): the 40-entry front (20 per
@@ -214,7 +235,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         CHECK_ALLOC();
         w.rng_rec -= 4 * G0;                                         // indexed with the batch's own range offsets
         be.zero(w.cs_bad, 8);
-        be.launch(KN_CS_RANGES, cdiv(R, 256), 256, w);
+        launch(be, KN_CS_RANGES, cdiv(R, 256), w);
         be.phase_end(AASM_PH_CS);
         const int32_t badv = (int32_t)(uint32_t)(uint64_t)be.read_i64((const int64_t *)w.cs_bad);   // 0 = none, else record - INT32_MAX
         if (badv != 0) { sz.bad_record = R0 + ((int64_t)badv + INT32_MAX); return AASM_E_PARSE; }
@@ -228,18 +249,18 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     A(s_qt, int64_t, R, "s_qt"); A(s_rb, int64_t, R, "s_rb"); A(s_rn, int32_t, R, "s_rn"); A(s_chr, int32_t, R, "s_chr");
     A(s_orig, int32_t, R, "s_orig"); A(s_ctg, int32_t, R, "s_ctg"); A(s_pid, int32_t, R, "s_pid"); A(s_fl, uint8_t, R, "s_fl");
     CHECK_ALLOC();
-    if (h.launch_failure) be.launch(KN_SORT, C, 4096, w);           // an invalid launch configuration (block size > 1024)
-    be.launch(KN_SORT, C, 256, w);
-    be.launch(KN_SORT_RANK, cdiv(R, 256), 256, w);
-    be.launch(KN_SORT_FIX, C, AASM_WAVE, w);
-    be.launch(KN_GATHER_PARTS, C, AASM_WAVE, w);
+    if (h.launch_failure) be.launch(KN_SORT, C, 4096, w);           // the one block size off the table: an invalid launch configuration (> 1024)
+    launch(be, KN_SORT, C, w);
+    launch(be, KN_SORT_RANK, cdiv(R, 256), w);
+    launch(be, KN_SORT_FIX, C, w);
+    launch(be, KN_GATHER_PARTS, C, w);
     be.phase_end(AASM_PH_SORT);
 
     // ---- K2 overlap slots
     be.phase_begin(AASM_PH_PAIRS);
     A(ov_cnt, int32_t, R, "ov_cnt"); A(ov_off, int64_t, R + 1, "ov_off");
     CHECK_ALLOC();
-    be.launch(KN_OV_COUNT, cdiv(R, 256), 256, w);
+    launch(be, KN_OV_COUNT, cdiv(R, 256), w);
     be.scan_i32(w.ov_cnt, R, w.ov_off);
     const int64_t S = be.read_i64(w.ov_off + R);
     w.S = S; sz.S = S;
@@ -247,18 +268,18 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     A(ov_peq, int64_t, S, "ov_peq"); A(ov_per, int64_t, S, "ov_per"); A(ov_stq, int64_t, S, "ov_stq"); A(ov_str, int64_t, S, "ov_str");
     A(ov_ok, uint8_t, S, "ov_ok");
     CHECK_ALLOC();
-    if (S > 0) be.launch(KN_OV_MERGE, cdiv(S, 256), 256, w);
+    if (S > 0) launch(be, KN_OV_MERGE, cdiv(S, 256), w);
     be.scan_u8(w.ov_ok, S, w.ov_rank);
     A(ctgV, int32_t, C, "ctgV"); A(voff, int64_t, C + 1, "voff");
     CHECK_ALLOC();
-    be.launch(KN_VCOUNT, cdiv(C, 256), 256, w);
+    launch(be, KN_VCOUNT, cdiv(C, 256), w);
     be.scan_i32(w.ctgV, C, w.voff);
     const int64_t VT = be.read_i64(w.voff + C);
     w.VT = VT; sz.VT = VT;
     A(v_i, int32_t, VT, "v_i"); A(v_j, int32_t, VT, "v_j"); A(v_ctg, int32_t, VT, "v_ctg"); A(v_slot, int64_t, VT, "v_slot");
     CHECK_ALLOC();
-    be.launch(KN_VFILL_REC, cdiv(R, 256), 256, w);
-    if (S > 0) be.launch(KN_VFILL_SLOT, cdiv(S, 256), 256, w);
+    launch(be, KN_VFILL_REC, cdiv(R, 256), w);
+    if (S > 0) launch(be, KN_VFILL_SLOT, cdiv(S, 256), w);
     be.phase_end(AASM_PH_PAIRS);
 
     // main/alt outputs exist even when no contig has a graph (all single-record contigs)
@@ -276,7 +297,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         if (w.nsl) {
             A(dis_end, int32_t, R, "dis_end"); AZ(next_cnt, int32_t, R, "next_cnt");
             CHECK_ALLOC();
-            be.launch(KN_NSL, cdiv(R, 256), 256, w);
+            launch(be, KN_NSL, cdiv(R, 256), w);
         }
         A(deg, int32_t, VT, "deg"); A(rowptr, int64_t, VT + 1, "csr_rowptr");
         // (heap arena sizing + classes need only V and E per contig: sized here, so that their read-back shares the edges' one)
@@ -287,9 +308,9 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         w.mw_mode = h.heap_mw;
         w.mw_compact = opts.keep_debug ? 1 : 0;   // debug runs compare arena indices with the reference's allocation order
         CHECK_ALLOC();
-        be.launch(KN_ROW_COUNT, cdiv(VT, 256), 256, w);
+        launch(be, KN_ROW_COUNT, cdiv(VT, 256), w);
         be.scan_i32(w.deg, VT, w.rowptr);
-        be.launch(KN_HEAP_CAP, cdiv(C, 256), 256, w);
+        launch(be, KN_HEAP_CAP, cdiv(C, 256), w);
         be.scan_i32_pair(w.hcap_cnt, w.hoff, w.mw_cap, w.mw_off, C);
         int64_t et_mv[12];
         be.read_i64s({w.rowptr + VT, w.counters + CNT_MAXV, w.hoff + C, w.mw_off + C, w.counters + CNT_MW, w.counters + CNT_MAXN, w.counters + CNT_CHAIN, w.counters + CNT_GB_S, w.counters + CNT_GB_L, w.counters + CNT_GB_REST}, et_mv);
@@ -313,14 +334,14 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         w.indeg = nullptr;
         if (GB_REST > 0) { AZ(indeg, int32_t, VT, "indeg"); AZ(rcur, int32_t, VT, "rcur"); }   // (two fills in one)
         CHECK_ALLOC();
-        if (GB_S > 0) be.launch(KN_GRAPH, C, GB_TPB, w);
-        if (GB_L > 0) be.launch(KN_GRAPH_L, C, GB_TPB, w);
+        if (GB_S > 0) launch(be, KN_GRAPH, C, w);
+        if (GB_L > 0) launch(be, KN_GRAPH_L, C, w);
         if (GB_REST == 0) {
             be.phase_end(AASM_PH_EDGES);
             be.phase_begin(AASM_PH_REVCSR);
             be.phase_end(AASM_PH_REVCSR);
         } else {
-        be.launch(KN_ROW_FILL, cdiv(VT, AASM_WAVE), AASM_WAVE, w);
+        launch(be, KN_ROW_FILL, cdiv(VT, AASM_WAVE), w);
         be.phase_end(AASM_PH_EDGES);
 
         // ---- reversed CSR
@@ -328,13 +349,13 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         A(r_e, int32_t, ET, "r_e"); A(tmp_pk, I4, ET, "tmp_pk");
         CHECK_ALLOC();
         be.scan_i32(w.indeg, VT, w.rptr);
-        if (f.rev_fill == KN_REV_FILL_ORD_S || f.rev_fill == KN_REV_FILL_ORD) be.launch(f.rev_fill, C, AASM_WAVE, w);
+        if (f.rev_fill == KN_REV_FILL_ORD_S || f.rev_fill == KN_REV_FILL_ORD) launch(be, f.rev_fill, C, w);
         else {
-            if (f.rev_fill == KN_REV_FILL_W) be.launch(KN_REV_FILL_W, cdiv(VT, AASM_WAVE), AASM_WAVE, w);
-            else be.launch(KN_REV_FILL, cdiv(VT, 256), 256, w);
-            be.launch(KN_SORT_ROWS_REV, cdiv(VT, AASM_WAVE), AASM_WAVE, w);
+            if (f.rev_fill == KN_REV_FILL_W) launch(be, KN_REV_FILL_W, cdiv(VT, AASM_WAVE), w);
+            else launch(be, KN_REV_FILL, cdiv(VT, 256), w);
+            launch(be, KN_SORT_ROWS_REV, cdiv(VT, AASM_WAVE), w);
         }
-        be.launch(KN_REV_HDR, cdiv(VT, 256), 256, w);
+        launch(be, KN_REV_HDR, cdiv(VT, 256), w);
         be.phase_end(AASM_PH_REVCSR);
         }
 
@@ -349,13 +370,13 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             be.fork();                                               // side stream waits for everything enqueued so far
             be.use_side(true);
             be.phase_begin(AASM_PH_FWD);
-            if (f.grouped) be.launch(KN_FWD_SWEEP_G, cdiv(C, sweep_n), AASM_WAVE, w);
-            else be.launch(KN_FWD_SWEEP, C, AASM_WAVE, w);
+            if (f.grouped) launch(be, KN_FWD_SWEEP_G, cdiv(C, sweep_n), w);
+            else launch(be, KN_FWD_SWEEP, C, w);
             be.phase_end(AASM_PH_FWD);
             be.phase_begin(AASM_PH_TOPO);
-            be.launch(KN_TOPO_COUNT, cdiv(VT, 256), 256, w);
+            launch(be, KN_TOPO_COUNT, cdiv(VT, 256), w);
             be.scan_i32(w.tp_deg, VT, w.tp_ptr);
-            be.launch(KN_TOPO_FILL, cdiv(VT, AASM_WAVE), AASM_WAVE, w);
+            launch(be, KN_TOPO_FILL, cdiv(VT, AASM_WAVE), w);
             be.phase_end(AASM_PH_TOPO);
             be.use_side(false);
         };
@@ -381,15 +402,15 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             be.fork2();
             be.use_side2(true);
             be.phase_begin(AASM_PH_CHAIN);
-            if (f.chain == KN_CHAIN) be.launch(KN_CHAIN, NCHAIN, AASM_WAVE * CHAIN_WAVES, w);
-            else be.launch(KN_CHAIN3, NCHAIN, AASM_WAVE * (CHAIN_WAVES - 1), w);   // (no order wave: three waves a contig, five workgroups a CU; 1 250 contigs 4.6 ms where four-wave workgroups took 6.0)
+            if (f.chain == KN_CHAIN) launch(be, KN_CHAIN, NCHAIN, w);
+            else launch(be, KN_CHAIN3, NCHAIN, w);   // (no order wave: three waves a contig, five workgroups a CU; 1 250 contigs 4.6 ms where four-wave workgroups took 6.0)
             be.phase_end(AASM_PH_CHAIN);
             be.use_side2(false);
         }
         if (NCHAIN < C) {
         be.phase_begin(AASM_PH_SPTREE);
-        if (f.grouped) be.launch(KN_REV_SWEEP_G, cdiv(C, sweep_n), AASM_WAVE, w);
-        else be.launch(KN_REV_SWEEP, C, AASM_WAVE, w);
+        if (f.grouped) launch(be, KN_REV_SWEEP_G, cdiv(C, sweep_n), w);
+        else launch(be, KN_REV_SWEEP, C, w);
         be.phase_end(AASM_PH_SPTREE);
 
         // ---- K7 heaps
@@ -397,25 +418,25 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         // side stream, which finishes its topological copy about when the reverse sweep ends, and run beside the heap pre-pass
         be.fork_again();
         be.use_side(true);
-        if (GB_S + GB_L > 0) be.launch(KN_TNX16_WG, C, TNX_TPB, w);  // (the small contigs of a sparse batch - kb_graph_build's class: sixteen hops through the tree in LDS)
+        if (GB_S + GB_L > 0) launch(be, KN_TNX16_WG, C, w);  // (the small contigs of a sparse batch - kb_graph_build's class: sixteen hops through the tree in LDS)
         if (GB_REST > 0) {
-            be.launch(KN_TNX, cdiv(VT, 256), 256, w);
-            be.launch(KN_TNX16, cdiv(VT, 256), 256, w);
+            launch(be, KN_TNX, cdiv(VT, 256), w);
+            launch(be, KN_TNX16, cdiv(VT, 256), w);
         }
         be.use_side(false);
         be.phase_begin(AASM_PH_HEAP_PREP);
         if (f.dense) {
-            be.launch(KN_CHILDREN, cdiv(VT, 256), 256, w);
-            be.launch(KN_SIDETRACK_W, cdiv(VT, AASM_WAVE), AASM_WAVE, w);   // dense: lanes over the edges of 64 rows
-            be.launch(KN_HEAP_HDR, cdiv(VT, 256), 256, w);
-        } else be.launch(KN_K7_PREP, cdiv(VT, 256), 256, w);         // child list + keys + header of a vertex: one thread, one launch
+            launch(be, KN_CHILDREN, cdiv(VT, 256), w);
+            launch(be, KN_SIDETRACK_W, cdiv(VT, AASM_WAVE), w);   // dense: lanes over the edges of 64 rows
+            launch(be, KN_HEAP_HDR, cdiv(VT, 256), w);
+        } else launch(be, KN_K7_PREP, cdiv(VT, 256), w);         // child list + keys + header of a vertex: one thread, one launch
         be.phase_end(AASM_PH_HEAP_PREP);
         // Nothing may START beside the heap kernel: all its workgroups are resident for the whole launch, so whatever share of the CUs a
         // second queue holds while they are dealt out skews their placement for good (measured: the 0.2 ms jump-record kernel started
         // beside it cost it 1.8 ms, 4.05 -> 5.8; the forward sweep beside it 0.5-0.9 ms in round 4).  The side stream is done by now.
         be.join();
         be.phase_begin(AASM_PH_HEAP);
-        be.launch(KN_HEAP, C, AASM_WAVE, w);
+        launch(be, KN_HEAP, C, w);
         // contigs of the wide-tree class (kb_heap skips them)
         w.mw_n = (int32_t)NMW; w.mw_base = -1;
         if (HTM > 0) {
@@ -424,11 +445,11 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             // share a CU's issue slots and the launch ends with such a clump.  Largest first deals every CU a spread of weights and
             // starts the longest chains first: C5 share 35.5 -> 30.0 ms, 700 contigs 27.3 -> 25.5, 400 x 1 500 records 25.1 -> 22.8.
             if (f.mw_ranked) {
-                be.launch(KN_MW_RANK, cdiv(NMW, 256), 256, w);
+                launch(be, KN_MW_RANK, cdiv(NMW, 256), w);
                 w.mw_base = 0;
-                { const int32_t xm = w.xcd_map; w.xcd_map = 0; be.launch(f.mw_kern, NMW, AASM_WAVE * f.mw_waves, w); w.xcd_map = xm; }   // (its order is its own)
+                { const int32_t xm = w.xcd_map; w.xcd_map = 0; launch(be, f.mw_kern, NMW, w); w.xcd_map = xm; }   // (its order is its own)
                 w.mw_base = -1;
-            } else be.launch(f.mw_kern, C, AASM_WAVE * f.mw_waves, w);
+            } else launch(be, f.mw_kern, C, w);
         }
         be.phase_end(AASM_PH_HEAP);
         }                                                            // (NCHAIN < C)
@@ -441,7 +462,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         A(kcand, I4, 2 * C * (3 * K + 1), "kcand"); A(pq, PqK, C * w.pq_stride, "pq");
         CHECK_ALLOC();
         be.phase_begin(AASM_PH_ENUM);
-        be.launch(f.enum_kern, C, AASM_WAVE, w);
+        launch(be, f.enum_kern, C, w);
         be.phase_end(AASM_PH_ENUM);
     }
 
@@ -460,7 +481,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     int64_t nm[2] = {0, 0};
     if (!sequential) {
         be.phase_begin(AASM_PH_MISC);
-        if (VT > 0) be.launch(KN_SEL_PLAN, C, AASM_WAVE, w);
+        if (VT > 0) launch(be, KN_SEL_PLAN, C, w);
         be.scan_i32(w.nconv, C, w.conv_off);
         NCONV = be.read_i64(w.conv_off + C);
         w.NCONV = NCONV;
@@ -469,7 +490,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             A(cv_szr, int32_t, NCONV, "cv_szr"); A(cv_szv, int32_t, NCONV, "cv_szv"); A(cv_roff, int64_t, NCONV + 1, "cv_roff"); A(cv_voff, int64_t, NCONV + 1, "cv_voff");
             AZ(cv_n, int32_t, NCONV, "cv_n"); AZ(cv_err, int32_t, NCONV, "cv_err"); AZ(cv_cov, int64_t, NCONV, "cv_cov"); A(cv_la, int32_t, NCONV, "cv_la");
             CHECK_ALLOC();
-            be.launch(KN_SEL_PLANFILL, C, AASM_WAVE, w);
+            launch(be, KN_SEL_PLANFILL, C, w);
             be.scan_i32_pair(w.cv_szr, w.cv_roff, w.cv_szv, w.cv_voff, NCONV);
             int64_t sv[2];
             be.read_i64s({w.cv_roff + NCONV, w.cv_voff + NCONV}, sv);
@@ -485,13 +506,13 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             A(cv_dist2, Dist, SV, "cv_dist2"); A(cv_pre2, int32_t, SV, "cv_pre2"); AZ(cv_stamp, int32_t, SV, "cv_stamp");
             CHECK_ALLOC();
             be.phase_begin(AASM_PH_SELECT);
-            be.launch(KN_SEL_RECOVER, NCONV, AASM_WAVE, w);
-            be.launch(KN_SEL_CLASSIFY, NCONV, 256, w);
-            be.launch(KN_SEL_CONVERT, NCONV, AASM_WAVE, w);
+            launch(be, KN_SEL_RECOVER, NCONV, w);
+            launch(be, KN_SEL_CLASSIFY, NCONV, w);
+            launch(be, KN_SEL_CONVERT, NCONV, w);
             be.phase_end(AASM_PH_SELECT);
         }
         be.phase_begin(AASM_PH_FINAL);
-        be.launch(KN_SEL_FINAL, C, AASM_WAVE, w);
+        launch(be, KN_SEL_FINAL, C, w);
         // the output lengths are final with the pick: their offsets are scanned at once, and ONE read-back brings the pool demand and the
         // two totals (it was a wait for the demand, then the scans, then a wait for the totals)
         be.scan_i32_pair(w.main_len, w.main_off, w.alt_len, w.alt_off, C);
@@ -507,7 +528,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             CHECK_ALLOC();
             be.zero(w.all_seq, sizeof(int32_t) * (size_t)C);
             be.zero(w.counters + CNT_POOL, sizeof(int64_t)); be.zero(w.counters + CNT_AR, sizeof(int64_t)); be.zero(w.counters + CNT_OVF, sizeof(int64_t));
-            be.launch(KN_SEL_FINAL, C, AASM_WAVE, w);
+            launch(be, KN_SEL_FINAL, C, w);
             nm_ready = false;                                        // (the same lengths again, but keep the one code path: scanned and read below)
         }
         be.phase_end(AASM_PH_FINAL);
@@ -516,7 +537,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
         A(pre2, int32_t, VT, "pre2"); AZ(stamp, int32_t, VT, "stamp"); A(dist2, Dist, VT, "dist2");
         CHECK_ALLOC();
         be.phase_begin(AASM_PH_SELECT);
-        be.launch(KN_SELECT, C, AASM_WAVE, w);
+        launch(be, KN_SELECT, C, w);
         be.phase_end(AASM_PH_SELECT);
         int64_t np2[2];
         be.read_i64s({w.counters + CNT_POOL, w.counters + CNT_AR}, np2);
@@ -535,7 +556,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
             be.zero(w.counters + CNT_ISPR_E, sizeof(int64_t)); be.zero(w.counters + CNT_ISPR_V, sizeof(int64_t));
             be.zero(w.counters + CNT_PATH_E, sizeof(int64_t)); be.zero(w.counters + CNT_OUT_E, sizeof(int64_t));
             be.phase_begin(AASM_PH_MISC);
-            be.launch(KN_SELECT, C, AASM_WAVE, w);
+            launch(be, KN_SELECT, C, w);
             be.phase_end(AASM_PH_MISC);
         }
     }
@@ -549,7 +570,7 @@ int run_pipeline(B &be, const aasm_batch_in &in, const aasm_opts &opts, WS &w, P
     const int64_t NM = nm[0], NA = nm[1];
     A(main_c, OutElem, NM, "main_c"); A(alt_c, OutElem, NA, "alt_c");
     CHECK_ALLOC();
-    be.launch(KN_GATHER_OUT, C, AASM_WAVE, w);
+    launch(be, KN_GATHER_OUT, C, w);
     be.phase_end(AASM_PH_GATHER);
 #undef A
 #undef AZ
@@ -637,19 +658,27 @@ int fetch_results(B &be, const WS &w, const PipelineSizes &sz, aasm_batch_out *o
 
 // ---- device-side export (aasm_result_sizes / aasm_result_export): fetch_results' arrays built on the device ----------------
 // Backends provide alloc / zero / fill_ff / scan_i32 / read_i64s as for the pipeline, and launch_pack(kernel, blocks, threads,
-// PackArgs).  The scratch is carved out of the result's workspace when the result is made (pack_alloc, behind run_pipeline);
+// PackArgs).
+// The scratch is carved out of the result's workspace when the result is made (pack_alloc, behind run_pipeline);
 // sizes = count -> scan -> place -> scan -> ONE read-back, run once per result: exports in flight read that scratch, so a later
 // sizes call answers from the cached sizes and never rebuilds it; export = two launches, no read-back.
-enum PackKern { KP_COUNT, KP_PLACE, KP_FLAT, KP_ALL };
-AASM_DEV void run_pack_body(int kn, const KCtx &k, const PackArgs &a) {
-    switch (kn) {
-        case KP_COUNT: kb_pack_count(k, a); break;
-        case KP_PLACE: kb_pack_place(k, a); break;
-        case KP_FLAT: kb_pack_flat(k, a); break;
-        case KP_ALL: kb_pack_all(k, a); break;
-        default: break;
+// The pack kernels: K(id, symbol, block, lanes, body) as AASM_PIPELINE_KERNELS, body called as body(k, a).
+#define AASM_PACK_KERNELS(K)                                    \
+    K(KP_COUNT, aasm_pack_count, 256, ALL_LANES, kb_pack_count) \
+    K(KP_PLACE, aasm_pack_place, 256, ALL_LANES, kb_pack_place) \
+    K(KP_FLAT, aasm_pack_flat, 256, ALL_LANES, kb_pack_flat)    \
+    K(KP_ALL, aasm_pack_all, 256, ALL_LANES, kb_pack_all)
+enum PackKern { AASM_PACK_KERNELS(AASM_ROW_ID) };
+constexpr int pack_block[] = {AASM_PACK_KERNELS(AASM_ROW_BLOCK)};
+// a pack kernel's body by id
+AASM_DEV void run_pack_body(int kp, const KCtx &k, const PackArgs &a) {
+    switch (kp) {
+#define K(id, sym, block, lanes, ...) case id: __VA_ARGS__(k, a); break;
+        AASM_PACK_KERNELS(K)
+#undef K
     }
 }
+template <class B> void launch(B &be, int kp, int64_t nblocks, const PackArgs &a) { be.launch_pack(kp, nblocks, pack_block[kp], a); }
 #define AASM_PACK_MAX_BLOCKS 2048   // 256-thread blocks of the copies: 8 waves per CU of the 256 (grid-stride beyond)
 
 struct PackWS {
@@ -699,9 +728,9 @@ int pack_sizes(B &be, const WS &w, PackWS &p) {
     be.zero(p.np, sizeof(int32_t) * (size_t)C);
     be.fill_ff(p.prec, sizeof(int32_t) * (size_t)AR);
     be.zero(p.plen, sizeof(int32_t) * (size_t)AR);
-    be.launch_pack(KP_COUNT, cdiv(std::max(C, AR), 256), 256, a);
+    launch(be, KP_COUNT, cdiv(std::max(C, AR), 256), a);
     be.scan_i32(p.np, C, p.poff);
-    be.launch_pack(KP_PLACE, cdiv(AR, 256), 256, a);
+    launch(be, KP_PLACE, cdiv(AR, 256), a);
     be.scan_i32(p.plen, AR, p.eoff);                                 // (slots past the last path are 0: eoff[NP .. AR] = NE)
     int64_t v[4];
     be.read_i64s({p.poff + C, p.eoff + AR, w.main_off + C, w.alt_off + C}, v);
@@ -719,8 +748,8 @@ void pack_export(B &be, const WS &w, const PackWS &p, const aasm_dev_out &d) {
     a.d_main_off = d.main_off; a.d_alt_off = d.alt_off; a.d_path_off = d.all_path_off; a.d_elem_off = d.all_elem_off;
     a.d_main = (OutElem *)d.main_elems; a.d_alt = (OutElem *)d.alt_elems; a.d_all = (OutElem *)d.all_elems; a.d_status = d.ctg_status;
     const int64_t words = std::max(std::max(w.C + 1, a.NP + 1), 5 * std::max(a.NM, a.NA));
-    be.launch_pack(KP_FLAT, std::min<int64_t>(cdiv(words, 256), AASM_PACK_MAX_BLOCKS), 256, a);
-    if (a.NP > 0) be.launch_pack(KP_ALL, std::min<int64_t>(cdiv(a.NP, 256 / AASM_WAVE), AASM_PACK_MAX_BLOCKS), 256, a);
+    launch(be, KP_FLAT, std::min<int64_t>(cdiv(words, 256), AASM_PACK_MAX_BLOCKS), a);
+    if (a.NP > 0) launch(be, KP_ALL, std::min<int64_t>(cdiv(a.NP, 256 / AASM_WAVE), AASM_PACK_MAX_BLOCKS), a);
 }
 
 }  // namespace aasm

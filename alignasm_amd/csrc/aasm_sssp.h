@@ -309,7 +309,12 @@ template <class BE> struct DevMem {
     }
 };
 
-enum { SSSP_K_DIJKSTRA = 0, SSSP_K_DIAL };
+// The SSSP kernels, one 64-lane workgroup per graph: K(id, symbol, block, lanes, body) as AASM_PIPELINE_KERNELS (aasm_pipeline.h),
+// KL(id, symbol, block, lanes, LDS bytes, body) for Dial's, which keeps its buckets in LDS (no waves-per-SIMD bound); body(k, a).
+#define AASM_SSSP_KERNELS(K, KL)                                     \
+    K(SSSP_K_DIJKSTRA, aasm_sssp_dijkstra_kernel, 64, 1, kb_sssp_dijkstra) \
+    KL(SSSP_K_DIAL, aasm_sssp_dial_kernel, 64, 1, sizeof(DialLds), kb_sssp_dial)
+enum { AASM_SSSP_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
 
 // Backend BE: ksw_run's contract (aasm_ksw.h), with bool launch(kernel, n_graphs, SsspArgs) for the SSSP kernels (one block
 // per graph of the whole batch).  why: the message of a failure the driver itself finds.

@@ -10,7 +10,6 @@ and the PRODUCT through alignasm_amd.api (libalignasm_amd.so, C-ABI).
 """
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -58,6 +57,7 @@ def emul():
         lib.emul_debug_fetch.restype = C.c_int64
         lib.emul_last_bad_record.restype = C.c_int64
         lib.emul_launch_log.restype = C.c_int64
+        lib.emul_kernel_name.restype = C.c_char_p
         _cache["e"] = lib
     return _cache["e"]
 
@@ -335,10 +335,11 @@ def emul_solve(hb: HostBatch, K=10000, nsl=False, **hooks):
 
 
 def kernel_ids():
-    """{"KN_...": id} of the pipeline's kernel enum (aasm_pipeline.h)."""
-    src = open(os.path.join(ROOT, "alignasm_amd", "csrc", "aasm_pipeline.h")).read()
-    body = re.search(r"enum Kern \{(.*?)\};", src, re.S).group(1)
-    return {name: i for i, name in enumerate(re.findall(r"\b(KN_\w+)", body))}
+    """{"KN_...": id} of the pipeline's kernels (the emulation library's names, from the kernel table in aasm_pipeline.h)."""
+    ids = {}
+    while (name := emul().emul_kernel_name(len(ids))) is not None:
+        ids[name.decode()] = len(ids)
+    return ids
 
 
 def emul_launches():

@@ -17,6 +17,18 @@
 using namespace aasm;
 
 namespace {
+alignas(16) char g_lds[65536];                    // the LDS of every emulated block
+#define K(...)
+#define KL(id, sym, block, lanes, lds, ...) static_assert((lds) <= sizeof(g_lds), #sym ": LDS beyond the emulation's buffer");
+AASM_PIPELINE_KERNELS(K, KL)
+#undef K
+#undef KL
+// a launch on the host: its blocks one after the other, in each `lanes` threads one after the other
+template <class Body> void emulate(int64_t nblocks, int lanes, Body body) {
+    for (int64_t b = 0; b < nblocks; b++)
+        for (int t = 0; t < lanes; t++) body(KCtx{t, lanes, b, nblocks, 0, g_lds});
+}
+
 struct EmuBackend {
     static constexpr bool host_emulation = true;
     std::vector<void *> blocks;
@@ -38,30 +50,25 @@ struct EmuBackend {
     void zero_alloc(void *p, size_t n) { memset(p, 0, n); }
     void fill_ff(void *p, size_t n) { memset(p, 0xFF, n); }
     void fill_byte(void *p, int v, size_t n) { memset(p, v, n); }
+    // nthreads: the table's block size (AASM_H2_LAUNCH_FAILURE's 4 096 is an invalid launch: logged, nothing runs)
     void launch(int kn, int64_t nblocks, int nthreads, const WS &w) {
         launches.insert(launches.end(), {kn, nblocks, nthreads});
-        if (nthreads > 1024) return;                // (the injected bad launch of the GPU tests: nothing to emulate)
-        for (int64_t b = 0; b < nblocks; b++) {
-            // one logical thread per block slot: bodies index with bid*nthreads+tid
-            for (int t = 0; t < (kn == KN_SORT ? 1 : nthreads_emul(kn, nthreads)); t++) {
-                alignas(16) static char lds[65536];
-                static_assert(65536 >= AASM_SORTFIX_LDS_BYTES && 65536 >= AASM_SORT_LDS_BYTES && 65536 >= AASM_ENUM_LDS_BYTES && 65536 >= AASM_GB_LDS_BYTES_T(GB_MAXV_L, GB_MAXE_L), "emulation LDS");
-                static_assert(AASM_SEL_LDS_BYTES <= AASM_SORT_LDS_BYTES && AASM_HEAP_LDS_BYTES <= AASM_SORT_LDS_BYTES && AASM_LDS_BYTES <= AASM_SORT_LDS_BYTES, "emulation LDS");
-                KCtx k{t, kn == KN_SORT ? 1 : nthreads_emul(kn, nthreads), b, nblocks, 0, lds};
-                run_kernel_body(kn, k, w);
-            }
-        }
-    }
-    // wave-per-X kernels run with ONE lane (AASM_WAVE == 1); thread-per-X kernels keep their block size
-    static int nthreads_emul(int kn, int nthreads) {
+        int lanes = 0;
         switch (kn) {
-            case KN_SORT_FIX: case KN_GATHER_PARTS: case KN_ROW_FILL: case KN_GRAPH: case KN_GRAPH_L: case KN_TNX16_WG: case KN_SORT_ROWS_REV: case KN_REV_FILL_W: case KN_REV_FILL_ORD: case KN_REV_FILL_ORD_S: case KN_SIDETRACK_W:
-            case KN_REV_SWEEP: case KN_FWD_SWEEP: case KN_REV_SWEEP_G: case KN_FWD_SWEEP_G: case KN_HEAP: case KN_HEAP_MW: case KN_HEAP_MW8: case KN_HEAP_MW16: case KN_ENUM: case KN_SELECT: case KN_GATHER_OUT: case KN_TOPO_FILL: case KN_SEL_RECOVER: case KN_SEL_CONVERT: case KN_SEL_FINAL: case KN_SEL_PLAN: case KN_SEL_PLANFILL:
-                return 1;
-            case KN_CHAIN3: return CHAIN_WAVES - 1;
-            case KN_CHAIN: return CHAIN_WAVES;          // one "thread" per wave, in wave order: the sweep runs to its end, then the pre-pass, then the heaps
-            default: return nthreads;
+#define K(id, sym, block, l, ...) case id: lanes = emul_lanes(nthreads, l); break;
+            AASM_PIPELINE_KERNELS(K, K)
+#undef K
         }
+        if (nthreads <= 1024) emulate(nblocks, lanes, [&](const KCtx &k) { run_kernel_body(kn, k, w); });
+    }
+    void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) {
+        int lanes = 0;
+        switch (kp) {
+#define K(id, sym, block, l, ...) case id: lanes = emul_lanes(nthreads, l); break;
+            AASM_PACK_KERNELS(K)
+#undef K
+        }
+        emulate(nblocks, lanes, [&](const KCtx &k) { run_pack_body(kp, k, a); });
     }
     void scan_i32(const int32_t *in, int64_t n, int64_t *out) { int64_t s = 0; for (int64_t i = 0; i < n; i++) { out[i] = s; s += in[i]; } out[n] = s; }
     void scan_i32_pair(const int32_t *a, int64_t *oa, const int32_t *b, int64_t *ob, int64_t n) { scan_i32(a, n, oa); scan_i32(b, n, ob); }
@@ -99,6 +106,15 @@ int emul_solve_batch(const aasm_batch_in *in, const aasm_opts *opts, aasm_batch_
     g_bad_record = sz.bad_record;
     if (rc != AASM_OK) return rc;
     return fetch_results(*g_be, g_ws, sz, out);
+}
+// the name of pipeline kernel `id` ("KN_..."), nullptr beyond the last
+const char *emul_kernel_name(int id) {
+    static const char *const names[] = {
+#define K(id, ...) #id,
+        AASM_PIPELINE_KERNELS(K, K)
+#undef K
+    };
+    return id >= 0 && id < (int)(sizeof(names) / sizeof(names[0])) ? names[id] : nullptr;
 }
 // the last solve's launch log: 3 int64 per launch (kernel id, blocks, threads); returns the launch count
 int64_t emul_launch_log(int64_t *dst, int64_t cap) {

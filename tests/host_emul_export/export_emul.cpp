@@ -6,24 +6,6 @@
 #include "../host_emul/emul.cpp"
 
 namespace {
-// the emulation backend plus the one launch the pack needs (threads of a block one after the other, as EmuBackend::launch)
-struct PackEmu {
-    EmuBackend &be;
-    void *alloc(const char *name, size_t n) { return be.alloc(name, n); }
-    bool failed() const { return be.failed(); }
-    bool oom() const { return be.oom(); }
-    void zero(void *p, size_t n) { be.zero(p, n); }
-    void fill_ff(void *p, size_t n) { be.fill_ff(p, n); }
-    void scan_i32(const int32_t *in, int64_t n, int64_t *out) { be.scan_i32(in, n, out); }
-    void read_i64s(std::initializer_list<const int64_t *> ps, int64_t *out) { be.read_i64s(ps, out); }
-    void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) {
-        for (int64_t b = 0; b < nblocks; b++)
-            for (int t = 0; t < nthreads; t++) {
-                KCtx k{t, nthreads, b, nblocks, 0, nullptr};
-                run_pack_body(kp, k, a);
-            }
-    }
-};
 PackWS g_pk;
 }  // namespace
 
@@ -38,10 +20,9 @@ int emx_solve_and_size(const aasm_batch_in *in, const aasm_opts *opts, int64_t *
     PipelineSizes ps;
     int rc = run_pipeline(*g_be, *in, o, g_ws, ps);
     if (rc != AASM_OK) return rc;
-    PackEmu pe{*g_be};
-    rc = pack_alloc(pe, g_ws, g_pk);
+    rc = pack_alloc(*g_be, g_ws, g_pk);
     if (rc != AASM_OK) return rc;
-    rc = pack_sizes(pe, g_ws, g_pk);
+    rc = pack_sizes(*g_be, g_ws, g_pk);
     if (rc != AASM_OK) return rc;
     for (int i = 0; i < 5; i++) sz[i] = g_pk.sizes[i];
     return AASM_OK;
@@ -60,8 +41,7 @@ int64_t emx_break_rank(int mode, int64_t *sz) {
             if (mode == 0) g_ws.ar_seq[q] = g_ws.ar_seq[r];
             else g_ws.ar_seq[r] = g_ws.all_seq[c] + 5;
             g_pk.sized = false;
-            PackEmu pe{*g_be};
-            if (pack_sizes(pe, g_ws, g_pk) != AASM_OK) return -1;
+            if (pack_sizes(*g_be, g_ws, g_pk) != AASM_OK) return -1;
             for (int i = 0; i < 5; i++) sz[i] = g_pk.sizes[i];
             return c;
         }
@@ -71,8 +51,7 @@ int64_t emx_break_rank(int mode, int64_t *sz) {
 // the export of the last solve into caller (host) arrays sized by emx_solve_and_size
 int emx_export(const aasm_dev_out *dst) {
     if (!g_be || !g_pk.sized) return AASM_E_INVAL;
-    PackEmu pe{*g_be};
-    pack_export(pe, g_ws, g_pk, *dst);
+    pack_export(*g_be, g_ws, g_pk, *dst);
     return g_be->failed() ? AASM_E_HIP : AASM_OK;
 }
 // fetch_results on the same workspace (release with emul_free_out)

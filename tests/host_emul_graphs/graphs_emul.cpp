@@ -29,25 +29,29 @@ struct GraphEmu {
     bool h2d(void *d, const void *h, size_t n) { memcpy(d, h, n); return true; }
     bool d2h(void *h, const void *d, size_t n) { memcpy(h, d, n); return true; }
     bool sync() { return true; }
-    bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
+    // the blocks of a launch one after the other, each with LDS of its own (poisoned: catches reads of never-written cells), and in
+    // each block `lanes` threads one after the other
+    template <class Body> static void emulate(int64_t g0, int64_t g1, int lanes, size_t lds_bytes, Body body) {
         for (int64_t b = g0; b < g1; b++) {
-            KCtx k{0, 1, b, g1 - g0, 0, nullptr};
-            switch (kid) {
-                case KSW_K_TREE: kb_ksw_tree(k, a); break;
-                case KSW_K_HEAP: kb_ksw_heap(k, a); break;
-                case KSW_K_ENUM: kb_ksw_enum(k, a); break;
-                case KSW_K_COUNT: kb_ksw_count(k, a); break;
-                default: kb_ksw_fill(k, a); break;
-            }
+            std::vector<char> lds(lds_bytes, (char)0xA5);
+            for (int t = 0; t < lanes; t++) body(KCtx{t, lanes, b, g1 - g0, 0, lds_bytes ? lds.data() : nullptr});
+        }
+    }
+    bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
+        switch (kid) {
+#define K(id, sym, block, lanes, ...) case id: emulate(g0, g1, emul_lanes(block, lanes), 0, [&](const KCtx &k) { __VA_ARGS__(k, a); }); break;
+            AASM_KSW_KERNELS(K)
+#undef K
         }
         return true;
     }
     bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
-        for (int64_t b = 0; b < n_graphs; b++) {
-            std::vector<char> lds(sizeof(DialLds), (char)0xA5);     // a block's LDS, poisoned
-            KCtx k{0, 1, b, n_graphs, 0, lds.data()};
-            if (kid == SSSP_K_DIJKSTRA) kb_sssp_dijkstra(k, a);
-            else kb_sssp_dial(k, a);
+        switch (kid) {
+#define KL(id, sym, block, lanes, lds, ...) case id: emulate(0, n_graphs, emul_lanes(block, lanes), lds, [&](const KCtx &k) { __VA_ARGS__(k, a); }); break;
+#define K(id, sym, block, lanes, ...) KL(id, sym, block, lanes, 0, __VA_ARGS__)
+            AASM_SSSP_KERNELS(K, KL)
+#undef K
+#undef KL
         }
         return true;
     }
