@@ -129,249 +129,6 @@ std::string cs_error_message(const char *cs, int64_t cs_len, bool aln_fwd, int64
     return cs_err_text(cs_diagnose(cs, cs_len, aln_fwd, qry_str, qry_end, ref_str, ref_end));
 }
 
-static int64_t fast_ranges(const char *p, const char *e, bool fwd, int64_t qs, int64_t qe, int64_t rs, int64_t re, int64_t *ql, int64_t *qr, int64_t *rl);
-
-// get_overlap_range into growing vectors (serial reader, --alt rows, aasm_cs_match_ranges); returns the count or -1 + message
-template <class VEC>
-static int64_t match_ranges(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end,
-                            int64_t ref_str, int64_t ref_end, VEC *ql, VEC *qr, VEC *rl, std::string &err) {
-    int64_t colons = 0, n = -1;
-    for (int64_t i = 5; i < cs_len; i++) colons += cs[i] == ':';             // upper bound of the range count
-    if (cs_len >= 5 && std::memcmp(cs, "cs:Z:", 5) == 0) {
-        const size_t base = ql ? ql->size() : 0;
-        std::vector<int64_t> tmp;
-        int64_t *a, *b, *c;
-        if (ql) { ql->resize(base + colons); qr->resize(base + colons); rl->resize(base + colons); a = ql->data() + base; b = qr->data() + base; c = rl->data() + base; }
-        else { tmp.resize(3 * (size_t)colons + 3); a = tmp.data(); b = a + colons + 1; c = b + colons + 1; }
-        n = fast_ranges(cs + 5, cs + cs_len, aln_fwd, qry_str, qry_end, ref_str, ref_end, a, b, c);
-        if (ql) { const size_t keep = base + (size_t)(n > 0 ? n : 0); ql->resize(keep); qr->resize(keep); rl->resize(keep); }
-    }
-    if (n < 0) { err = cs_err_text(cs_diagnose(cs, cs_len, aln_fwd, qry_str, qry_end, ref_str, ref_end)); return -1; }
-    return n;
-}
-
-struct Edit { std::string cs; int32_t mat_num, aln_len; bool is_cut; };
-
-// get_edited_paf_data (paf_data.cpp:125-220) in one pass over the tag: every operation is clipped
-// against the edited query interval [eq_s, eq_e] as it is met and what survives is rendered at once.
-static bool edit_cs(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end,
-                    int32_t mat_num, int32_t aln_len, int64_t eq_s, int64_t eq_e, int64_t er_s, int64_t er_e,
-                    Edit &out, std::string &err) {
-    if (eq_s == qry_str && eq_e == qry_end) {                                  // not cut: the record's own tag (:131-136)
-        out.cs.assign(cs, (size_t)cs_len);
-        out.mat_num = mat_num; out.aln_len = aln_len; out.is_cut = false;
-        return true;
-    }
-    out.cs.assign("cs:Z:"); out.mat_num = 0; out.aln_len = 0; out.is_cut = true;
-    CsCursor c(aln_fwd, qry_str, qry_end, 0, 0);
-    int64_t q_bases = 0, r_bases = 0;
-    bool ins_clipped = false;
-    char num[24];
-    const CsErr te = cs_scan(cs, cs_len, [&](char t, int64_t n, const char *text, int64_t text_len) {
-        if (t == '-') {                                                        // sits between query bases at() - 1 and at(): kept when both stay (:171-177)
-            if (eq_s < c.q && c.q <= eq_e) { out.cs.append(text, (size_t)text_len); r_bases += n; out.aln_len += (int32_t)n; }
-            return;
-        }
-        const int64_t lo = c.lo(n), hi = lo + n - 1;                           // the query bases this operation covers
-        const int64_t a = std::max(lo, eq_s), b = std::min(hi, eq_e);
-        c.take_q(n);
-        if (a > b) return;                                                     // entirely clipped away
-        if (t == ':') {                                                        // :144-152: the surviving part of the run
-            const int64_t keep = b - a + 1;
-            char *e = num + sizeof num, *p = e;
-            for (uint64_t u = (uint64_t)keep; ; u /= 10) { *--p = (char)('0' + u % 10); if (u < 10) break; }
-            *--p = ':';
-            out.cs.append(p, (size_t)(e - p));
-            out.mat_num += (int32_t)keep; out.aln_len += (int32_t)keep; q_bases += keep; r_bases += keep;
-        } else if (t == '+') {                                                 // :153-164: all of it or an error
-            if (a != lo || b != hi) { ins_clipped = true; return; }
-            out.cs.append(text, (size_t)text_len); q_bases += n; out.aln_len += (int32_t)n;
-        } else {                                                               // '*', :165-170
-            out.cs.append(text, (size_t)text_len); q_bases += 1; r_bases += 1; out.aln_len += 1;
-        }
-    });
-    CsErr e = te;
-    if (e == CS_OK && ins_clipped) e = CS_E_INS_CLIP;
-    if (e == CS_OK && (q_bases != eq_e - eq_s + 1 || r_bases != std::llabs(er_e - er_s) + 1)) e = CS_E_EDIT;   // :209-218
-    if (e != CS_OK) { err = cs_err_text(e); return false; }
-    return true;
-}
-
-// The writers' form of the same walk.  What a re-cut keeps is one stretch of the tag: query coverage is monotone along the
-// text, only the first and the last kept ':' run can lose bases (they are rendered anew), '*' '+' '-' operations stay or go
-// whole - so the row's tag is  [:head]  +  the kept operations as they stand (ONE copy)  +  [:tail], and the walk itself
-// only adds up numbers.  `irregular` (a kept run not written the way std::to_string writes it, e.g. ":007") sends the
-// row through edit_cs, which renders every operation.
-struct CutPlan { int64_t head_keep, tail_keep; const char *v0, *v1; int32_t mat_num, aln_len; bool irregular; };
-static CsErr plan_cut(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end, int64_t eq_s, int64_t eq_e,
-                      int64_t er_s, int64_t er_e, CutPlan &pl) {
-    pl.head_keep = pl.tail_keep = 0; pl.v0 = pl.v1 = nullptr; pl.mat_num = 0; pl.aln_len = 0; pl.irregular = false;
-    CsCursor c(aln_fwd, qry_str, qry_end, 0, 0);
-    int64_t q_bases = 0, r_bases = 0;
-    bool ins_clipped = false, any = false;
-    auto whole = [&](const char *text, int64_t text_len) {                     // an operation kept as it stands
-        if (pl.tail_keep) pl.irregular = true;                                 // (cannot happen: nothing is kept behind a shortened run)
-        if (!pl.v0) { pl.v0 = text; pl.v1 = text + text_len; }
-        else if (text == pl.v1) pl.v1 = text + text_len;
-        else pl.irregular = true;                                              // (cannot happen: the kept operations are neighbours)
-        any = true;
-    };
-    const CsErr te = cs_scan(cs, cs_len, [&](char t, int64_t n, const char *text, int64_t text_len) {
-        if (t == '-') {
-            if (eq_s < c.q && c.q <= eq_e) { whole(text, text_len); r_bases += n; pl.aln_len += (int32_t)n; }
-            return;
-        }
-        const int64_t lo = c.lo(n), hi = lo + n - 1;
-        const int64_t a = std::max(lo, eq_s), b = std::min(hi, eq_e);
-        c.take_q(n);
-        if (a > b) return;
-        if (t == ':') {
-            const int64_t keep = b - a + 1;
-            pl.mat_num += (int32_t)keep; pl.aln_len += (int32_t)keep; q_bases += keep; r_bases += keep;
-            if (keep == n) {
-                if (text[1] == '0') pl.irregular = true;                       // ":007" comes out as ":7"
-                whole(text, text_len);
-            } else if (!any) { pl.head_keep = keep; any = true; }
-            else if (!pl.tail_keep) pl.tail_keep = keep;
-            else pl.irregular = true;
-        } else if (t == '+') {
-            if (a != lo || b != hi) { ins_clipped = true; return; }
-            whole(text, text_len); q_bases += n; pl.aln_len += (int32_t)n;
-        } else { whole(text, text_len); q_bases += 1; r_bases += 1; pl.aln_len += 1; }
-    });
-    if (te != CS_OK) return te;
-    if (ins_clipped) return CS_E_INS_CLIP;
-    if (q_bases != eq_e - eq_s + 1 || r_bases != std::llabs(er_e - er_s) + 1) return CS_E_EDIT;
-    return CS_OK;
-}
-
-// ---- reader (alignasm.cpp:76-183) ---------------------------------------------------
-static bool parse_i64(std::string_view f, int64_t &v) {
-    if (f.empty()) return false;
-    char *endp = nullptr;
-    std::string tmp(f);
-    v = std::strtoll(tmp.c_str(), &endp, 10);
-    return endp && *endp == '\0';
-}
-
-static int parse_text(const char *text, int64_t len, aasm_paf &paf) {
-    std::unordered_map<std::string, int32_t> chr_map;
-    std::string ctg_chr;
-    std::vector<std::string_view> f;
-    int32_t row_global_index = 0;
-    paf.ctg_rec_off.assign(1, 0);
-    paf.cs_off.assign(1, 0);
-    paf.rec_rng_off.assign(1, 0);
-    int64_t p = 0;
-    while (p < len) {
-        const char *nl = (const char *)std::memchr(text + p, '\n', len - p);
-        int64_t e = nl ? (nl - text) : len;
-        int64_t le = e;
-        if (le > p && text[le - 1] == '\r') le--;
-        if (le > p) {
-            f.clear();
-            int64_t s = p;
-            for (int64_t i = p; i <= le; i++)
-                if (i == le || text[i] == '\t') { f.emplace_back(text + s, i - s); s = i + 1; }
-            if (f.size() < 12) { paf.error = "PAF row " + std::to_string(row_global_index) + " has fewer than 12 columns"; return AASM_E_PARSE; }
-            std::string qry_chr(f[0]), ref_chr(f[5]);
-            if (ctg_chr.empty()) ctg_chr = qry_chr;                    // :115-117
-            auto it = chr_map.find(ref_chr);
-            int32_t chr_id;
-            if (it == chr_map.end()) { chr_id = (int32_t)paf.chr_name.size(); chr_map.emplace(ref_chr, chr_id); paf.chr_name.push_back(ref_chr); }
-            else chr_id = it->second;
-            if (ctg_chr != qry_chr) {                                  // :125-133
-                paf.ctg_name.push_back(ctg_chr);
-                paf.ctg_rec_off.push_back(paf.n_records());
-                ctg_chr = qry_chr;
-            }
-            int64_t qtot, qs, qe, rtot, rs, re, mq, mat, aln;
-            if (!parse_i64(f[1], qtot) || !parse_i64(f[2], qs) || !parse_i64(f[3], qe) || !parse_i64(f[6], rtot) ||
-                !parse_i64(f[7], rs) || !parse_i64(f[8], re) || !parse_i64(f[9], mat) || !parse_i64(f[10], aln) ||
-                !parse_i64(f[11], mq)) {
-                paf.error = "PAF row " + std::to_string(row_global_index) + ": non-numeric field";
-                return AASM_E_PARSE;
-            }
-            qe--; re--;                                                // closed intervals, :141-151
-            bool fwd = !f[4].empty() && f[4][0] == '+';
-            if (!fwd) std::swap(rs, re);                               // :155-159
-            std::string_view cs;
-            for (size_t i = 12; i < f.size(); i++)                     // find_cs_tag, :100-108
-                if (f[i].size() >= 5 && f[i].substr(0, 5) == "cs:Z:") { cs = f[i]; break; }
-            if (cs.empty()) { paf.error = "Missing cs:Z tag in PAF record for query '" + qry_chr + "'"; return AASM_E_PARSE; }
-            std::string err;
-            int64_t nr = match_ranges(cs.data(), (int64_t)cs.size(), fwd, qs, qe, rs, re, &paf.rng_qry_l, &paf.rng_qry_r, &paf.rng_ref_l, err);
-            if (nr < 0) { paf.error = err + " (row " + std::to_string(row_global_index) + ")"; return AASM_E_PARSE; }
-            paf.rec_rng_off.push_back((int64_t)paf.rng_qry_l.size());
-            paf.qry_str.push_back(qs); paf.qry_end.push_back(qe); paf.ref_str.push_back(rs); paf.ref_end.push_back(re);
-            paf.qry_total.push_back(qtot); paf.ref_total.push_back(rtot);
-            paf.ref_chr.push_back(chr_id); paf.mat_num.push_back((int32_t)mat); paf.aln_len.push_back((int32_t)aln);
-            paf.row_index.push_back(row_global_index); paf.cord_type.push_back(0);
-            paf.aln_fwd.push_back(fwd ? 1 : 0); paf.map_qul.push_back((uint8_t)mq);
-            paf.cs_pool.insert(paf.cs_pool.end(), cs.data(), cs.data() + cs.size());
-            paf.cs_off.push_back((int64_t)paf.cs_pool.size());
-            row_global_index++;
-        }
-        p = e + 1;
-    }
-    if (paf.n_records() == 0) { paf.error = "empty PAF"; return AASM_E_PARSE; }
-    paf.ctg_name.push_back(ctg_chr);                                   // :180-181
-    paf.ctg_rec_off.push_back(paf.n_records());
-    return AASM_OK;
-}
-
-// ---- parallel reader -------------------------------------------------------------------
-// Same result as parse_text(), built for whole-genome files (GBs of cs text): the file is cut
-// at line boundaries into one chunk per host thread.  Pass 1 indexes every row (line start,
-// cs field) and counts its match ranges (= ':' operations), which fixes every offset in the
-// final arrays; pass 2 parses rows straight into those arrays with a fused cs scanner that
-// allocates nothing.  Anything the fast path does not recognise as a well-formed row sends the
-// whole file through parse_text(), which owns the error messages and the odd cases.
-static std::atomic<int> g_host_threads{0};
-// CPUs this process may really use: the machine's, cut to the affinity mask and to the cgroup's CPU quota (a container with
-// 16 CPUs' worth of quota on a 256-thread host: 64 busy threads there spend most of every period throttled)
-static int usable_cpus() {
-    int n = (int)std::thread::hardware_concurrency();
-    if (n <= 0) n = 1;
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) { const int a = CPU_COUNT(&set); if (a > 0 && a < n) n = a; }
-    auto quota = [&](const char *path, const char *path_period) {
-        FILE *f = std::fopen(path, "r");
-        if (!f) return;
-        char a[64] = {0};
-        long long q = -1, per = 100000;
-        if (path_period) {                                             // cgroup v1: two files
-            if (std::fscanf(f, "%lld", &q) != 1) q = -1;
-            FILE *g = std::fopen(path_period, "r");
-            if (g) { if (std::fscanf(g, "%lld", &per) != 1) per = 100000; std::fclose(g); }
-        } else if (std::fscanf(f, "%63s %lld", a, &per) == 2 && std::strcmp(a, "max") != 0) q = std::atoll(a);   // cgroup v2: "<quota|max> <period>"
-        std::fclose(f);
-        if (q > 0 && per > 0) { const int c = (int)((q + per - 1) / per); if (c > 0 && c < n) n = c; }
-    };
-    quota("/sys/fs/cgroup/cpu.max", nullptr);
-    quota("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "/sys/fs/cgroup/cpu/cpu.cfs_period_us");
-    return n;
-}
-int host_threads() {
-    int n = g_host_threads.load();
-    if (n <= 0) { static const int cpus = usable_cpus(); n = cpus; if (n > 64) n = 64; }
-    return n;
-}
-
-static inline bool fast_i64(const char *s, const char *e, int64_t &v) {       // [-]digits, <= 18 of them
-    bool neg = false;
-    if (s < e && *s == '-') { neg = true; s++; }
-    const int64_t n = e - s;
-    if (n <= 0 || n > 18) return false;
-    int64_t x = 0;
-    for (; s < e; s++) { const unsigned d = (unsigned)(*s - '0'); if (d > 9) return false; x = x * 10 + d; }
-    v = neg ? -x : x;
-    return true;
-}
-static inline bool field_i64(const char *s, const char *e, int64_t &v) {
-    return fast_i64(s, e, v) || parse_i64(std::string_view(s, (size_t)(e - s)), v);
-}
-
 // get_overlap_range (paf_data.cpp:90-123) fused with the tokenizer (:29-72): walks the cs text
 // once and writes the ranges in query order.  For a '-' strand row the reference visits the
 // operations last to first; walking them first to last from the query END gives the same
@@ -412,46 +169,286 @@ static int64_t fast_ranges(const char *p, const char *e, bool fwd, int64_t qs, i
     return n;
 }
 
-struct RowIdx { int64_t line, cs; int32_t line_len, cs_len, n_colon; };
+// get_overlap_range into fresh vectors (--alt rows, aasm_cs_match_ranges); returns the count or -1 + message
+static int64_t match_ranges(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end, int64_t ref_str,
+                            int64_t ref_end, std::vector<int64_t> &ql, std::vector<int64_t> &qr, std::vector<int64_t> &rl, std::string &err) {
+    int64_t n = -1;
+    if (cs_len >= 5 && std::memcmp(cs, "cs:Z:", 5) == 0) {
+        const size_t colons = (size_t)std::count(cs + 5, cs + cs_len, ':');        // upper bound of the range count
+        ql.resize(colons); qr.resize(colons); rl.resize(colons);
+        n = fast_ranges(cs + 5, cs + cs_len, aln_fwd, qry_str, qry_end, ref_str, ref_end, ql.data(), qr.data(), rl.data());
+        const size_t keep = (size_t)(n > 0 ? n : 0);
+        ql.resize(keep); qr.resize(keep); rl.resize(keep);
+    }
+    if (n < 0) { err = cs_err_text(cs_diagnose(cs, cs_len, aln_fwd, qry_str, qry_end, ref_str, ref_end)); return -1; }
+    return n;
+}
+
+static inline void put_i64(std::string &s, int64_t v) {
+    char buf[24];
+    char *e = buf + sizeof buf, *p = e;
+    uint64_t u = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    do { *--p = (char)('0' + u % 10); u /= 10; } while (u);
+    if (v < 0) *--p = '-';
+    s.append(p, (size_t)(e - p));
+}
+
+// get_edited_paf_data's walk (paf_data.cpp:137-218) in one pass over the tag: every operation is clipped against the edited
+// query interval [eq_s, eq_e] as it is met.  keep(type, kept, n, text, text_len) sees every operation that survives (kept:
+// the bases of a ':' run that stay, of n; n otherwise); mat_num / aln_len add up what is kept.
+template <class K>
+static CsErr cut_walk(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end, int64_t eq_s, int64_t eq_e,
+                      int64_t er_s, int64_t er_e, int32_t &mat_num, int32_t &aln_len, K &&keep) {
+    mat_num = 0; aln_len = 0;
+    CsCursor c(aln_fwd, qry_str, qry_end, 0, 0);
+    int64_t q_bases = 0, r_bases = 0;
+    bool ins_clipped = false;
+    const CsErr te = cs_scan(cs, cs_len, [&](char t, int64_t n, const char *text, int64_t text_len) {
+        if (t == '-') {                                                        // sits between query bases at() - 1 and at(): kept when both stay (:171-177)
+            if (eq_s < c.q && c.q <= eq_e) { keep(t, n, n, text, text_len); r_bases += n; aln_len += (int32_t)n; }
+            return;
+        }
+        const int64_t lo = c.lo(n), hi = lo + n - 1;                           // the query bases this operation covers
+        const int64_t a = std::max(lo, eq_s), b = std::min(hi, eq_e);
+        c.take_q(n);
+        if (a > b) return;                                                     // entirely clipped away
+        if (t == ':') {                                                        // :144-152: the surviving part of the run
+            const int64_t kept = b - a + 1;
+            keep(t, kept, n, text, text_len);
+            mat_num += (int32_t)kept; aln_len += (int32_t)kept; q_bases += kept; r_bases += kept;
+        } else if (t == '+') {                                                 // :153-164: all of it or an error
+            if (a != lo || b != hi) { ins_clipped = true; return; }
+            keep(t, n, n, text, text_len); q_bases += n; aln_len += (int32_t)n;
+        } else {                                                               // '*', :165-170
+            keep(t, 1, 1, text, text_len); q_bases += 1; r_bases += 1; aln_len += 1;
+        }
+    });
+    if (te != CS_OK) return te;
+    if (ins_clipped) return CS_E_INS_CLIP;
+    if (q_bases != eq_e - eq_s + 1 || r_bases != std::llabs(er_e - er_s) + 1) return CS_E_EDIT;   // :209-218
+    return CS_OK;
+}
+
+struct Edit { std::string cs; int32_t mat_num, aln_len; bool is_cut; };
+
+// get_edited_paf_data (paf_data.cpp:125-220): what survives the cut is rendered as it is met
+static bool edit_cs(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end,
+                    int32_t mat_num, int32_t aln_len, int64_t eq_s, int64_t eq_e, int64_t er_s, int64_t er_e,
+                    Edit &out, std::string &err) {
+    if (eq_s == qry_str && eq_e == qry_end) {                                  // not cut: the record's own tag (:131-136)
+        out.cs.assign(cs, (size_t)cs_len);
+        out.mat_num = mat_num; out.aln_len = aln_len; out.is_cut = false;
+        return true;
+    }
+    out.cs.assign("cs:Z:"); out.is_cut = true;
+    const CsErr e = cut_walk(cs, cs_len, aln_fwd, qry_str, qry_end, eq_s, eq_e, er_s, er_e, out.mat_num, out.aln_len,
+                             [&](char t, int64_t kept, int64_t, const char *text, int64_t text_len) {
+        if (t == ':') { out.cs += ':'; put_i64(out.cs, kept); }
+        else out.cs.append(text, (size_t)text_len);
+    });
+    if (e != CS_OK) { err = cs_err_text(e); return false; }
+    return true;
+}
+
+// The writers' form of the same walk.  What a re-cut keeps is one stretch of the tag: query coverage is monotone along the
+// text, only the first and the last kept ':' run can lose bases (they are rendered anew), '*' '+' '-' operations stay or go
+// whole - so the row's tag is  [:head]  +  the kept operations as they stand (ONE copy)  +  [:tail], and the walk itself
+// only adds up numbers.  `irregular` (a kept run not written the way std::to_string writes it, e.g. ":007") sends the
+// row through edit_cs, which renders every operation.
+struct CutPlan { int64_t head_keep, tail_keep; const char *v0, *v1; int32_t mat_num, aln_len; bool irregular; };
+static CsErr plan_cut(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end, int64_t eq_s, int64_t eq_e,
+                      int64_t er_s, int64_t er_e, CutPlan &pl) {
+    pl.head_keep = pl.tail_keep = 0; pl.v0 = pl.v1 = nullptr; pl.irregular = false;
+    bool any = false;
+    return cut_walk(cs, cs_len, aln_fwd, qry_str, qry_end, eq_s, eq_e, er_s, er_e, pl.mat_num, pl.aln_len,
+                    [&](char t, int64_t kept, int64_t n, const char *text, int64_t text_len) {
+        if (kept < n) {                                                        // a shortened ':' run: the first or the last one kept
+            if (!any) { pl.head_keep = kept; any = true; }
+            else if (!pl.tail_keep) pl.tail_keep = kept;
+            else pl.irregular = true;
+            return;
+        }
+        if (t == ':' && text[1] == '0') pl.irregular = true;                   // ":007" comes out as ":7"
+        if (pl.tail_keep) pl.irregular = true;                                 // (cannot happen: nothing is kept behind a shortened run)
+        if (!pl.v0) { pl.v0 = text; pl.v1 = text + text_len; }
+        else if (text == pl.v1) pl.v1 = text + text_len;
+        else pl.irregular = true;                                              // (cannot happen: the kept operations are neighbours)
+        any = true;
+    });
+}
+
+// ---- reader (alignasm.cpp:76-183) ---------------------------------------------------
+// One record of the container, its columns declared once (AASM_PAF_RECORD_COLUMNS).
+struct Rec {
+#define AASM_X(T, name) T name = 0;
+    AASM_PAF_RECORD_COLUMNS(AASM_X)
+#undef AASM_X
+};
+static void store_rec(aasm_paf &paf, int64_t g, const Rec &r) {
+#define AASM_X(T, name) paf.name[g] = r.name;
+    AASM_PAF_RECORD_COLUMNS(AASM_X)
+#undef AASM_X
+}
+static void append_rec(aasm_paf &paf, const Rec &r) {
+#define AASM_X(T, name) paf.name.push_back(r.name);
+    AASM_PAF_RECORD_COLUMNS(AASM_X)
+#undef AASM_X
+}
+static Rec rec_at(const aasm_paf &paf, int64_t g) {
+    Rec r;
+#define AASM_X(T, name) r.name = paf.name[g];
+    AASM_PAF_RECORD_COLUMNS(AASM_X)
+#undef AASM_X
+    return r;
+}
+
+static bool parse_i64(std::string_view f, int64_t &v) {
+    if (f.empty()) return false;
+    char *endp = nullptr;
+    std::string tmp(f);
+    v = std::strtoll(tmp.c_str(), &endp, 10);
+    return endp && *endp == '\0';
+}
+static inline bool fast_i64(const char *s, const char *e, int64_t &v) {       // [-]digits, <= 18 of them
+    bool neg = false;
+    if (s < e && *s == '-') { neg = true; s++; }
+    const int64_t n = e - s;
+    if (n <= 0 || n > 18) return false;
+    int64_t x = 0;
+    for (; s < e; s++) { const unsigned d = (unsigned)(*s - '0'); if (d > 9) return false; x = x * 10 + d; }
+    v = neg ? -x : x;
+    return true;
+}
+static inline bool field_i64(const char *s, const char *e, int64_t &v) {      // exactly what strtoll takes whole
+    return fast_i64(s, e, v) || parse_i64(std::string_view(s, (size_t)(e - s)), v);
+}
+
+// One PAF line as written (alignasm.cpp:100-159); the views point into the text.
+struct Row {
+    std::string_view qname, rname, cs;                 // cs: the first tag after the 12 columns that starts with cs:Z: (find_cs_tag, :100-108)
+    int64_t qtot, qs, qe, rtot, rs, re, mat, aln, mq;
+    bool fwd;
+};
+enum RowErr { ROW_OK = 0, ROW_COLUMNS, ROW_NUMBER, ROW_NO_CS, ROW_CS, ROW_LONG };
+
+// col[k] = first byte of column k of [s, e), for the first 13 columns; returns how many there are (<= 13).  The column
+// after the last one found "starts" at e + 1, so column k always ends at col[k + 1] - 1.
+static int split_columns(const char *s, const char *e, const char *col[13]) {
+    col[0] = s;
+    int n = 1;
+    for (; n < 13; n++) {
+        const char *t = (const char *)std::memchr(col[n - 1], '\t', (size_t)(e - col[n - 1]));
+        if (!t) break;
+        col[n] = t + 1;
+    }
+    if (n < 13) col[n] = e + 1;
+    return n;
+}
+static std::string_view find_cs(const char *f, const char *e) {                 // the first cs:Z: tag of the tags [f, e)
+    while (f < e) {
+        const char *t = (const char *)std::memchr(f, '\t', (size_t)(e - f));
+        const char *fe = t ? t : e;
+        if (fe - f >= 5 && std::memcmp(f, "cs:Z:", 5) == 0) return std::string_view(f, (size_t)(fe - f));
+        if (!t) break;
+        f = t + 1;
+    }
+    return {};
+}
+// one line without its line end; the checks in the reference's order: columns, numbers, the tag (names are set from ROW_NUMBER on)
+static RowErr parse_row(const char *s, const char *e, Row &w) {
+    const char *c[13];
+    const int n = split_columns(s, e, c);
+    if (n < 12) return ROW_COLUMNS;
+    w.qname = std::string_view(c[0], (size_t)(c[1] - 1 - c[0]));
+    w.rname = std::string_view(c[5], (size_t)(c[6] - 1 - c[5]));
+    if (!field_i64(c[1], c[2] - 1, w.qtot) || !field_i64(c[2], c[3] - 1, w.qs) || !field_i64(c[3], c[4] - 1, w.qe) ||
+        !field_i64(c[6], c[7] - 1, w.rtot) || !field_i64(c[7], c[8] - 1, w.rs) || !field_i64(c[8], c[9] - 1, w.re) ||
+        !field_i64(c[9], c[10] - 1, w.mat) || !field_i64(c[10], c[11] - 1, w.aln) || !field_i64(c[11], c[12] - 1, w.mq))
+        return ROW_NUMBER;
+    w.fwd = c[5] - 1 > c[4] && c[4][0] == '+';
+    w.cs = n == 13 ? find_cs(c[12], e) : std::string_view();
+    return w.cs.empty() ? ROW_NO_CS : ROW_OK;
+}
+// the record a row becomes: closed intervals, the reference span in query order (:141-159)
+static Rec record_of(const Row &w, int32_t chr, int32_t row, uint8_t type) {
+    Rec r;
+    r.qry_str = w.qs; r.qry_end = w.qe - 1; r.ref_str = w.rs; r.ref_end = w.re - 1;
+    if (!w.fwd) std::swap(r.ref_str, r.ref_end);
+    r.qry_total = w.qtot; r.ref_total = w.rtot; r.ref_chr = chr;
+    r.mat_num = (int32_t)w.mat; r.aln_len = (int32_t)w.aln; r.row_index = row;
+    r.aln_fwd = w.fwd ? 1 : 0; r.map_qul = (uint8_t)w.mq; r.cord_type = type;
+    return r;
+}
+
+// ---- parallel reader -------------------------------------------------------------------
+// Built for whole-genome files (GBs of cs text): the file is cut at line boundaries into one chunk per host thread.  Pass 1
+// indexes every row (line, match ranges = ':' operations), which fixes every offset in the final arrays; pass 2 parses rows
+// straight into those arrays with a fused cs scanner that allocates nothing.  A chunk stops at its first bad row and
+// records it; pass 1 drops every chunk behind the first one that stopped, so the rows pass 2 reads are exactly those before
+// the first row pass 1 rejects, and the error reported is the first in the file.
+static std::atomic<int> g_host_threads{0};
+// CPUs this process may really use: the machine's, cut to the affinity mask and to the cgroup's CPU quota (a container with
+// 16 CPUs' worth of quota on a 256-thread host: 64 busy threads there spend most of every period throttled)
+static int usable_cpus() {
+    int n = (int)std::thread::hardware_concurrency();
+    if (n <= 0) n = 1;
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof set, &set) == 0) { const int a = CPU_COUNT(&set); if (a > 0 && a < n) n = a; }
+    auto quota = [&](const char *path, const char *path_period) {
+        FILE *f = std::fopen(path, "r");
+        if (!f) return;
+        char a[64] = {0};
+        long long q = -1, per = 100000;
+        if (path_period) {                                             // cgroup v1: two files
+            if (std::fscanf(f, "%lld", &q) != 1) q = -1;
+            FILE *g = std::fopen(path_period, "r");
+            if (g) { if (std::fscanf(g, "%lld", &per) != 1) per = 100000; std::fclose(g); }
+        } else if (std::fscanf(f, "%63s %lld", a, &per) == 2 && std::strcmp(a, "max") != 0) q = std::atoll(a);   // cgroup v2: "<quota|max> <period>"
+        std::fclose(f);
+        if (q > 0 && per > 0) { const int c = (int)((q + per - 1) / per); if (c > 0 && c < n) n = c; }
+    };
+    quota("/sys/fs/cgroup/cpu.max", nullptr);
+    quota("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "/sys/fs/cgroup/cpu/cpu.cfs_period_us");
+    return n;
+}
+int host_threads() {
+    int n = g_host_threads.load();
+    if (n <= 0) { static const int cpus = usable_cpus(); n = cpus; if (n > 64) n = 64; }
+    return n;
+}
+
+struct RowIdx { int64_t line; int32_t line_len, n_colon; };
+struct RowFault { RowErr kind = ROW_OK; CsErr cs = CS_OK; int64_t row = 0; std::string_view qname; };   // row: index inside the chunk
 struct ReadChunk {
     int64_t b = 0, e = 0;                      // byte range (whole lines)
     std::vector<RowIdx> rows;
     int64_t n_ranges = 0, cs_bytes = 0;
-    bool bad = false;
+    RowFault fault;                            // the chunk's first bad row
     // pass 2
     std::vector<std::string_view> chr_names;   // first-appearance order inside the chunk
     std::vector<std::pair<std::string_view, int64_t>> runs;   // (query name, first global row) of each run of equal names
 };
 
 static void read_pass1(const char *text, ReadChunk &ck) {
-    int64_t p = ck.b;
-    while (p < ck.e) {
+    for (int64_t p = ck.b; p < ck.e;) {
         const char *nl = (const char *)std::memchr(text + p, '\n', (size_t)(ck.e - p));
         const int64_t e = nl ? (nl - text) : ck.e;
         int64_t le = e;
         if (le > p && text[le - 1] == '\r') le--;
         if (le > p) {
-            // the 12 mandatory columns, then the first tag that starts with cs:Z: (find_cs_tag, alignasm.cpp:100-108)
-            const char *f = text + p, *end = text + le;
-            int nf = 0;
-            while (nf < 12) { const char *t = (const char *)std::memchr(f, '\t', (size_t)(end - f)); if (!t) break; f = t + 1; nf++; }
-            const char *cs = nullptr, *cs_end = nullptr;
-            if (nf == 12) {
-                while (f < end) {
-                    const char *t = (const char *)std::memchr(f, '\t', (size_t)(end - f));
-                    const char *fe = t ? t : end;
-                    if (fe - f >= 5 && std::memcmp(f, "cs:Z:", 5) == 0) { cs = f; cs_end = fe; break; }
-                    if (!t) break;
-                    f = t + 1;
-                }
+            const char *c[13];
+            std::string_view cs;
+            if (le - p > INT32_MAX) ck.fault.kind = ROW_LONG;
+            else if (split_columns(text + p, text + le, c) < 13 || (cs = find_cs(c[12], text + le)).empty()) {
+                Row w;                                                 // not a row: what the parser says is wrong with it
+                ck.fault.kind = parse_row(text + p, text + le, w);
+                ck.fault.qname = w.qname;
             }
-            if (!cs || le - p > INT32_MAX) { ck.bad = true; return; }
-            int64_t colons = 0;
-            for (const char *c = cs + 5; c < cs_end; c++) colons += (*c == ':');
-            if (colons > INT32_MAX) { ck.bad = true; return; }
-            ck.rows.push_back(RowIdx{p, (int64_t)(cs - text), (int32_t)(le - p), (int32_t)(cs_end - cs), (int32_t)colons});
+            if (ck.fault.kind != ROW_OK) { ck.fault.row = (int64_t)ck.rows.size(); return; }
+            const int64_t colons = std::count(cs.data() + 5, cs.data() + cs.size(), ':');
+            ck.rows.push_back(RowIdx{p, (int32_t)(le - p), (int32_t)colons});
             ck.n_ranges += colons;
-            ck.cs_bytes += cs_end - cs;
+            ck.cs_bytes += (int64_t)cs.size();
         }
         p = e + 1;
     }
@@ -467,45 +464,34 @@ static void read_pass2(const char *text, ReadChunk &ck, aasm_paf &paf, int64_t r
     for (size_t i = 0; i < ck.rows.size(); i++) {
         const RowIdx &ri = ck.rows[i];
         const int64_t g = row0 + (int64_t)i;
-        const char *f[13];
-        const char *c = text + ri.line, *end = c + ri.line_len;
-        f[0] = c;
-        for (int k = 1; k <= 12; k++) { c = (const char *)std::memchr(c, '\t', (size_t)(end - c)) + 1; f[k] = c; }   // pass 1 saw 12 tabs
-        int64_t qtot, qs, qe, rtot, rs, re, mq, mat, aln;
-        if (!field_i64(f[1], f[2] - 1, qtot) || !field_i64(f[2], f[3] - 1, qs) || !field_i64(f[3], f[4] - 1, qe) ||
-            !field_i64(f[6], f[7] - 1, rtot) || !field_i64(f[7], f[8] - 1, rs) || !field_i64(f[8], f[9] - 1, re) ||
-            !field_i64(f[9], f[10] - 1, mat) || !field_i64(f[10], f[11] - 1, aln) || !field_i64(f[11], f[12] - 1, mq)) { ck.bad = true; return; }
-        qe--; re--;                                                    // closed intervals, :141-151
-        const bool fwd = f[5] - 1 > f[4] && f[4][0] == '+';
-        if (!fwd) std::swap(rs, re);                                   // :155-159
-        const std::string_view qname(f[0], (size_t)(f[1] - 1 - f[0])), rname(f[5], (size_t)(f[6] - 1 - f[5]));
-        if (!have_ctg || qname != cur_ctg) { ck.runs.emplace_back(qname, g); cur_ctg = qname; have_ctg = true; }   // :125-133
+        Row w;
+        const RowErr k = parse_row(text + ri.line, text + ri.line + ri.line_len, w);   // pass 1 found the columns and the tag: ROW_NUMBER at most
+        if (k != ROW_OK) { ck.fault = RowFault{k, CS_OK, (int64_t)i, w.qname}; return; }
+        if (!have_ctg || w.qname != cur_ctg) { ck.runs.emplace_back(w.qname, g); cur_ctg = w.qname; have_ctg = true; }   // :125-133
         int32_t chr_id;
-        if (last_chr_id >= 0 && rname == last_chr) chr_id = last_chr_id;
+        if (last_chr_id >= 0 && w.rname == last_chr) chr_id = last_chr_id;
         else {
-            auto it = chr_map.find(rname);
-            if (it == chr_map.end()) { chr_id = (int32_t)ck.chr_names.size(); chr_map.emplace(rname, chr_id); ck.chr_names.push_back(rname); }
+            auto it = chr_map.find(w.rname);
+            if (it == chr_map.end()) { chr_id = (int32_t)ck.chr_names.size(); chr_map.emplace(w.rname, chr_id); ck.chr_names.push_back(w.rname); }
             else chr_id = it->second;
-            last_chr = rname; last_chr_id = chr_id;
+            last_chr = w.rname; last_chr_id = chr_id;
         }
-        const char *cs = text + ri.cs;
+        const Rec r = record_of(w, chr_id, (int32_t)g, 0);           // ref_chr: chunk-local id, remapped after the join
+        const char *cs = w.cs.data();
         if (paf.device_ranges) ro += ri.n_colon;                       // the GPU parses (and validates) the tag
         else {
-            const int64_t nr = fast_ranges(cs + 5, cs + ri.cs_len, fwd, qs, qe, rs, re, QL + ro, QR + ro, RL + ro);
-            if (nr < 0) { ck.bad = true; return; }
+            const int64_t nr = fast_ranges(cs + 5, cs + w.cs.size(), w.fwd, r.qry_str, r.qry_end, r.ref_str, r.ref_end, QL + ro, QR + ro, RL + ro);
+            if (nr < 0) {
+                ck.fault = RowFault{ROW_CS, cs_diagnose(cs, (int64_t)w.cs.size(), w.fwd, r.qry_str, r.qry_end, r.ref_str, r.ref_end), (int64_t)i, w.qname};
+                return;
+            }
             ro += nr;
         }
-        std::memcpy(paf.cs_pool.data() + co, cs, (size_t)ri.cs_len);
-        co += ri.cs_len;
-        paf.qry_str[g] = qs; paf.qry_end[g] = qe; paf.ref_str[g] = rs; paf.ref_end[g] = re;
-        paf.qry_total[g] = qtot; paf.ref_total[g] = rtot;
-        paf.ref_chr[g] = chr_id;                                       // chunk-local id, remapped after the join
-        paf.mat_num[g] = (int32_t)mat; paf.aln_len[g] = (int32_t)aln;
-        paf.row_index[g] = (int32_t)g; paf.cord_type[g] = 0;
-        paf.aln_fwd[g] = fwd ? 1 : 0; paf.map_qul[g] = (uint8_t)mq;
+        std::memcpy(paf.cs_pool.data() + co, cs, w.cs.size());
+        co += (int64_t)w.cs.size();
+        store_rec(paf, g, r);
         paf.rec_rng_off[g + 1] = ro; paf.cs_off[g + 1] = co;
     }
-    if (ro != rng0 + ck.n_ranges) ck.bad = true;                       // a ':' that was not an operation
 }
 
 template <class F> static void run_threads(int n, F fn) {
@@ -513,6 +499,18 @@ template <class F> static void run_threads(int n, F fn) {
     for (int t = 1; t < n; t++) th.emplace_back(fn, t);
     fn(0);
     for (auto &x : th) x.join();
+}
+
+static std::string fault_message(const RowFault &f, int64_t row) {
+    const std::string n = std::to_string(row);
+    switch (f.kind) {
+        case ROW_COLUMNS: return "PAF row " + n + " has fewer than 12 columns";
+        case ROW_NUMBER: return "PAF row " + n + ": non-numeric field";
+        case ROW_NO_CS: return "Missing cs:Z tag in PAF record for query '" + std::string(f.qname) + "'";
+        case ROW_CS: return std::string(cs_err_text(f.cs)) + " (row " + n + ")";
+        case ROW_LONG: return "PAF row " + n + " is longer than 2147483647 bytes";
+        default: return "";
+    }
 }
 
 static int parse_text_mt(const char *text, int64_t len, aasm_paf &paf, int flags) {
@@ -531,34 +529,46 @@ static int parse_text_mt(const char *text, int64_t len, aasm_paf &paf, int flags
     const auto tr0 = std::chrono::steady_clock::now();
     run_threads(T, [&](int t) { read_pass1(text, ck[t]); });
     const auto tr1 = std::chrono::steady_clock::now();
-    std::vector<int64_t> row0(T + 1, 0), rng0(T + 1, 0), cs0(T + 1, 0);
-    bool bad = false;
-    for (int t = 0; t < T; t++) {
-        bad |= ck[t].bad;
+    int TP = 0;                                                        // chunks pass 2 reads: up to the first that pass 1 stopped in
+    while (TP < T && ck[TP++].fault.kind == ROW_OK) {}
+    std::vector<int64_t> row0(TP + 1, 0), rng0(TP + 1, 0), cs0(TP + 1, 0);
+    for (int t = 0; t < TP; t++) {
         row0[t + 1] = row0[t] + (int64_t)ck[t].rows.size(); rng0[t + 1] = rng0[t] + ck[t].n_ranges; cs0[t + 1] = cs0[t] + ck[t].cs_bytes;
     }
-    const int64_t R = row0[T];
-    if (bad || R == 0 || R > INT32_MAX) return parse_text(text, len, paf);   // errors / empty input: the serial reader reports
-    {   // sixteen arrays to size (the per-record ones are zero-filled by resize: 0.4 GB at whole-genome scale): one thread each
+    const int64_t R = row0[TP];
+    if (R > INT32_MAX) { paf.error = "PAF has more than 2147483647 rows"; return AASM_E_PARSE; }   // (row_index is 32-bit)
+    {   // the arrays to size (the per-record ones are zero-filled by resize: 0.4 GB at whole-genome scale): one thread each
         const std::vector<std::function<void()>> jobs = {
-            [&] { paf.qry_str.resize(R); }, [&] { paf.qry_end.resize(R); }, [&] { paf.ref_str.resize(R); }, [&] { paf.ref_end.resize(R); },
-            [&] { paf.qry_total.resize(R); }, [&] { paf.ref_total.resize(R); }, [&] { paf.ref_chr.resize(R); }, [&] { paf.mat_num.resize(R); },
-            [&] { paf.aln_len.resize(R); }, [&] { paf.row_index.resize(R); }, [&] { paf.aln_fwd.resize(R); paf.map_qul.resize(R); paf.cord_type.resize(R); },
+#define AASM_X(T_, name) [&] { paf.name.resize(R); },
+            AASM_PAF_RECORD_COLUMNS(AASM_X)
+#undef AASM_X
             [&] { paf.cs_off.resize(R + 1); }, [&] { paf.rec_rng_off.resize(R + 1); },
-            [&] { if (!paf.device_ranges) { paf.rng_qry_l.resize(rng0[T]); paf.rng_qry_r.resize(rng0[T]); paf.rng_ref_l.resize(rng0[T]); } },
-            [&] { paf.cs_pool.resize(cs0[T]); }};
+            [&] { if (!paf.device_ranges) { paf.rng_qry_l.resize(rng0[TP]); paf.rng_qry_r.resize(rng0[TP]); paf.rng_ref_l.resize(rng0[TP]); } },
+            [&] { paf.cs_pool.resize(cs0[TP]); }};
         const int J = (int)jobs.size(), TJ = std::min(T, J);
         run_threads(TJ, [&](int t) { for (int j = t; j < J; j += TJ) jobs[j](); });
     }
     paf.cs_off[0] = 0; paf.rec_rng_off[0] = 0;
     const auto tr2 = std::chrono::steady_clock::now();
-    run_threads(T, [&](int t) { read_pass2(text, ck[t], paf, row0[t], rng0[t], cs0[t]); });
+    run_threads(TP, [&](int t) { read_pass2(text, ck[t], paf, row0[t], rng0[t], cs0[t]); });
     const auto tr3 = std::chrono::steady_clock::now();
     if (std::getenv("AASM_IO_TIMING"))
         std::fprintf(stderr, "aasm io: reader %d threads: index %.3f s, allocate %.3f s, parse + copy %.3f s (%.1f MB)\n", T, std::chrono::duration<double>(tr1 - tr0).count(),
                      std::chrono::duration<double>(tr2 - tr1).count(), std::chrono::duration<double>(tr3 - tr2).count(), len / 1e6);
-    for (int t = 0; t < T; t++) bad |= ck[t].bad;
-    if (bad) { paf = aasm_paf(); return parse_text(text, len, paf); }            // (host ranges: parse_text builds them)
+    for (int t = 0; t < TP; t++) {
+        if (ck[t].fault.kind == ROW_OK) continue;
+        RowFault f = ck[t].fault;
+        int64_t row = row0[t] + f.row;
+        if (paf.device_ranges)                                         // a bad file: the tags before the bad row are checked too, and the first bad one is the error (row order)
+            for (int64_t g = 0; g < row; g++) {
+                const CsErr e = cs_diagnose(paf.cs_pool.data() + paf.cs_off[g], paf.cs_off[g + 1] - paf.cs_off[g], paf.aln_fwd[g] != 0,
+                                            paf.qry_str[g], paf.qry_end[g], paf.ref_str[g], paf.ref_end[g]);
+                if (e != CS_OK) { f = RowFault{ROW_CS, e, 0, {}}; row = g; break; }
+            }
+        paf.error = fault_message(f, row);
+        return AASM_E_PARSE;
+    }
+    if (R == 0) { paf.error = "empty PAF"; return AASM_E_PARSE; }
     // reference names numbered by first appearance in the file (chr_map, :119-123)
     std::unordered_map<std::string_view, int32_t> chr_map;
     std::vector<std::vector<int32_t>> remap((size_t)T);
@@ -595,9 +605,7 @@ static int parse_text_mt(const char *text, int64_t len, aasm_paf &paf, int flags
 //      own, unless a zeroed record is the last one at that moment.  The reference appends a piece's stand-in record only
 //      when the NEXT piece's first row has been read (:305-306 after :269), so that row never sees it.
 struct AltRec {
-    int64_t qs = 0, qe = 0, rs = 0, re = 0, qtot = 0, rtot = 0;
-    int32_t chr = 0, mat = 0, aln = 0, row = 0;
-    uint8_t fwd = 0, mq = 0, type = 0;             // type: TYPE_ALT for a real row, TYPE_MAIN (0) for the zeroed record
+    Rec rec;                                       // cord_type: TYPE_ALT for a real row, TYPE_MAIN (0) for the zeroed record
     std::string cs;
     std::vector<int64_t> ql, qr, rl;
     int32_t ctg = 0;                               // contig the piece name resolves to (unknown names: 0, operator[] at :269)
@@ -621,7 +629,6 @@ static bool split_piece_name(std::string_view q, std::string_view &name, int64_t
 
 static int scan_alt_rows(const char *text, int64_t len, aasm_paf &paf, std::unordered_map<std::string, int32_t> &chr_map,
                          const std::unordered_map<std::string_view, int32_t> &ctg_of, std::vector<AltRec> &rows) {
-    std::vector<std::string_view> f;
     for (int64_t p = 0; p < len;) {
         const char *nl = (const char *)std::memchr(text + p, '\n', len - p);
         const int64_t e = nl ? (nl - text) : len;
@@ -630,39 +637,25 @@ static int scan_alt_rows(const char *text, int64_t len, aasm_paf &paf, std::unor
         const int64_t b = p;
         p = e + 1;
         if (le == b) continue;
-        f.clear();
-        for (int64_t i = b, st = b; i <= le; i++)
-            if (i == le || text[i] == '\t') { f.emplace_back(text + st, i - st); st = i + 1; }
         const int32_t row = (int32_t)rows.size();
-        if (f.size() < 12) { paf.error = "alt PAF row " + std::to_string(row) + " has fewer than 12 columns"; return AASM_E_PARSE; }
+        Row w;
+        const RowErr k = parse_row(text + b, text + le, w);
+        if (k == ROW_COLUMNS) { paf.error = "alt PAF row " + std::to_string(row) + " has fewer than 12 columns"; return AASM_E_PARSE; }
         AltRec r;
-        r.row = row; r.type = 1;
-        std::string ref_name(f[5]);
+        std::string ref_name(w.rname);
         auto ci = chr_map.find(ref_name);
         if (ci == chr_map.end()) { ci = chr_map.emplace(ref_name, (int32_t)paf.chr_name.size()).first; paf.chr_name.push_back(ref_name); }
-        r.chr = ci->second;
-        if (!split_piece_name(f[0], r.piece, r.shift, paf.error)) return AASM_E_PARSE;
+        if (!split_piece_name(w.qname, r.piece, r.shift, paf.error)) return AASM_E_PARSE;
         auto ct = ctg_of.find(r.piece);
         r.ctg = ct == ctg_of.end() ? 0 : ct->second;
-        int64_t piece_len, qs, qe, re, mq, mat, aln;
-        if (!parse_i64(f[1], piece_len) || !parse_i64(f[2], qs) || !parse_i64(f[3], qe) || !parse_i64(f[6], r.rtot) ||
-            !parse_i64(f[7], r.rs) || !parse_i64(f[8], re) || !parse_i64(f[9], mat) || !parse_i64(f[10], aln) || !parse_i64(f[11], mq)) {
-            paf.error = "alt PAF row " + std::to_string(row) + ": non-numeric field";
-            return AASM_E_PARSE;
-        }
-        r.qs = qs + r.shift; r.qe = qe + r.shift - 1;                               // closed interval in contig coordinates (:275-277)
-        r.re = re - 1;
-        r.fwd = (!f[4].empty() && f[4][0] == '+') ? 1 : 0;
-        if (!r.fwd) std::swap(r.rs, r.re);
-        r.mq = (uint8_t)mq; r.mat = (int32_t)mat; r.aln = (int32_t)aln;
-        r.ratio = (double)aln / (double)piece_len;
-        std::string_view cs;
-        for (size_t i = 12; i < f.size() && cs.empty(); i++)
-            if (f[i].substr(0, 5) == "cs:Z:") cs = f[i];
-        if (cs.empty()) { paf.error = "Missing cs:Z tag in alternative PAF record for query '" + std::string(f[0]) + "'"; return AASM_E_PARSE; }
-        r.cs.assign(cs.data(), cs.size());
+        if (k == ROW_NUMBER) { paf.error = "alt PAF row " + std::to_string(row) + ": non-numeric field"; return AASM_E_PARSE; }
+        if (k == ROW_NO_CS) { paf.error = "Missing cs:Z tag in alternative PAF record for query '" + std::string(w.qname) + "'"; return AASM_E_PARSE; }
+        r.rec = record_of(w, ci->second, row, 1);                                   // TYPE_ALT (:302)
+        r.rec.qry_str += r.shift; r.rec.qry_end += r.shift;                         // closed interval in contig coordinates (:275-277)
+        r.ratio = (double)w.aln / (double)w.qtot;
+        r.cs.assign(w.cs.data(), w.cs.size());
         std::string err;
-        if (match_ranges(cs.data(), (int64_t)cs.size(), r.fwd != 0, r.qs, r.qe, r.rs, r.re, &r.ql, &r.qr, &r.rl, err) < 0) {
+        if (match_ranges(w.cs.data(), (int64_t)w.cs.size(), w.fwd, r.rec.qry_str, r.rec.qry_end, r.rec.ref_str, r.rec.ref_end, r.ql, r.qr, r.rl, err) < 0) {
             paf.error = err + " (alt row " + std::to_string(row) + ")";
             return AASM_E_PARSE;
         }
@@ -693,16 +686,16 @@ static int merge_alt_text(const char *text, int64_t len, double baseline, aasm_p
         const int32_t c = rows[g0].ctg;
         size_t over = 0, top = g1;                                                  // rows above the baseline; first row of the largest positive ratio
         for (size_t i = g0; i < g1; i++) {
-            rows[i].qtot = qtot_now[c];
+            rows[i].rec.qry_total = qtot_now[c];
             if (i == g0 && pend_c >= 0) { qtot_now[pend_c] = pend_qtot; pend_c = -1; }
-            if (rows[i].ratio > baseline) { over++; qtot_now[c] = rows[i].qtot; }
+            if (rows[i].ratio > baseline) { over++; qtot_now[c] = rows[i].rec.qry_total; }
             if (rows[i].ratio > (top == g1 ? 0.0 : rows[top].ratio)) top = i;
         }
         if (over) {
             for (size_t i = g0; i < g1; i++)
                 if (rows[i].ratio > baseline) added[c].push_back(std::move(rows[i]));
         } else if (top != g1) {
-            pend_c = c; pend_qtot = rows[top].qtot;
+            pend_c = c; pend_qtot = rows[top].rec.qry_total;
             added[c].push_back(std::move(rows[top]));
         } else {
             added[c].emplace_back();                                                // every ratio <= 0: the zeroed record
@@ -715,10 +708,7 @@ static int merge_alt_text(const char *text, int64_t len, double baseline, aasm_p
     n.ctg_rec_off.assign(1, 0); n.cs_off.assign(1, 0); n.rec_rng_off.assign(1, 0);
     for (int64_t c = 0; c < C; c++) {
         for (int64_t r = paf.ctg_rec_off[c]; r < paf.ctg_rec_off[c + 1]; r++) {
-            n.qry_str.push_back(paf.qry_str[r]); n.qry_end.push_back(paf.qry_end[r]); n.ref_str.push_back(paf.ref_str[r]); n.ref_end.push_back(paf.ref_end[r]);
-            n.qry_total.push_back(paf.qry_total[r]); n.ref_total.push_back(paf.ref_total[r]); n.ref_chr.push_back(paf.ref_chr[r]);
-            n.mat_num.push_back(paf.mat_num[r]); n.aln_len.push_back(paf.aln_len[r]); n.row_index.push_back(paf.row_index[r]);
-            n.cord_type.push_back(paf.cord_type[r]); n.aln_fwd.push_back(paf.aln_fwd[r]); n.map_qul.push_back(paf.map_qul[r]);
+            append_rec(n, rec_at(paf, r));
             n.cs_pool.insert(n.cs_pool.end(), paf.cs_pool.data() + paf.cs_off[r], paf.cs_pool.data() + paf.cs_off[r + 1]);
             n.cs_off.push_back((int64_t)n.cs_pool.size());
             if (!paf.device_ranges)
@@ -726,10 +716,7 @@ static int merge_alt_text(const char *text, int64_t len, double baseline, aasm_p
             n.rec_rng_off.push_back(n.rec_rng_off.back() + (paf.rec_rng_off[r + 1] - paf.rec_rng_off[r]));
         }
         for (const AltRec &a : added[c]) {
-            n.qry_str.push_back(a.qs); n.qry_end.push_back(a.qe); n.ref_str.push_back(a.rs); n.ref_end.push_back(a.re);
-            n.qry_total.push_back(a.qtot); n.ref_total.push_back(a.rtot); n.ref_chr.push_back(a.chr);
-            n.mat_num.push_back(a.mat); n.aln_len.push_back(a.aln); n.row_index.push_back(a.row);
-            n.cord_type.push_back(a.type); n.aln_fwd.push_back(a.fwd); n.map_qul.push_back(a.mq);   // TYPE_ALT (:302)
+            append_rec(n, a.rec);
             n.cs_pool.insert(n.cs_pool.end(), a.cs.begin(), a.cs.end()); n.cs_off.push_back((int64_t)n.cs_pool.size());
             if (!paf.device_ranges) {
                 n.rng_qry_l.insert(n.rng_qry_l.end(), a.ql.begin(), a.ql.end()); n.rng_qry_r.insert(n.rng_qry_r.end(), a.qr.begin(), a.qr.end());
@@ -744,15 +731,27 @@ static int merge_alt_text(const char *text, int64_t len, double baseline, aasm_p
 }
 
 // ---- writers (alignasm.cpp:398-490) ---------------------------------------------------
-static inline void put_i64(std::string &s, int64_t v) {
-    char buf[24];
-    char *e = buf + sizeof buf, *p = e;
-    uint64_t u = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
-    do { *--p = (char)('0' + u % 10); u /= 10; } while (u);
-    if (v < 0) *--p = '-';
-    s.append(p, (size_t)(e - p));
+// The 12 PAF columns of record r over the given query / reference spans (closed, the reference span in query order, as
+// stored) and counts, each followed by a tab: every writer appends its own tags.
+static void put_columns(std::string &buf, const std::string &name, const aasm_paf &paf, int64_t r, int64_t qs, int64_t qe,
+                        int64_t rs, int64_t re, int32_t mat_num, int32_t aln_len) {
+    const bool fwd = paf.aln_fwd[r] != 0;
+    if (!fwd) std::swap(rs, re);
+    buf += name; buf += '\t';
+    put_i64(buf, paf.qry_total[r]); buf += '\t';
+    put_i64(buf, qs); buf += '\t';
+    put_i64(buf, qe + 1); buf += '\t';
+    buf += fwd ? '+' : '-'; buf += '\t';
+    buf += paf.chr_name[paf.ref_chr[r]]; buf += '\t';
+    put_i64(buf, paf.ref_total[r]); buf += '\t';
+    put_i64(buf, rs); buf += '\t';
+    put_i64(buf, re + 1); buf += '\t';
+    put_i64(buf, mat_num); buf += '\t';
+    put_i64(buf, aln_len); buf += '\t';
+    put_i64(buf, paf.map_qul[r]); buf += '\t';
 }
 
+// an output row: the 12 columns of the (re-cut) record + tp + xi + its edited cs tag
 static int emit_line(const aasm_paf &paf, int64_t contig, const std::string &name, const aasm_out_elem &o,
                      std::string &buf, std::string &err) {
     const int64_t r = paf.ctg_rec_off[contig] + o.ctg_index;
@@ -773,18 +772,7 @@ static int emit_line(const aasm_paf &paf, int64_t contig, const std::string &nam
                           o.edited_qry_end, o.edited_ref_str, o.edited_ref_end, ed, err))
             return AASM_E_PARSE;
     }
-    buf += name; buf += '\t';
-    put_i64(buf, paf.qry_total[r]); buf += '\t';
-    put_i64(buf, o.edited_qry_str); buf += '\t';
-    put_i64(buf, o.edited_qry_end + 1); buf += '\t';
-    buf += fwd ? '+' : '-'; buf += '\t';
-    buf += paf.chr_name[paf.ref_chr[r]]; buf += '\t';
-    put_i64(buf, paf.ref_total[r]); buf += '\t';
-    put_i64(buf, fwd ? o.edited_ref_str : o.edited_ref_end); buf += '\t';
-    put_i64(buf, (fwd ? o.edited_ref_end : o.edited_ref_str) + 1); buf += '\t';
-    put_i64(buf, ed.mat_num); buf += '\t';
-    put_i64(buf, ed.aln_len); buf += '\t';
-    put_i64(buf, paf.map_qul[r]); buf += '\t';
+    put_columns(buf, name, paf, r, o.edited_qry_str, o.edited_qry_end, o.edited_ref_str, o.edited_ref_end, ed.mat_num, ed.aln_len);
     buf += o.is_alt_path ? "tp:A:S" : "tp:A:P"; buf += '\t';
     buf += "xi:Z:"; buf += paf.cord_type[r] == 0 ? "P_" : "A_"; put_i64(buf, paf.row_index[r]); buf += '\t';
     if (uncut) buf.append(cs, (size_t)cs_len);
@@ -798,32 +786,24 @@ static int emit_line(const aasm_paf &paf, int64_t contig, const std::string &nam
     return AASM_OK;
 }
 
-
-// buffers -> one file, in order; every thread writes its own buffer at its own offset
-static int write_buffers(const char *path, const std::vector<std::string> &bufs) {
-    // the rounds go to a temporary name beside the target, which takes its place only when every row is on disk: a row that
-    // cannot be formatted (a cs tag clipped inside an insertion: get_edited_paf_data throws) or a failing write leaves no
-    // truncated .paf behind
-    const std::string tmp_path = std::string(path) + ".tmp." + std::to_string((long long)::getpid());
-    const int fd = ::open(tmp_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) { set_last_error(std::string("cannot open ") + path + " for writing"); return AASM_E_IO; }
-    const int T = (int)bufs.size();
-    std::vector<int64_t> off((size_t)T + 1, 0);
-    for (int t = 0; t < T; t++) off[t + 1] = off[t] + (int64_t)bufs[t].size();
-    std::atomic<int> rc{AASM_OK};
-    run_threads(T, [&](int t) {
-        const char *p = bufs[t].data();
-        int64_t left = (int64_t)bufs[t].size(), o = off[t];
-        while (left > 0) {
-            const ssize_t w = ::pwrite(fd, p, (size_t)std::min<int64_t>(left, 1 << 30), (off_t)o);
-            if (w <= 0) { rc = AASM_E_IO; return; }
-            p += w; o += w; left -= w;
-        }
-    });
-    if (::close(fd) != 0) rc = AASM_E_IO;
-    if (rc == AASM_OK && ::rename(tmp_path.c_str(), path) != 0) rc = AASM_E_IO;
-    if (rc != AASM_OK) { ::unlink(tmp_path.c_str()); set_last_error(std::string("write to ") + path + " failed"); }
-    return rc;
+// the batch's own rows of contig c, as PAF text (12 columns + tp + cs): Paf.save / Paf.to_text
+static void emit_input_rows(const aasm_paf &paf, int64_t c, std::string &buf) {
+    for (int64_t r = paf.ctg_rec_off[c]; r < paf.ctg_rec_off[c + 1]; r++) {
+        put_columns(buf, paf.ctg_name[c], paf, r, paf.qry_str[r], paf.qry_end[r], paf.ref_str[r], paf.ref_end[r], paf.mat_num[r], paf.aln_len[r]);
+        buf += "tp:A:P\t";
+        buf.append(paf.cs_pool.data() + paf.cs_off[r], (size_t)(paf.cs_off[r + 1] - paf.cs_off[r]));
+        buf += '\n';
+    }
+}
+// prefix sums of an upper estimate of those rows' bytes, per contig
+static std::vector<int64_t> input_row_bytes(const aasm_paf &paf) {
+    const int64_t C = paf.n_contigs();
+    std::vector<int64_t> wp((size_t)C + 1, 0);
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t r0 = paf.ctg_rec_off[c], r1 = paf.ctg_rec_off[c + 1];
+        wp[c + 1] = wp[c] + (paf.cs_off[r1] - paf.cs_off[r0]) + (r1 - r0) * (96 + (int64_t)paf.ctg_name[c].size());
+    }
+    return wp;
 }
 
 // One output file, rows in contig order (as process_output writes them), formatted AND written by T threads.  The contigs
@@ -902,40 +882,6 @@ static int append_rounds(int fd, int64_t &file_off, const char *path, int64_t C,
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (end - file_off) / 1e6, T, (long long)NCH);
     if (rc == AASM_OK) file_off = end;
     return rc;
-}
-
-// the batch as PAF text (12 columns + tp + cs), rows shared out over the host threads
-static void format_rows_mt(const aasm_paf &paf, std::vector<std::string> &bufs) {
-    const int64_t R = paf.n_records();
-    int T = host_threads();
-    if (R < 4096) T = 1;
-    bufs.assign((size_t)T, std::string());
-    std::vector<int32_t> ctg_of((size_t)R);
-    for (int64_t c = 0; c < paf.n_contigs(); c++) for (int64_t r = paf.ctg_rec_off[c]; r < paf.ctg_rec_off[c + 1]; r++) ctg_of[r] = (int32_t)c;
-    run_threads(T, [&](int t) {
-        std::string &buf = bufs[t];
-        const int64_t r0 = R * t / T, r1 = R * (t + 1) / T;
-        if (r1 > r0) buf.reserve((size_t)((paf.cs_off[r1] - paf.cs_off[r0]) + (r1 - r0) * 96));
-        for (int64_t r = r0; r < r1; r++) {
-            const bool fwd = paf.aln_fwd[r] != 0;
-            int64_t rs = paf.ref_str[r], re = paf.ref_end[r];
-            if (!fwd) std::swap(rs, re);
-            buf += paf.ctg_name[ctg_of[r]]; buf += '\t';
-            put_i64(buf, paf.qry_total[r]); buf += '\t';
-            put_i64(buf, paf.qry_str[r]); buf += '\t';
-            put_i64(buf, paf.qry_end[r] + 1); buf += '\t';
-            buf += fwd ? '+' : '-'; buf += '\t';
-            buf += paf.chr_name[paf.ref_chr[r]]; buf += '\t';
-            put_i64(buf, paf.ref_total[r]); buf += '\t';
-            put_i64(buf, rs); buf += '\t';
-            put_i64(buf, re + 1); buf += '\t';
-            put_i64(buf, paf.mat_num[r]); buf += '\t';
-            put_i64(buf, paf.aln_len[r]); buf += '\t';
-            put_i64(buf, paf.map_qul[r]); buf += "\ttp:A:P\t";
-            buf.append(paf.cs_pool.data() + paf.cs_off[r], (size_t)(paf.cs_off[r + 1] - paf.cs_off[r]));
-            buf += '\n';
-        }
-    });
 }
 
 }  // namespace aasm
@@ -1157,6 +1103,14 @@ int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out
     return AASM_OK;
 }
 
+// the files of a session that ended with rc: kept if rc is AASM_OK, else removed, rc's message kept
+static int close_session(aasm_writer *w, int rc) {
+    const std::string msg = rc != AASM_OK ? aasm_last_error() : "";
+    const int rc2 = aasm_writer_close(w, rc == AASM_OK ? 1 : 0);
+    if (rc != AASM_OK) { set_last_error(msg); return rc; }
+    return rc2;
+}
+
 int aasm_paf_write_outputs(const aasm_paf *paf, const aasm_batch_out *out, const char *main_path, const char *alt_path,
                            const char *all_path) {
     if (!paf || !out || out->n_contigs != paf->n_contigs()) return AASM_E_INVAL;
@@ -1164,18 +1118,14 @@ int aasm_paf_write_outputs(const aasm_paf *paf, const aasm_batch_out *out, const
     aasm_writer *w = nullptr;
     int rc = aasm_writer_open(main_path, alt_path, all_path, &w);
     if (rc != AASM_OK) return rc;
-    rc = aasm_writer_append(w, paf, out, 0);
-    const std::string msg = rc != AASM_OK ? aasm_last_error() : "";
-    const int rc2 = aasm_writer_close(w, rc == AASM_OK ? 1 : 0);
-    if (rc != AASM_OK) { set_last_error(msg); return rc; }
-    return rc2;
+    return close_session(w, aasm_writer_append(w, paf, out, 0));
 }
 
 int64_t aasm_cs_match_ranges(const char *cs, int64_t cs_len, int aln_fwd, int64_t qry_str, int64_t qry_end, int64_t ref_str,
                              int64_t ref_end, int64_t *qry_l, int64_t *qry_r, int64_t *ref_l, int64_t cap) {
     std::vector<int64_t> a, b, c;
     std::string err;
-    int64_t n = match_ranges(cs, cs_len, aln_fwd != 0, qry_str, qry_end, ref_str, ref_end, &a, &b, &c, err);
+    int64_t n = match_ranges(cs, cs_len, aln_fwd != 0, qry_str, qry_end, ref_str, ref_end, a, b, c, err);
     if (n < 0) { set_last_error(err); return AASM_E_PARSE; }
     for (int64_t i = 0; i < n && i < cap; i++) {
         if (qry_l) qry_l[i] = a[i];
@@ -1207,8 +1157,16 @@ int64_t aasm_cs_edit(const char *cs, int64_t cs_len, int aln_fwd, int64_t qry_st
 int aasm_paf_to_text(const aasm_paf *paf, char **text, int64_t *len) {
     if (!paf || !text || !len) return AASM_E_INVAL;
     if (!paf->has_cs) { set_last_error("PAF was generated without cs strings"); return AASM_E_INVAL; }
-    std::vector<std::string> bufs;
-    format_rows_mt(*paf, bufs);
+    const int64_t C = paf->n_contigs();
+    const std::vector<int64_t> wp = input_row_bytes(*paf);
+    const int T = paf->n_records() < 4096 ? 1 : host_threads();
+    std::vector<int64_t> cut((size_t)T + 1, C);                       // thread t: contigs [cut[t], cut[t + 1]), a T-th of the bytes
+    for (int t = 0; t < T; t++) cut[t] = std::lower_bound(wp.begin(), wp.end(), wp[C] * t / T) - wp.begin();
+    std::vector<std::string> bufs((size_t)T);
+    run_threads(T, [&](int t) {
+        bufs[t].reserve((size_t)(wp[cut[t + 1]] - wp[cut[t]]));
+        for (int64_t c = cut[t]; c < cut[t + 1]; c++) emit_input_rows(*paf, c, bufs[t]);
+    });
     size_t total = 0;
     for (auto &b : bufs) total += b.size();
     *len = (int64_t)total;
@@ -1220,12 +1178,15 @@ int aasm_paf_to_text(const aasm_paf *paf, char **text, int64_t *len) {
     return AASM_OK;
 }
 
+// through the writer session's temporary file: a failing write leaves no truncated file behind
 int aasm_paf_save(const aasm_paf *paf, const char *path) {
     if (!paf || !path) return AASM_E_INVAL;
     if (!paf->has_cs) { set_last_error("PAF was generated without cs strings"); return AASM_E_INVAL; }
-    std::vector<std::string> bufs;
-    format_rows_mt(*paf, bufs);
-    return write_buffers(path, bufs);
+    aasm_writer *w = nullptr;
+    const int rc = aasm_writer_open(path, nullptr, nullptr, &w);
+    if (rc != AASM_OK) return rc;
+    return close_session(w, append_rounds(w->fd[0], w->off[0], path, paf->n_contigs(), input_row_bytes(*paf), w->bufs[0], 0,
+                                          [&](int64_t c, std::string &buf, std::string &) { emit_input_rows(*paf, c, buf); return (int)AASM_OK; }));
 }
 
 }  // extern "C"

@@ -23,14 +23,21 @@ using big_i64 = std::vector<int64_t, default_init_alloc<int64_t>>;
 using big_char = std::vector<char, default_init_alloc<char>>;
 }  // namespace aasm
 
+// X(type, name) for every per-record column (one value per record, input order): the arrays below and the codec's
+// record type (aasm_paf.cpp) derive from this one list
+#define AASM_PAF_RECORD_COLUMNS(X)                                                                                      \
+    X(int64_t, qry_str) X(int64_t, qry_end) X(int64_t, ref_str) X(int64_t, ref_end) X(int64_t, qry_total)              \
+    X(int64_t, ref_total) X(int32_t, ref_chr) X(int32_t, mat_num) X(int32_t, aln_len) X(int32_t, row_index)            \
+    X(uint8_t, aln_fwd) X(uint8_t, map_qul) X(uint8_t, cord_type) /* cord_type: TYPE_MAIN=0 / TYPE_ALT=1 */
+
 struct aasm_paf {
     // per contig (consecutive rows with the same query name, alignasm.cpp:125-133)
     std::vector<std::string> ctg_name;
     std::vector<int64_t> ctg_rec_off;          // [C+1]
     // per record, input order
-    std::vector<int64_t> qry_str, qry_end, ref_str, ref_end, qry_total, ref_total;
-    std::vector<int32_t> ref_chr, mat_num, aln_len, row_index;
-    std::vector<uint8_t> aln_fwd, map_qul, cord_type;   // cord_type: TYPE_MAIN=0 / TYPE_ALT=1
+#define AASM_X(T, name) std::vector<T> name;
+    AASM_PAF_RECORD_COLUMNS(AASM_X)
+#undef AASM_X
     std::vector<int64_t> cs_off;               // [R+1] into cs_pool (each entry "cs:Z:...")
     aasm::big_char cs_pool;
     bool has_cs = true;                        // generator may skip cs strings (bench)
