@@ -226,8 +226,8 @@ class HostBatch:
         return HostBatch(out)
 
 
-# ---- k shortest walks on caller DAGs (aasm_k_shortest_walks) ----------------------------------------------------------------
-AASM_KSW_WALKS, AASM_KSW_TREE, AASM_KSW_HOOK_ARENA = 0x1, 0x2, 0x100
+# ---- k shortest walks on caller graphs (aasm_k_shortest_walks) ----------------------------------------------------------------
+AASM_KSW_WALKS, AASM_KSW_TREE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA = 0x1, 0x2, 0x4, 0x100
 
 
 class KswOut(C.Structure):

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_E_INVAL, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, KswOut, Opts,
+from ._abi import (AASM_E_INVAL, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, KswOut, Opts,
                    OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,15 +107,19 @@ def sssp_dijkstra(g_voff, rowptr, col, w5, src, device=0):
     return d, prev
 
 
-def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=False, device=0, _hooks=0):
+def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=False, device=0, _hooks=0, cycles=False):
     """k_shortest_walks(source, sink, k) of the reference's solver with is_dag = true, and every walk recovered
     (k_shortest_walks.hpp:177-290), on the GPU over a batch of DAGs in sssp_dijkstra's layout.  w: [E, 5] int64
     {qry_score, ref_score, anom, qul_nonzero, qul_total} or [E] (scalar weights, taken as (w, 0, 0, 0, 1)).
     Returns a dict of numpy arrays: n_found [G], dist [G, k, 5], status [G] (0, or AASM_E_INVAL for a graph with a cycle),
     heap_nodes [G]; with walks, walk_off [G * k + 1] and walk_edges (caller CSR positions, source -> sink, walk g * k + i
-    at walk_edges[walk_off[g * k + i]:walk_off[g * k + i + 1]]); with tree, d [V, 5] and best [V] (local ids)."""
+    at walk_edges[walk_off[g * k + i]:walk_off[g * k + i + 1]]); with tree, d [V, 5] and best [V] (local ids).
+    cycles=True solves every graph as the solver does with is_dag = false (the tree of dijkstra() from the sink): graphs may
+    hold cycles, and walks may repeat vertices and pass through the sink.  status is then AASM_E_OVERFLOW for a graph that
+    meets one of the limits include/alignasm_amd.h lists (a cycle that improves a distance for ever, distances out of range,
+    more than 2^28 walk edges) and AASM_E_INVAL for one whose best[] is no tree into the sink."""
     g_voff, rowptr, col, w5, source, sink = ksw_inputs(g_voff, rowptr, col, w, source, sink)
-    flags = (AASM_KSW_WALKS if walks else 0) | (AASM_KSW_TREE if tree else 0) | int(_hooks)
+    flags = (AASM_KSW_WALKS if walks else 0) | (AASM_KSW_TREE if tree else 0) | (AASM_KSW_CYCLES if cycles else 0) | int(_hooks)
     out = KswOut()
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     rc = LIB.aasm_k_shortest_walks(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(source), P(sink), C.c_int64(int(k)),

@@ -1,11 +1,15 @@
-// aasm_ksw.h -- batched k shortest walks on caller-supplied DAGs (row ★K): the solver's k_shortest_walks() with
-// is_dag = true (k_shortest_walks.hpp:177-249) and kth_shortest_walk_recover() (:252-290), one workgroup per graph.
+// aasm_ksw.h -- batched k shortest walks on caller-supplied graphs (row ★K): the solver's k_shortest_walks()
+// (k_shortest_walks.hpp:177-249) with is_dag = true, or with is_dag = false, negative_edge = false under AASM_KSW_CYCLES, and
+// kth_shortest_walk_recover() (:252-290), one workgroup per graph.
 //
 // Kernel bodies (KCtx style, so tests/host_emul_graphs compiles them for one lane on the host):
 //   kb_ksw_tree   reversed CSR in the reference's list order (:180-183), Kahn order of the reversed graph (:132-156) fused
 //                 with the DAG relaxation to the sink (:160-175; strict `>` in CALC_SUM order), the best EDGE beside best,
 //                 cycle detection, the children of every tree vertex in ascending u (:191-194), the BFS from the sink, the
 //                 exact sidetrack insert count and the number of walks (saturated at k): the bounds the host sizes by
+//   kb_ksw_tree_cyc   the same stage for graphs that may hold cycles: the tree is the one dijkstra() from the sink over the
+//                 reversed graph leaves (:69-87, kb_sssp_dijkstra's formulation), with a bound on its pushes and a guard that
+//                 best[] is a tree into the sink; the number of walks is k as soon as a cycle lies between source and sink
 //   kb_ksw_heap   the persistent leftist heaps (:196-215, leftist_heap.hpp:29-40) in the reference's allocation order
 //   kb_ksw_enum   k pops of the min-queue of (distance, node, insertion index) (:230-249): ties by arena index, the
 //                 monotonic allocator's order (hazard B3)
@@ -19,7 +23,11 @@ namespace aasm {
 
 #define AASM_KSW_MAX_V ((int64_t)1 << 20)     // vertices per graph: a walk sum over < 2^20 edges of |w| < 2^39 stays in int64
 #define AASM_KSW_MAX_K ((int64_t)1 << 24)
+#define AASM_KSW_MAX_WALK_EDGES ((int64_t)1 << 28)   // AASM_KSW_CYCLES: edges of one graph's walks together
 #define AASM_KSW_SPINE 64                     // right-spine stack of one insert (a version of <= 2^31 keys has a spine <= 33)
+#define AASM_KSW_DJ_PUSHES 64                 // dijkstra of kb_ksw_tree_cyc: at most 64 * (E + 2) pushes per graph
+#define AASM_KSW_SAFE_SCORE ((int64_t)1 << 62)   // with cycles a walk has any number of edges: a queued distance stays below
+#define AASM_KSW_SAFE_COUNT ((int32_t)1 << 30)   // these in |qry|, |ref| and in anom, qnz, qtot
 
 // heap node (leftist_heap.hpp:18-27), 48 bytes: the value (u, v) is the edge e (u = its tail, v = col[e]) -
 // the edge id is what tells parallel edges apart
@@ -55,9 +63,49 @@ struct KswArgs {
     int32_t *qnode, *qprev, *rlast;
     Dist *rdist;
     int64_t *woff, *wedges;
+    // AASM_KSW_CYCLES: graph g's dijkstra heap is [hoff[g], hoff[g + 1]) of dheap (empty: the graph is left as it is)
+    int32_t cycles;
+    const int64_t *hoff;
+    DjEnt *dheap;
 };
 
 AASM_DEV bool ksw_is_ident(const Dist &c) { return dist_eq(c, dist_zero()); }
+
+// tree[best[u]] in ascending u (its end is deg[], which must be 0 everywhere on entry), the BFS order from the sink with depth[]
+// (-1 on entry), and the inserts the heap stage will make: nbfs[g], ins[g].  False when a vertex is reached twice (best[] is no
+// tree; never in a DAG).
+AASM_DEV bool ksw_tree_bfs(const KswArgs &a, int64_t g) {
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb];
+    const int32_t t = a.sink[g];
+    int32_t *deg = a.deg + vb, *koff = a.koff + vb, *kids = a.kids + vb, *bfs = a.bfs + vb, *depth = a.depth + vb;
+    const int32_t *best = a.best + vb, *col = a.col + eb;
+    const Dist *d = a.d + vb;
+    const int64_t *rp = a.rowptr + vb;
+    for (int64_t v = 0; v < V; v++) if (best[v] >= 0) deg[best[v]]++;
+    int32_t run = 0;
+    for (int64_t v = 0; v < V; v++) { const int32_t c = deg[v]; koff[v] = run; deg[v] = run; run += c; }
+    for (int64_t v = 0; v < V; v++) if (best[v] >= 0) kids[deg[best[v]]++] = (int32_t)v;
+    // BFS from the sink over the tree, counting the inserts the heap stage will make
+    int64_t bh = 0, bt = 0, ins = 0;
+    bfs[bt++] = t; depth[t] = 0;
+    while (bh < bt) {
+        const int32_t u = bfs[bh++];
+        bool seen_p = false;
+        for (int64_t e = rp[u] - eb; e < rp[u + 1] - eb; e++) {
+            const int32_t v = col[e];
+            if (dist_is_max(d[v])) continue;
+            if (!seen_p && v == best[u] && ksw_is_ident(dist_sub(dist_add(edge_w5(a.w5, eb + e), d[v]), d[u]))) { seen_p = true; continue; }
+            ins++;
+        }
+        for (int32_t j = koff[u]; j < deg[u]; j++) {
+            const int32_t p = kids[j];
+            if (depth[p] >= 0) return false;
+            depth[p] = depth[u] + 1; bfs[bt++] = p;
+        }
+    }
+    a.nbfs[g] = bt; a.ins[g] = ins;
+    return true;
+}
 
 // ---- stage 1-2: reversed CSR, Kahn order + DAG relaxation, tree children, BFS, bounds ------------------------------------
 AASM_DEV void kb_ksw_tree(const KCtx &k, const KswArgs &a) {
@@ -66,7 +114,7 @@ AASM_DEV void kb_ksw_tree(const KCtx &k, const KswArgs &a) {
     const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], E = a.rowptr[vb + V] - eb;
     const int32_t s = a.src[g], t = a.sink[g];
     int32_t *roff = a.roff + vb, *deg = a.deg + vb, *order = a.order + vb, *best = a.best + vb, *bedge = a.bedge + vb;
-    int32_t *koff = a.koff + vb, *kids = a.kids + vb, *bfs = a.bfs + vb, *depth = a.depth + vb;
+    int32_t *koff = a.koff + vb, *depth = a.depth + vb;
     int32_t *rev = a.rev + eb, *etail = a.etail + eb;
     Dist *d = a.d + vb;
     int64_t *cnt = a.cnt + vb;
@@ -113,26 +161,123 @@ AASM_DEV void kb_ksw_tree(const KCtx &k, const KswArgs &a) {
     }
     a.status[g] = 0;
     a.walks[g] = dist_is_max(d[s]) ? 0 : cnt[s];
-    // tree[best[u]] in ascending u; its end is deg[] (the Kahn countdown is 0 everywhere now)
-    for (int64_t v = 0; v < V; v++) if (best[v] >= 0) deg[best[v]]++;
-    run = 0;
-    for (int64_t v = 0; v < V; v++) { const int32_t c = deg[v]; koff[v] = run; deg[v] = run; run += c; }
-    for (int64_t v = 0; v < V; v++) if (best[v] >= 0) kids[deg[best[v]]++] = (int32_t)v;
-    // BFS from the sink over the tree, counting the inserts the heap stage will make
-    int64_t bh = 0, bt = 0, ins = 0;
-    bfs[bt++] = t; depth[t] = 0;
-    while (bh < bt) {
-        const int32_t u = bfs[bh++];
-        bool seen_p = false;
+    ksw_tree_bfs(a, g);                                              // (the Kahn countdown deg[] is 0 everywhere now)
+}
+
+// ---- stage 1-2 under AASM_KSW_CYCLES: the tree of dijkstra() from the sink over the reversed graph (:185, :69-87) ---------------
+// kb_sssp_dijkstra's formulation on the reversed lists: wave-uniform control, lane 0 stores; bedge[to] is the edge whose
+// relaxation last set best[to].  CALC_SUM's third key is not monotone under addition (a larger qnz / qtot ratio is "smaller"),
+// so a cycle can improve a distance for ever while the heap holds a few entries: the pushes are counted and a graph that makes
+// more than 64 * (E + 2) of them ends with AASM_E_OVERFLOW (the reference does not return on it).  A graph whose heap room
+// runs out first is marked ins = -1 and run again by the host with more.  The rest runs on lane 0 as kb_ksw_tree.
+AASM_DEV void kb_ksw_tree_cyc(const KCtx &k, const KswArgs &a) {
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs || k.tid >= AASM_WAVE) return;
+    const int64_t cap = a.hoff[g + 1] - a.hoff[g];
+    if (cap <= 0) return;                                            // solved with less heap room
+    const int lane = k.lane;
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], E = a.rowptr[vb + V] - eb;
+    const int32_t s = a.src[g], t = a.sink[g];
+    int32_t *roff = a.roff + vb, *deg = a.deg + vb, *order = a.order + vb, *best = a.best + vb, *bedge = a.bedge + vb;
+    int32_t *koff = a.koff + vb, *kids = a.kids + vb, *depth = a.depth + vb;
+    int32_t *rev = a.rev + eb, *etail = a.etail + eb;
+    Dist *d = a.d + vb;
+    int64_t *cnt = a.cnt + vb;
+    const int64_t *rp = a.rowptr + vb;
+    const int32_t *col = a.col + eb;
+    if (lane == 0) {
+        for (int64_t v = 0; v < V; v++) {
+            roff[v] = 0; d[v] = dist_max(); best[v] = -1; bedge[v] = -1; cnt[v] = 0; depth[v] = -1; deg[v] = 0;
+            for (int64_t e = rp[v] - eb; e < rp[v + 1] - eb; e++) etail[e] = (int32_t)v;
+        }
+        // g_rev[v] as in kb_ksw_tree: ascending edge id within a head
+        for (int64_t e = 0; e < E; e++) roff[col[e]]++;
+        int32_t run = 0;
+        for (int64_t v = 0; v < V; v++) { const int32_t c = roff[v]; roff[v] = run; run += c; }
+        for (int64_t v = 0; v < V; v++) koff[v] = roff[v];
+        for (int64_t e = 0; e < E; e++) rev[koff[col[e]]++] = (int32_t)e;
+        d[t] = dist_zero();                                          // IDENTITY_DISTANCE (:73)
+    }
+    wave_fence();
+    DjEnt *H = a.dheap + a.hoff[g];
+    const int64_t push_lim = AASM_KSW_DJ_PUSHES * (E + 2);
+    int64_t n = 0, pushes = 0;
+    int over = 0;                                                    // 1: heap room, 2: the bound on pushes
+    auto push = [&](const Dist &dd, int32_t v) {
+        if (++pushes > push_lim) { over = 2; return; }
+        if (n >= cap) { over = 1; return; }
+        dj_heap_push(H, n, lane, dd, v);
+    };
+    push(dist_zero(), t);
+    while (n > 0 && !over) {
+        const DjEnt top = dj_heap_pop(H, n, lane);
+        const int32_t v = uni(top.v);
+        const Dist dv = uni(top.d);
+        if (!uni(dist_eq(dv, d[v]))) continue;                       // :77 (operator!=)
+        const int64_t r0 = uni((int64_t)roff[v]), r1 = v + 1 < V ? uni((int64_t)roff[v + 1]) : E;
+        for (int64_t r = r0; r < r1 && !over; r++) {
+            const int32_t e = uni(rev[r]), to = uni(etail[e]);
+            const Dist cand = uni(dist_add(dv, edge_w5(a.w5, eb + e)));
+            if (uni(dist_lt<CALC_SUM_MODE>(cand, d[to]))) {          // d_[to] > dv + w (:79)
+                if (lane == 0) { d[to] = cand; best[to] = v; bedge[to] = e; }
+                wave_fence();
+                push(cand, to);
+            }
+        }
+    }
+    if (lane != 0) return;
+    a.nbfs[g] = 0; a.ins[g] = 0; a.walks[g] = 0;
+    if (over) {
+        a.status[g] = AASM_E_OVERFLOW;
+        if (over == 1) a.ins[g] = -1;
+        for (int64_t v = 0; v < V; v++) { d[v] = dist_max(); best[v] = -1; bedge[v] = -1; }
+        d[t] = dist_zero();
+        return;
+    }
+    // best[] must be a tree into the sink: the BFS from the sink over tree[] visits every vertex with a distance, once (where it
+    // is none - the sink's own distance improved round a cycle - the reference's BFS does not end)
+    int64_t fin = 0;
+    for (int64_t v = 0; v < V; v++) fin += !dist_is_max(d[v]);
+    if (!ksw_tree_bfs(a, g) || a.nbfs[g] != fin) {
+        a.status[g] = AASM_E_INVAL;
+        a.nbfs[g] = 0; a.ins[g] = 0;
+        return;
+    }
+    a.status[g] = 0;
+    if (dist_is_max(d[s])) return;                                   // no walk (:188-189)
+    // An upper bound on distances.size(): the walks source -> sink stay on S, the vertices the source reaches among those with a
+    // distance.  Kahn on the reversed graph of S; a vertex left over lies on or behind a cycle, then there is no bound but k;
+    // otherwise the walks are the paths of a DAG, counted as in kb_ksw_tree.  (koff, kids, order, deg are free after the BFS.)
+    int32_t *mark = koff, *queue = kids;
+    for (int64_t v = 0; v < V; v++) { mark[v] = 0; deg[v] = 0; cnt[v] = 0; }
+    int64_t head = 0, nS = 0;
+    order[nS++] = s; mark[s] = 1;
+    while (head < nS) {
+        const int32_t u = order[head++];
         for (int64_t e = rp[u] - eb; e < rp[u + 1] - eb; e++) {
             const int32_t v = col[e];
-            if (dist_is_max(d[v])) continue;
-            if (!seen_p && v == best[u] && ksw_is_ident(dist_sub(dist_add(edge_w5(a.w5, eb + e), d[v]), d[u]))) { seen_p = true; continue; }
-            ins++;
+            if (!mark[v] && !dist_is_max(d[v])) { mark[v] = 1; order[nS++] = v; }
         }
-        for (int32_t j = koff[u]; j < deg[u]; j++) { const int32_t p = kids[j]; depth[p] = depth[u] + 1; bfs[bt++] = p; }
     }
-    a.nbfs[g] = bt; a.ins[g] = ins;
+    for (int64_t i = 0; i < nS; i++) {
+        const int32_t u = order[i];
+        for (int64_t e = rp[u] - eb; e < rp[u + 1] - eb; e++) deg[u] += mark[col[e]];
+    }
+    int64_t tail = 0;
+    for (int64_t i = 0; i < nS; i++) if (deg[order[i]] == 0) queue[tail++] = order[i];
+    cnt[t] = 1;
+    for (head = 0; head < tail; head++) {
+        const int32_t v = queue[head];
+        const int64_t r1 = v + 1 < V ? roff[v + 1] : E;
+        for (int64_t r = roff[v]; r < r1; r++) {
+            const int32_t to = etail[rev[r]];
+            if (!mark[to]) continue;
+            const int64_t c = cnt[to] + cnt[v];
+            cnt[to] = c < a.k ? c : a.k;
+            if (--deg[to] == 0) queue[tail++] = to;
+        }
+    }
+    a.walks[g] = tail < nS ? a.k : cnt[s];
 }
 
 // heap_insert (leftist_heap.hpp:29-40) without recursion: the right spine below which the key goes is walked down first,
@@ -203,6 +348,12 @@ AASM_DEV bool ksw_qe_less(const KswQE &x, const KswQE &y) {        // std::tuple
     if (x.hp != y.hp) return x.hp < y.hp;
     return x.cur < y.cur;
 }
+// a distance the next additions keep inside int64 / int32 (never outside on a DAG of <= 2^20 vertices)
+AASM_DEV bool ksw_in_range(const Dist &x) {
+    const int64_t S = AASM_KSW_SAFE_SCORE;
+    const int32_t C = AASM_KSW_SAFE_COUNT;
+    return x.qry > -S && x.qry < S && x.ref > -S && x.ref < S && x.anom > -C && x.anom < C && x.qnz > -C && x.qnz < C && x.qtot > -C && x.qtot < C;
+}
 AASM_DEV void kb_ksw_enum(const KCtx &k, const KswArgs &a) {
     const int64_t g = k.bid;
     if (g >= a.n_graphs || k.tid != 0) return;
@@ -221,7 +372,7 @@ AASM_DEV void kb_ksw_enum(const KCtx &k, const KswArgs &a) {
     const int32_t hs = hroot[s];
     bool over = false;
     auto emplace = [&](const Dist &dd, int32_t hp, int32_t pre) {
-        if (nn >= qcap) { over = true; return; }
+        if (nn >= qcap || !ksw_in_range(dd)) { over = true; return; }
         KswQE x; x.d = dd; x.hp = hp; x.cur = (int32_t)nn; x.pad = 0;
         nodes[nn] = hp; prev[nn] = pre; nn++;
         int64_t i = qn++;
@@ -266,15 +417,16 @@ AASM_DEV void kb_ksw_enum(const KCtx &k, const KswArgs &a) {
 
 // ---- stage 5: walk recovery (:252-290) as caller edge ids --------------------------------------------------------------
 // A walk is source ->tree-> u_1 -side-> v_1 ->tree-> u_2 ... v_m ->tree-> sink, the tree segment from x to y taking
-// depth[x] - depth[y] edges (the reference takes a sidetrack the first time it stands on its tail: a tree path in a DAG
-// visits a vertex once).  The sidetracks come off the prev chain last first, so a walk is written back to front.
+// depth[x] - depth[y] edges (the reference takes a sidetrack the first time it stands on its tail: best[] is a tree into the
+// sink, so a tree path visits a vertex once - with cycles too, where the sink, at depth 0, may be a sidetrack's tail).  The
+// sidetracks come off the prev chain last first, so a walk is written back to front.  Walk i holds at most i sidetracks.
 AASM_DEV int64_t ksw_walk_len(const KswArgs &a, int64_t g, int64_t i) {
-    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb];
+    const int64_t vb = a.voff[g], nf = a.nfound[g], eb = a.rowptr[vb];
     const int32_t *depth = a.depth + vb, *etail = a.etail + eb, *col = a.col + eb;
     const KswNode *A = a.arena + a.aoff[g];
     const int32_t *nodes = a.qnode + a.qoff[g], *prev = a.qprev + a.qoff[g];
     int64_t len = 0, stop = 0, steps = 0;
-    for (int32_t c = a.rlast[a.rofs[g] + i]; c >= 0 && steps < V; c = prev[c], steps++) {
+    for (int32_t c = a.rlast[a.rofs[g] + i]; c >= 0 && steps < nf; c = prev[c], steps++) {
         const int32_t e = A[nodes[c]].e;
         len += depth[col[e]] - stop + 1;
         stop = depth[etail[e]];
@@ -286,23 +438,31 @@ AASM_DEV void kb_ksw_count(const KCtx &k, const KswArgs &a) {
     if (g >= a.n_graphs || k.tid >= AASM_WAVE) return;
     const int64_t nf = a.nfound[g], per = (nf + AASM_WAVE - 1) / AASM_WAVE;
     const int64_t i0 = k.lane * per < nf ? k.lane * per : nf, i1 = i0 + per < nf ? i0 + per : nf;
+    // under AASM_KSW_CYCLES a lane's sum saturates just above the cap on a graph's walk edges (a walk through a cycle has any length)
+    const int64_t sat = a.cycles ? AASM_KSW_MAX_WALK_EDGES + 1 : INT64_MAX;
     int64_t sum = 0;
-    for (int64_t i = i0; i < i1; i++) sum += ksw_walk_len(a, g, i);
+    for (int64_t i = i0; i < i1; i++) { const int64_t len = ksw_walk_len(a, g, i); sum = len < sat - sum ? sum + len : sat; }
     const int64_t incl = wave_incl_add(sum);
+    const int64_t tot = wave_bcast(incl, AASM_WAVE - 1);
+    if (tot >= sat) {                                                // the distances stay, the walks come back empty
+        for (int64_t i = i0; i < i1; i++) a.woff[a.rofs[g] + i] = 0;
+        if (k.lane == 0) { a.wtot[g] = 0; a.status[g] = AASM_E_OVERFLOW; }
+        return;
+    }
     int64_t at = incl - sum;
     for (int64_t i = i0; i < i1; i++) { a.woff[a.rofs[g] + i] = at; at += ksw_walk_len(a, g, i); }
-    const int64_t tot = wave_bcast(incl, AASM_WAVE - 1);
     if (k.lane == 0) a.wtot[g] = tot;
 }
 AASM_DEV void kb_ksw_fill(const KCtx &k, const KswArgs &a) {
     const int64_t g = k.bid;
     if (g >= a.n_graphs || k.tid >= AASM_WAVE) return;
-    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], nf = a.nfound[g];
+    const int64_t vb = a.voff[g], eb = a.rowptr[vb], nf = a.nfound[g];
     const int32_t *depth = a.depth + vb, *bedge = a.bedge + vb, *etail = a.etail + eb, *col = a.col + eb;
     const KswNode *A = a.arena + a.aoff[g];
     const int32_t *nodes = a.qnode + a.qoff[g], *prev = a.qprev + a.qoff[g];
     int64_t *out = a.wedges + a.wbase[g];
     const int64_t lim = a.wtot[g];
+    if (lim <= 0) return;                                            // no edge to write (or the walks were capped)
     auto tree_seg = [&](int32_t x, int64_t from, int64_t n) {        // n tree edges from x into out[from, from + n)
         for (int64_t j = 0; j < n; j++) {
             const int32_t e = bedge[x];
@@ -314,7 +474,7 @@ AASM_DEV void kb_ksw_fill(const KCtx &k, const KswArgs &a) {
     for (int64_t i = k.lane; i < nf; i += AASM_WAVE) {
         int64_t p = a.woff[a.rofs[g] + i] + ksw_walk_len(a, g, i);   // one past the walk's last edge
         int64_t stop = 0, steps = 0;
-        for (int32_t c = a.rlast[a.rofs[g] + i]; c >= 0 && steps < V; c = prev[c], steps++) {
+        for (int32_t c = a.rlast[a.rofs[g] + i]; c >= 0 && steps < nf; c = prev[c], steps++) {
             const int32_t e = A[nodes[c]].e, v = col[e];
             const int64_t n = depth[v] - stop;
             tree_seg(v, p - n, n);
@@ -335,7 +495,7 @@ static inline int ksw_check_args(int64_t n_graphs, const int64_t *g_voff, const 
     int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, source, {w5, sink, out}, why);
     if (rc != AASM_OK) return rc;
     if (k < 1 || k > AASM_KSW_MAX_K) return check_fail(why, AASM_E_INVAL, "k outside 1 .. 2^24");
-    if (flags & ~(AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_HOOK_ARENA)) return check_fail(why, AASM_E_INVAL, "unknown flag");
+    if (flags & ~(AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_CYCLES | AASM_KSW_HOOK_ARENA)) return check_fail(why, AASM_E_INVAL, "unknown flag");
     for (int64_t g = 0; g < n_graphs; g++) {
         const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
         if (sink[g] < 0 || sink[g] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": sink outside it");
@@ -356,6 +516,7 @@ static inline void ksw_free_out(aasm_ksw_out *o) {
 // (aasm_pipeline.h); body(k, a)
 #define AASM_KSW_KERNELS(K)                         \
     K(KSW_K_TREE, aasm_ksw_tree, 64, 1, kb_ksw_tree)   \
+    K(KSW_K_TREE_CYC, aasm_ksw_tree_cyc, 64, 1, kb_ksw_tree_cyc) \
     K(KSW_K_HEAP, aasm_ksw_heap, 64, 1, kb_ksw_heap)   \
     K(KSW_K_ENUM, aasm_ksw_enum, 64, 1, kb_ksw_enum)   \
     K(KSW_K_COUNT, aasm_ksw_count, 64, 1, kb_ksw_count) \
@@ -393,11 +554,35 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
     int64_t *d_qcap = (int64_t *)m.alloc((size_t)G * 8), *d_rofs = (int64_t *)m.alloc((size_t)G * 8), *d_wbase = (int64_t *)m.alloc((size_t)G * 8);
     a.aoff = d_aoff; a.acap = d_acap; a.qoff = d_qoff; a.qcap = d_qcap; a.rofs = d_rofs; a.wbase = d_wbase;
     if (!m.ok) return be.err();
-    if (!be.launch_from(KSW_K_TREE, 0, G, a)) return be.err();
     std::vector<int32_t> status((size_t)G);
     std::vector<int64_t> ins((size_t)G), walks((size_t)G);
+    const bool cycles = flags & AASM_KSW_CYCLES;
+    a.cycles = cycles;
+    if (!cycles) {
+        if (!be.launch_from(KSW_K_TREE, 0, G, a)) return be.err();
+    } else {
+        // dijkstra_run's heap room (aasm_sssp.h): E + 2 entries, then 4x, 16x, 64x for the graphs that ran out of it; at 64x
+        // the kernel's bound on pushes ends a graph first
+        std::vector<char> todo((size_t)G, 1);
+        for (int64_t mult = 1; mult <= AASM_KSW_DJ_PUSHES; mult *= 4) {
+            std::vector<int64_t> ho((size_t)G + 1, 0);
+            for (int64_t g = 0; g < G; g++)
+                ho[(size_t)g + 1] = ho[(size_t)g] + (todo[(size_t)g] ? mult * (rowptr[g_voff[g + 1]] - rowptr[g_voff[g]] + 2) : 0);
+            const size_t mark = be.mark();
+            a.hoff = (const int64_t *)m.up(ho.data(), (size_t)(G + 1) * 8);
+            a.dheap = (DjEnt *)m.alloc((size_t)ho[(size_t)G] * sizeof(DjEnt));
+            if (!m.ok || !be.launch_from(KSW_K_TREE_CYC, 0, G, a) || !be.sync() || !be.d2h(status.data(), a.status, (size_t)G * 4) ||
+                !be.d2h(ins.data(), a.ins, (size_t)G * 8)) return be.err();
+            be.release(mark);
+            a.hoff = nullptr; a.dheap = nullptr;
+            bool again = false;
+            for (int64_t g = 0; g < G; g++) again |= (todo[(size_t)g] = status[(size_t)g] == AASM_E_OVERFLOW && ins[(size_t)g] < 0);
+            if (!again) break;
+        }
+    }
     if (!be.sync() || !be.d2h(status.data(), a.status, (size_t)G * 4) || !be.d2h(ins.data(), a.ins, (size_t)G * 8) ||
         !be.d2h(walks.data(), a.walks, (size_t)G * 8)) return be.err();
+    for (int64_t g = 0; g < G; g++) if (ins[(size_t)g] < 0) ins[(size_t)g] = 0;
     // bounds from the device's counts: an insert copies at most the right spine of a version of <= ins keys
     // (<= floor(log2(ins + 1)) + 1 nodes) and adds a leaf; a pop emplaces at most three entries
     std::vector<int64_t> acap((size_t)G), qcap((size_t)G), per((size_t)G);
@@ -462,6 +647,10 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
             if (!be.launch_from(KSW_K_COUNT, g0, g1, cc)) return fail(be.err());
             std::vector<int64_t> wtot((size_t)ng);
             if (!be.sync() || !be.d2h(wtot.data(), a.wtot + g0, (size_t)ng * 8)) return fail(be.err());
+            if (cycles) {                                            // a graph over the cap on walk edges: status from kb_ksw_count
+                if (!be.d2h(st.data(), a.status + g0, (size_t)ng * 4)) return fail(be.err());
+                for (int64_t g = g0; g < g1; g++) out->status[g] = st[(size_t)(g - g0)];
+            }
             int64_t nw = 0;
             for (int64_t g = g0; g < g1; g++) { wbase[g] = nw; nw += wtot[g - g0]; }
             cc.wedges = (int64_t *)m.alloc((size_t)nw * 8);

@@ -39,6 +39,42 @@ AASM_DEV bool dj_ent_less(const DjEnt &a, const DjEnt &b) {         // std::pair
     if (dist_lt<CALC_SUM_MODE>(b.d, a.d)) return false;
     return a.v < b.v;
 }
+// The binary min-heap of dijkstra(), shared with k-walks' tree kernel (aasm_ksw.h): all lanes hold the same n and entry, lane 0 stores.
+// dj_heap_push: the caller has checked n < capacity.  dj_heap_pop: n > 0; returns the top.
+AASM_DEV void dj_heap_push(DjEnt *H, int64_t &n, int lane, const Dist &dd, int32_t v) {
+    DjEnt x; x.d = dd; x.v = v; x.p0 = x.p1 = x.p2 = 0;
+    int64_t i = n++;
+    while (i > 0) {
+        const int64_t p = (i - 1) >> 1;
+        const DjEnt pe = H[p];
+        if (!uni(dj_ent_less(x, pe))) break;
+        if (lane == 0) H[i] = pe;
+        wave_fence();
+        i = p;
+    }
+    if (lane == 0) H[i] = x;
+    wave_fence();
+}
+AASM_DEV DjEnt dj_heap_pop(DjEnt *H, int64_t &n, int lane) {
+    const DjEnt top = H[0];
+    const DjEnt x = H[--n];
+    if (n > 0) {                                                     // the last entry sinks from the root
+        int64_t i = 0;
+        while (true) {
+            int64_t c = 2 * i + 1;
+            if (c >= n) break;
+            DjEnt ce = H[c];
+            if (c + 1 < n) { const DjEnt ce2 = H[c + 1]; if (uni(dj_ent_less(ce2, ce))) { ce = ce2; c++; } }
+            if (!uni(dj_ent_less(ce, x))) break;
+            if (lane == 0) H[i] = ce;
+            wave_fence();
+            i = c;
+        }
+        if (lane == 0) H[i] = x;
+        wave_fence();
+    }
+    return top;
+}
 AASM_DEV void kb_sssp_dijkstra(const KCtx &k, const SsspArgs &a) {
     const int64_t g = k.bid;
     if (g >= a.n_graphs) return;
@@ -53,42 +89,15 @@ AASM_DEV void kb_sssp_dijkstra(const KCtx &k, const SsspArgs &a) {
     const int64_t cap = a.hoff[g + 1] - a.hoff[g];
     bool over = false;
     auto push = [&](const Dist &dd, int32_t v) {
-        DjEnt x; x.d = dd; x.v = v; x.p0 = x.p1 = x.p2 = 0;
         if (n >= cap) { over = true; return; }                       // more relaxations than edges: a cycle keeps improving the order (the reference would not return)
-        int64_t i = n++;
-        while (i > 0) {
-            const int64_t p = (i - 1) >> 1;
-            const DjEnt pe = H[p];
-            if (!uni(dj_ent_less(x, pe))) break;
-            if (lane == 0) H[i] = pe;
-            wave_fence();
-            i = p;
-        }
-        if (lane == 0) H[i] = x;
-        wave_fence();
+        dj_heap_push(H, n, lane, dd, v);
     };
     const int32_t s = a.src[g];
     if (lane == 0) dg[s] = dist_zero();                              // IDENTITY_DISTANCE (:74)
     wave_fence();
     push(dist_zero(), s);
     while (n > 0 && !over) {
-        const DjEnt top = H[0];
-        const DjEnt x = H[--n];
-        if (n > 0) {                                                 // pop: the last entry sinks from the root
-            int64_t i = 0;
-            while (true) {
-                int64_t c = 2 * i + 1;
-                if (c >= n) break;
-                DjEnt ce = H[c];
-                if (c + 1 < n) { const DjEnt ce2 = H[c + 1]; if (uni(dj_ent_less(ce2, ce))) { ce = ce2; c++; } }
-                if (!uni(dj_ent_less(ce, x))) break;
-                if (lane == 0) H[i] = ce;
-                wave_fence();
-                i = c;
-            }
-            if (lane == 0) H[i] = x;
-            wave_fence();
-        }
+        const DjEnt top = dj_heap_pop(H, n, lane);
         const int32_t v = uni(top.v);
         const Dist dv = uni(top.d);
         if (!uni(dist_eq(dv, dg[v]))) continue;                      // :79 (operator!=)

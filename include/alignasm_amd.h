@@ -239,9 +239,23 @@ int  aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
  * reference's with the monotonic allocator's queue ties (node arena index, then insertion index).  A walk is reported as
  * caller CSR positions (global edge ids), source -> sink: a tree edge is the edge whose relaxation set best[], a sidetrack
  * the edge its heap node was inserted for, so parallel edges stay apart.  A graph with a cycle gets status AASM_E_INVAL and
- * no walks; the other graphs of the batch are solved.  Every array is allocated by the library: release with aasm_ksw_free. */
+ * no walks; the other graphs of the batch are solved.  Every array is allocated by the library: release with aasm_ksw_free.
+ *
+ * With AASM_KSW_CYCLES every graph of the call is solved as the reference does with is_dag = false, negative_edge = false
+ * (its default, :65,185): the shortest-path tree is the one dijkstra() from the sink over the reversed graph leaves (:69-87),
+ * also on a graph that happens to be acyclic, where it can differ from the DAG relaxation's tree among tied distances.  Walks
+ * may repeat vertices and run through cycles and through the sink.  Three limits hold there, each per graph, the rest of the
+ * batch being solved:
+ *  - dijkstra makes at most 64 * (E + 2) pushes.  A cycle can improve a distance for ever (a larger qul_nonzero / qul_total
+ *    ratio orders first and is not monotone under addition; the reference does not return): status AASM_E_OVERFLOW, no walks.
+ *    A graph whose best[] is no tree into the sink (the sink's own distance improved round a cycle; the reference does not
+ *    return either) gets AASM_E_INVAL and no walks, with d5 / best as dijkstra left them.
+ *  - a walk has any number of edges: when a queued distance leaves |qry_score|, |ref_score| < 2^62 or anom, qul_nonzero,
+ *    qul_total < 2^30 the enumeration ends with AASM_E_OVERFLOW; n_found, dist5 and the walks hold what was found before.
+ *  - a graph whose walks hold more than 2^28 edges together keeps n_found and dist5, gets empty walk ranges and AASM_E_OVERFLOW. */
 #define AASM_KSW_WALKS      0x1     /* fill walk_off / walk_edges                                                     */
 #define AASM_KSW_TREE       0x2     /* fill d5 / best                                                                 */
+#define AASM_KSW_CYCLES     0x4     /* graphs may hold cycles: the reference's is_dag = false                         */
 #define AASM_KSW_HOOK_ARENA 0x100   /* test hook, 0 in production: fill hook_arena / hook_hroot                       */
 typedef struct aasm_ksw_out {
     int64_t  n_graphs, k;
@@ -252,7 +266,7 @@ typedef struct aasm_ksw_out {
     int64_t *d5;               /* [VT * 5] distance to the sink (PafDistance::max() where there is none); AASM_KSW_TREE */
     int32_t *best;             /* [VT] next vertex towards the sink, local id (-1 = none); AASM_KSW_TREE              */
     int64_t *heap_nodes;       /* [n_graphs] heap nodes the reference allocates                                     */
-    int32_t *status;           /* [n_graphs] 0, AASM_E_INVAL (cycle), AASM_E_OVERFLOW (heap or queue capacity)      */
+    int32_t *status;           /* [n_graphs] 0, AASM_E_INVAL (cycle), AASM_E_OVERFLOW (a capacity or limit above) */
     int64_t *hook_arena;       /* AASM_KSW_HOOK_ARENA: {rank, key[5], u, v, left, right} per node, graph after graph */
     int32_t *hook_hroot;       /* AASM_KSW_HOOK_ARENA: [VT] heap root as the graph's arena index (-1 = nullptr)      */
 } aasm_ksw_out;

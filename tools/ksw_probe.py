@@ -1,6 +1,8 @@
 """aasm_k_shortest_walks on the C3 generator's contig DAGs, beside the pipeline's own K6-K8 phases on the same contigs and the
 CPU oracle.  One JSON line per (contigs, K):
   ksw_ms       minimum over --reps of the whole entry, wall clock (host checks, uploads, the five kernels, downloads; walks=False)
+  ksw_cyc_ms   with --cycles: the same with cycles=True (the tree of dijkstra() from the sink, the solver's is_dag = false), from the
+               same run; n_found and the distances' first keys (score sum, anom) must equal the default mode's
   pipe_ms      minimum over --reps of the pipeline's sptree + heap_prep + heap + enum phases (HIP events, timing=True)
   oracle_ms    the CPU oracle (oracle_generic_kwalks, one thread) on --oracle-sample graphs, scaled to all of them
 The first call of each configuration is a warm-up and is not counted.  Checks n_found / heap_nodes against the pipeline."""
@@ -27,6 +29,7 @@ ap.add_argument("--recs", type=int, default=1000)
 ap.add_argument("--seed", type=int, default=21)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--oracle-sample", type=int, default=40)
+ap.add_argument("--cycles", action="store_true", help="time cycles=True beside the default mode")
 a = ap.parse_args()
 
 for nc in (int(x) for x in a.contigs.split(",")):
@@ -52,6 +55,18 @@ for nc in (int(x) for x in a.contigs.split(",")):
             if r:
                 wall.append((time.perf_counter() - t) * 1e3)
         ok = bool(np.array_equal(got["n_found"], want["kfound"]) and np.array_equal(got["heap_nodes"], want["h_cnt"]))
+        cyc = {}
+        if a.cycles:
+            wall_c = []
+            for r in range(a.reps + 1):
+                t = time.perf_counter()
+                got_c = api.k_shortest_walks(*args, walks=False, tree=False, cycles=True)
+                if r:
+                    wall_c.append((time.perf_counter() - t) * 1e3)
+            same = bool(np.array_equal(got_c["n_found"], got["n_found"]) and not got_c["status"].any() and
+                        np.array_equal(got_c["dist"][:, :, :2].sum(2), got["dist"][:, :, :2].sum(2)) and
+                        np.array_equal(got_c["dist"][:, :, 2], got["dist"][:, :, 2]))
+            cyc = {"ksw_cyc_ms": round(min(wall_c), 2), "cycles_same_keys": same}
         rng = np.random.default_rng(1)
         pick = rng.choice(len(contigs), min(a.oracle_sample, len(contigs)), replace=False)
         t = time.perf_counter()
@@ -63,6 +78,6 @@ for nc in (int(x) for x in a.contigs.split(",")):
                           with_paths=False)
         oracle_ms = (time.perf_counter() - t) * 1e3 * len(contigs) / max(1, len(pick))
         print(json.dumps({"contigs": nc, "graphs": len(contigs), "K": K, "V": int(batch["g_voff"][-1]), "E": int(batch["rowptr"][-1]),
-                          "ksw_ms": round(min(wall), 2), "pipe_ms": round(min(pipe), 3), "oracle_ms": round(oracle_ms, 1),
+                          "ksw_ms": round(min(wall), 2), **cyc, "pipe_ms": round(min(pipe), 3), "oracle_ms": round(oracle_ms, 1),
                           "walks": int(got["n_found"].sum()), "heap_nodes": int(got["heap_nodes"].sum()), "equal_to_pipeline": ok}), flush=True)
     db.close()
