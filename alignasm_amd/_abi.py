@@ -120,6 +120,42 @@ class DevOut(C.Structure):
                                           "all_elems", "ctg_status")]
 
 
+# ---- cut plans (aasm_cut_plans_device / aasm_writer_append_cuts) ----------------------------------------------------------------
+AASM_CUT_IS_CUT, AASM_CUT_IRREGULAR = 0x1, 0x2
+AASM_CUT_E_TAG, AASM_CUT_E_INS_CLIP, AASM_CUT_E_EDIT, AASM_CUT_E_RECORD = 0x10, 0x20, 0x40, 0x80
+AASM_CUT_ERRORS = AASM_CUT_E_TAG | AASM_CUT_E_INS_CLIP | AASM_CUT_E_EDIT | AASM_CUT_E_RECORD
+
+
+class CutPlan(C.Structure):
+    """aasm_cut_plan: what a PAF row needs beyond its element's coordinates (48 bytes)."""
+    _fields_ = [("keep_lo", C.c_int64), ("keep_hi", C.c_int64), ("head_keep", C.c_int64), ("tail_keep", C.c_int64),
+                ("mat_num", C.c_int32), ("aln_len", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+CUT_DT = np.dtype([("keep_lo", np.int64), ("keep_hi", np.int64), ("head_keep", np.int64), ("tail_keep", np.int64),
+                   ("mat_num", np.int32), ("aln_len", np.int32), ("flags", np.int32), ("reserved", np.int32)])
+
+
+class DevCuts(C.Structure):
+    """aasm_dev_cuts: caller-owned DEVICE plan arrays, parallel to DevOut's element lists."""
+    _fields_ = [(n, C.c_void_p) for n in ("main", "alt", "all")]
+
+
+class Cuts(C.Structure):
+    """aasm_cuts: HOST plan arrays, parallel to BatchOut's element lists."""
+    _fields_ = [("n_main", C.c_int64), ("n_alt", C.c_int64), ("n_all", C.c_int64), ("main", C.c_void_p), ("alt", C.c_void_p), ("all", C.c_void_p)]
+
+
+def render_cut(plan, tag):
+    """The cs tag of a row from its plan and the record's own tag (both str or both bytes); plans without AASM_CUT_IRREGULAR."""
+    if not int(plan["flags"]) & AASM_CUT_IS_CUT:
+        return tag
+    colon, empty = (":", "") if isinstance(tag, str) else (b":", b"")
+    num = (lambda v: str(int(v))) if isinstance(tag, str) else (lambda v: str(int(v)).encode())
+    return (tag[:5] + (colon + num(plan["head_keep"]) if plan["head_keep"] else empty) + tag[int(plan["keep_lo"]):int(plan["keep_hi"])]
+            + (colon + num(plan["tail_keep"]) if plan["tail_keep"] else empty))
+
+
 class SynthCfg(C.Structure):
     _fields_ = [
         ("n_contigs", C.c_int64), ("recs_per_contig", C.c_int64), ("seed", C.c_uint64), ("dense", C.c_int32),

@@ -14,8 +14,8 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_E_INVAL, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevOut, HostBatch, KswOut, Opts,
-                   OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
+from ._abi import (AASM_E_INVAL, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, CUT_DT, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+                   HostBatch, KswOut, Opts, OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AASM_LIB_OVERRIDE") or os.path.join(_HERE, "libalignasm_amd.so")   # override: diagnostic builds (tools/)
@@ -77,7 +77,7 @@ EXPORTED = [
     "aasm_result_stats", "aasm_result_fetch", "aasm_result_free", "aasm_free_out", "aasm_upload_batch", "aasm_upload_free",
     "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
-    "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free",
+    "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
 ]
 
 
@@ -216,8 +216,22 @@ class Paf:
         """Write the batch as PAF text (rows with cs tags) to `path`."""
         _check(LIB.aasm_paf_save(self._h, os.fsencode(path)))
 
-    def write_outputs(self, out: BatchOut, main_path, alt_path, all_path):
-        _check(LIB.aasm_paf_write_outputs(self._h, C.byref(out), os.fsencode(main_path), os.fsencode(alt_path), os.fsencode(all_path)))
+    def write_outputs(self, out: BatchOut, main_path, alt_path, all_path, cuts=None):
+        """The three output files.  cuts: {"main", "alt", "all"} -> numpy CUT_DT arrays parallel to out's element lists (cut plans
+        fetched from the device, cuts_to_numpy): the rows are written from them (aasm_writer_append_cuts), byte for byte the same."""
+        if cuts is None:
+            _check(LIB.aasm_paf_write_outputs(self._h, C.byref(out), os.fsencode(main_path), os.fsencode(alt_path), os.fsencode(all_path)))
+            return
+        arr = [np.ascontiguousarray(cuts[k], dtype=CUT_DT) for k in ("main", "alt", "all")]
+        cs = Cuts(*(len(a) for a in arr), *(a.ctypes.data if len(a) else None for a in arr))
+        w = C.c_void_p()
+        _check(LIB.aasm_writer_open(os.fsencode(main_path), os.fsencode(alt_path), os.fsencode(all_path), C.byref(w)))
+        rc = LIB.aasm_writer_append_cuts(w, self._h, C.byref(out), C.byref(cs), C.c_int64(0))
+        msg = (LIB.aasm_last_error() or b"").decode(errors="replace")
+        rc2 = LIB.aasm_writer_close(w, 1 if rc == AASM_OK else 0)     # (a failed append leaves no file behind)
+        if rc != AASM_OK:
+            raise AlignasmError(rc, msg)
+        _check(rc2)
 
     def close(self):
         if self._h:
@@ -259,8 +273,16 @@ def solve_batch(batch, max_paths=10000, non_skip_linkable=False, device=0, timin
 class DeviceBatch:
     """A batch uploaded once to HBM; solve() can then be timed without PCIe traffic."""
 
-    def __init__(self, batch, device=0):
+    def __init__(self, batch, device=0, cs_only=False):
+        """cs_only: upload the batch in its cs form - the cs text and no match ranges, as a Paf read with device_ranges - also
+        when the batch holds match ranges as well (a synthetic Paf): the solve derives them on the GPU, and the tags are on the
+        device for DeviceResult.to_torch(cuts=...)."""
         view = batch.view if isinstance(batch, HostBatch) else batch.view()
+        if cs_only:
+            if not view.cs_text or not view.rec_cs_off:
+                raise AlignasmError(AASM_E_INVAL, "cs_only: the batch holds no cs text")
+            view = BatchIn.from_buffer_copy(view)
+            view.rng_qry_l = view.rng_qry_r = view.rng_ref_l = None
         self._keep = batch
         self.device = device
         self._up = C.c_void_p()
@@ -325,11 +347,14 @@ class DeviceResult:
         """aasm_result_export as is: returns the C-ABI code (0 = enqueued on `stream`, a hipStream_t handle or 0)."""
         return int(LIB.aasm_result_export(self._h, C.byref(sizes), C.byref(dst), C.c_void_p(stream or 0)))
 
-    def to_torch(self, stream=None):
+    def to_torch(self, stream=None, cuts=None):
         """The result in torch tensors on its device, packed there (aasm_result_export): the keys of unpack_out() without
         `stats`; element lists are int64 [n, 5] tensors holding the 40-byte rows (column 4 is ctg_index / is_alt as two int32:
         `.view(torch.int32)`).  Asynchronous on `stream` (default: the device's current torch stream); the tensors outlive the
-        next solve on the device."""
+        next solve on the device.
+        cuts: the DeviceBatch the result was solved from (one with cs tags on the device: a Paf read with device_ranges) - the
+        dict then also holds `main_cut`, `alt_cut`, `all_cut`, int64 [n, 6] tensors of the elements' 48-byte cut plans
+        (aasm_cut_plans_device; `cuts_to_numpy`), made on the same stream right behind the export."""
         import torch
         _check_one_hip_runtime()
         dev = torch.device("cuda", self.device)
@@ -349,7 +374,16 @@ class DeviceResult:
         ptr = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
         dst = DevOut(ptr(d["main_off"]), ptr(d["alt_off"]), ptr(d["all_path_off"]), ptr(d["all_elem_off"]), ptr(d["main"]),
                      ptr(d["alt"]), ptr(d["all"]), ptr(d["status"]))
-        _check(self.export_raw(OutSizes(*(sz[n] for n, _ in OutSizes._fields_)), dst, stream.cuda_stream))
+        csz = OutSizes(*(sz[n] for n, _ in OutSizes._fields_))
+        _check(self.export_raw(csz, dst, stream.cuda_stream))
+        if cuts is not None:
+            with torch.cuda.device(dev):
+                plans = {k: torch.empty((sz[n], 6), dtype=torch.int64, device=dev) for k, n in (("main_cut", "n_main"), ("alt_cut", "n_alt"), ("all_cut", "n_all_elems"))}
+            for t in plans.values():
+                t.record_stream(stream)
+            dc = DevCuts(ptr(plans["main_cut"]), ptr(plans["alt_cut"]), ptr(plans["all_cut"]))
+            _check(cut_plans_raw(cuts.dev_view, csz, dst, dc, self.device, stream.cuda_stream))
+            d.update(plans)
         d["n_contigs"] = c
         return d
 
@@ -371,6 +405,21 @@ class DeviceResult:
             self.close()
         except Exception:
             pass
+
+
+def cut_plans_raw(dev_view: BatchIn, sizes: OutSizes, dev_out: DevOut, dst: DevCuts, device=0, stream=0):
+    """aasm_cut_plans_device as is: returns the C-ABI code (0 = enqueued on `stream`, a hipStream_t handle or 0)."""
+    return int(LIB.aasm_cut_plans_device(C.byref(dev_view), C.byref(sizes), C.byref(dev_out), C.byref(dst), int(device), C.c_void_p(stream or 0)))
+
+
+def cuts_to_numpy(d):
+    """The cut plans of DeviceResult.to_torch(cuts=...)'s dict as {"main", "alt", "all"} -> numpy CUT_DT arrays (what
+    Paf.write_outputs takes).  The copies are ordered on the device's current torch stream, as torch_to_numpy's."""
+    out = {}
+    for k in ("main", "alt", "all"):
+        t = d[k + "_cut"].contiguous().cpu().numpy()
+        out[k] = np.ascontiguousarray(t).view(CUT_DT).reshape(-1) if t.size else np.zeros(0, CUT_DT)
+    return out
 
 
 _ONE_RUNTIME = False

@@ -255,6 +255,31 @@ AASM_DEV int64_t wave_sum(int64_t x) {
 }
 
 // ------------------------------------------------------------------------------------
+// short-form cs tags, a lane per tag: what K0 (kb_cs_ranges) and the cut plans (kb_cut_plan) share of the tokenizer
+// (parse_short_cs, paf_data.cpp:29-72)
+// ------------------------------------------------------------------------------------
+AASM_DEV bool cs_is_op(int c) { return c == ':' || c == '*' || c == '+' || c == '-'; }
+AASM_DEV bool cs_is_alpha(int c) { return (unsigned)((c | 32) - 'a') < 26u; }   // isalpha, "C" locale
+// The next nb <= 8 bytes of a tag of len bytes from pos on, first byte lowest: one aligned eight-byte load where eight bytes
+// are left, else byte loads up to the next aligned word or the end.  Never reads outside [cs, cs + len).
+AASM_DEV uint64_t cs_next_word(const uint8_t *cs, int64_t pos, int64_t len, int &nb) {
+    nb = (int)((len - pos < 8) ? (len - pos) : 8);
+    const int mis = (int)((uintptr_t)(cs + pos) & 7);
+    if (mis == 0 && nb == 8) return *(const uint64_t *)(cs + pos);
+    if (nb > 8 - mis) nb = 8 - mis;
+    uint64_t wd = 0;
+    for (int t = 0; t < nb; t++) wd |= (uint64_t)cs[pos + t] << (8 * t);
+    return wd;
+}
+// One more digit of a ':' run's length, as std::from_chars<int64_t> reads it: any number of digits, leading zeros included;
+// -1 once the value is beyond INT64_MAX (out_of_range), and from there on
+AASM_DEV int64_t cs_add_digit(int64_t val, unsigned dg) {
+    if ((uint64_t)val < 100000000ull) return (int64_t)((uint32_t)val * 10u + dg);   // (up to nine digits: 32-bit arithmetic, no overflow to look for)
+    const uint64_t nv = (uint64_t)val * 10u + dg;
+    return (val < 0 || val > INT64_MAX / 10 || nv > (uint64_t)INT64_MAX) ? -1 : (int64_t)nv;
+}
+
+// ------------------------------------------------------------------------------------
 // PafDistance (reference: src/paf_data.hpp:121-189) in 32 bytes.
 // anom / qul_nonzero / qul_total are path-length-bounded counters -> int32; the two
 // scores stay int64.  calc_sum_chk only feeds asserts in the reference and is dropped.

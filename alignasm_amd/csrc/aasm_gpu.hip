@@ -21,6 +21,7 @@
 
 #include "aasm_pipeline.h"
 #include "aasm_ksw.h"
+#include "aasm_cut.h"
 #include "aasm_paf.hpp"
 
 namespace aasm {
@@ -63,6 +64,11 @@ AASM_SSSP_KERNELS(K, KL)
 #define K(id, sym, block, lanes, ...) \
     __global__ void __launch_bounds__(block) sym(int64_t g0, KswArgs a) { AASM_KCTX(g0 + (int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
 AASM_KSW_KERNELS(K)
+#undef K
+// the cut plans of an exported result (aasm_cut_plans_device; body in aasm_cut.h)
+#define K(id, sym, block, lanes, lds, ...) \
+    __global__ void __launch_bounds__(block) sym(CutArgs a) { AASM_SMEM(lds); AASM_KCTX((int64_t)blockIdx.x, smem); __VA_ARGS__(k, a); }
+AASM_CUT_KERNELS(K)
 #undef K
 
 // ---- T1 truth tables on the device (test entry aasm_debug_predicates) ------------------
@@ -867,6 +873,47 @@ int aasm_result_export(aasm_result *res, const aasm_out_sizes *sz, const aasm_de
     pack_export(be, res->w, res->pk, *dst);
     if (be.failed()) return AASM_E_HIP;
     if ((e = hipEventRecord(ev_out, s)) != hipSuccess) { set_last_error(hip_err("hipEventRecord", e)); return AASM_E_HIP; }
+    return AASM_OK;
+}
+
+// ---- cut plans of an exported result (aasm_cut.h): one launch on the caller's stream, nothing else ----
+namespace {
+struct CutGpu {
+    hipStream_t stream;
+    hipError_t err = hipSuccess;
+    void launch_cut(int kc, int64_t nblocks, int nthreads, const CutArgs &a) {
+        switch (kc) {
+#define K(id, sym, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, stream, a); break;
+            AASM_CUT_KERNELS(K)
+#undef K
+        }
+        err = hipGetLastError();
+    }
+};
+}
+int aasm_cut_plans_device(const aasm_batch_in *dev_in, const aasm_out_sizes *sz, const aasm_dev_out *dev_out, const aasm_dev_cuts *dst,
+                          int device, void *stream) {
+    if (!dev_in || !sz || !dev_out || !dst) return AASM_E_INVAL;
+    if (!dev_in->cs_text || !dev_in->rec_cs_off) { set_last_error("the device batch carries no cs text (it was uploaded with match ranges)"); return AASM_E_INVAL; }
+    CutArgs a;
+    if (!cut_args(*dev_in, *sz, *dev_out, *dst, a)) { set_last_error("sizes do not fit the batch"); return AASM_E_INVAL; }
+    int rc = ctx_init(device);
+    if (rc != AASM_OK) return rc;
+    hipSetDevice(device);
+    const int64_t C = a.C, R = a.R;
+    if (!dev_buffer_ok(dev_in->ctg_rec_off, C + 1, 8, device) || !dev_buffer_ok(dev_in->qry_str, R, 8, device) || !dev_buffer_ok(dev_in->qry_end, R, 8, device) ||
+        !dev_buffer_ok(dev_in->aln_fwd, R, 1, device) || !dev_buffer_ok(dev_in->rec_cs_off, R + 1, 8, device) || !dev_buffer_ok(dev_in->cs_text, R > 0 ? 1 : 0, 1, device) ||   // (the text's length is rec_cs_off[R], on the device: only its base is checked)
+       
+        !dev_buffer_ok(dev_out->main_off, C + 1, 8, device) || !dev_buffer_ok(dev_out->alt_off, C + 1, 8, device) || !dev_buffer_ok(dev_out->all_path_off, C + 1, 8, device) ||
+        !dev_buffer_ok(dev_out->all_elem_off, a.NP + 1, 8, device) || !dev_buffer_ok(dev_out->main_elems, a.n[0], 8, device) ||
+        !dev_buffer_ok(dev_out->alt_elems, a.n[1], 8, device) || !dev_buffer_ok(dev_out->all_elems, a.n[2], 8, device) ||
+        !dev_buffer_ok(dst->main, a.n[0], 8, device) || !dev_buffer_ok(dst->alt, a.n[1], 8, device) || !dev_buffer_ok(dst->all, a.n[2], 8, device)) {
+        set_last_error("an array is NULL, not device memory of the device, or misaligned");
+        return AASM_E_INVAL;
+    }
+    CutGpu be{(hipStream_t)stream};
+    cut_launch(be, a);
+    if (be.err != hipSuccess) { set_last_error(hip_err("kernel launch", be.err)); return AASM_E_HIP; }
     return AASM_OK;
 }
 

@@ -164,7 +164,6 @@ AASM_DEV bool coord_ok(int64_t x) { return x >= 0 && x < AASM_COORD_LIMIT; }
 // Bit-exact with the host codec (tests); a malformed tag (any of the tokenizer's errors or the
 // consumption check, :119-122) puts the record's index into cs_bad and the solve fails with
 // AASM_E_PARSE.
-AASM_DEV bool cs_is_op(int c) { return c == ':' || c == '*' || c == '+' || c == '-'; }
 struct CsScan {
     int64_t q, rr, val, n, cnt, o0;
     int32_t plen;
@@ -213,11 +212,8 @@ AASM_DEV void kb_cs_ranges(const KCtx &k, const WS &w) {
     s.val = 0; s.n = 0; s.plen = 0; s.t = 0;
     s.bad = len < 5 || cs[0] != 'c' || cs[1] != 's' || cs[2] != ':' || cs[3] != 'Z' || cs[4] != ':';   // :30-33
     for (int64_t pos = 5; pos < len && !s.bad; ) {
-        uint64_t wd = 0;                                             // the next <= 8 bytes, first byte lowest
-        int nb = (int)((len - pos < 8) ? (len - pos) : 8);
-        const int mis = (int)((uintptr_t)(cs + pos) & 7);
-        if (mis == 0 && nb == 8) wd = *(const uint64_t *)(cs + pos);
-        else { if (nb > 8 - mis) nb = 8 - mis; for (int t = 0; t < nb; t++) wd |= (uint64_t)cs[pos + t] << (8 * t); }   // up to the next aligned word / the end
+        int nb;
+        uint64_t wd = cs_next_word(cs, pos, len, nb);                // the next <= 8 bytes, first byte lowest
         pos += nb;
         for (int t = 0; t < nb && !s.bad; t++) {
             const int c = (int)(wd & 0xff);
@@ -228,15 +224,8 @@ AASM_DEV void kb_cs_ranges(const KCtx &k, const WS &w) {
             } else if (s.t == ':') {
                 const unsigned dg = (unsigned)(c - '0');
                 if (dg > 9u) s.bad = true;
-                else {                                               // std::from_chars<int64_t>: any number of digits, leading zeros included, value <= INT64_MAX
-                    if ((uint64_t)s.val < 100000000ull) s.val = (int64_t)((uint32_t)s.val * 10u + dg);   // (up to nine digits: 32-bit arithmetic, no overflow to look for)
-                    else {
-                        const uint64_t nv = (uint64_t)s.val * 10u + dg;
-                        s.val = (s.val < 0 || s.val > INT64_MAX / 10 || nv > (uint64_t)INT64_MAX) ? -1 : (int64_t)nv;
-                    }
-                    s.plen = 1;
-                }
-            } else if (s.t && (unsigned)((c | 32) - 'a') < 26u) s.plen++;
+                else { s.val = cs_add_digit(s.val, dg); s.plen = 1; }
+            } else if (s.t && cs_is_alpha(c)) s.plen++;
             else s.bad = true;                                       // not a cs character, or payload before any operation (:66-68)
         }
     }

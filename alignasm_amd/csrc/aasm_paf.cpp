@@ -751,8 +751,9 @@ static void put_columns(std::string &buf, const std::string &name, const aasm_pa
     put_i64(buf, paf.map_qul[r]); buf += '\t';
 }
 
-// an output row: the 12 columns of the (re-cut) record + tp + xi + its edited cs tag
-static int emit_line(const aasm_paf &paf, int64_t contig, const std::string &name, const aasm_out_elem &o,
+// an output row: the 12 columns of the (re-cut) record + tp + xi + its edited cs tag.  cp: the element's cut plan
+// (aasm_writer_append_cuts: mat_num, aln_len and the tag's pieces come from it, no walk over the tag), or nullptr
+static int emit_line(const aasm_paf &paf, int64_t contig, const std::string &name, const aasm_out_elem &o, const aasm_cut_plan *cp,
                      std::string &buf, std::string &err) {
     const int64_t r = paf.ctg_rec_off[contig] + o.ctg_index;
     if (o.ctg_index < 0 || r >= paf.ctg_rec_off[contig + 1]) { err = "output element refers to a record outside its contig"; return AASM_E_INVAL; }
@@ -763,8 +764,28 @@ static int emit_line(const aasm_paf &paf, int64_t contig, const std::string &nam
     const int64_t cs_len = paf.cs_off[r + 1] - paf.cs_off[r];
     const bool uncut = o.edited_qry_str == paf.qry_str[r] && o.edited_qry_end == paf.qry_end[r];   // not cut: the record's own cs / mat_num / aln_len (paf_data.cpp:131-136)
     bool planned = false;
+    if (cp) {
+        const int32_t f = cp->flags;
+        if (f & AASM_CUT_E_RECORD) { err = "output element refers to a record outside its contig"; return AASM_E_INVAL; }
+        if (f & AASM_CUT_E_TAG) {                                              // the tokenizer's own message where the tag shows it
+            const CsErr te = cs_diagnose(cs, cs_len, fwd, paf.qry_str[r], paf.qry_end[r], paf.ref_str[r], paf.ref_end[r]);
+            err = cs_err_text(te == CS_OK || te == CS_E_CONSUME ? CS_E_TAG : te);
+            return AASM_E_PARSE;
+        }
+        if (f & (AASM_CUT_E_INS_CLIP | AASM_CUT_E_EDIT)) { err = cs_err_text(f & AASM_CUT_E_INS_CLIP ? CS_E_INS_CLIP : CS_E_EDIT); return AASM_E_PARSE; }
+        if (((f & AASM_CUT_IS_CUT) == 0) != uncut) { err = "cut plan does not belong to its output element"; return AASM_E_INVAL; }
+    }
     if (uncut) { ed.mat_num = paf.mat_num[r]; ed.aln_len = paf.aln_len[r]; ed.is_cut = false; }
-    else {
+    else if (cp && !(cp->flags & AASM_CUT_IRREGULAR)) {
+        const bool some = cp->keep_lo != cp->keep_hi;
+        if (cp->head_keep < 0 || cp->tail_keep < 0 || (some && (cp->keep_lo < 5 || cp->keep_lo > cp->keep_hi || cp->keep_hi > cs_len))) {
+            err = "cut plan reaches outside the record's cs tag";
+            return AASM_E_INVAL;
+        }
+        pl.head_keep = cp->head_keep; pl.tail_keep = cp->tail_keep;
+        pl.v0 = some ? cs + cp->keep_lo : nullptr; pl.v1 = some ? cs + cp->keep_hi : nullptr;
+        planned = true; ed.mat_num = cp->mat_num; ed.aln_len = cp->aln_len;
+    } else {
         const CsErr pe = plan_cut(cs, cs_len, fwd, paf.qry_str[r], paf.qry_end[r], o.edited_qry_str, o.edited_qry_end, o.edited_ref_str, o.edited_ref_end, pl);
         if (pe != CS_OK) { err = cs_err_text(pe); return AASM_E_PARSE; }
         if (!pl.irregular) { planned = true; ed.mat_num = pl.mat_num; ed.aln_len = pl.aln_len; }
@@ -1021,12 +1042,22 @@ int aasm_writer_close(aasm_writer *w, int commit) {
     return rc;
 }
 
-// rows of contigs [contig0, contig0 + out->n_contigs) of `paf`; ranges must arrive in order, without gaps
-int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, int64_t contig0) {
+}  // extern "C"
+
+// rows of contigs [contig0, contig0 + out->n_contigs) of `paf`; ranges must arrive in order, without gaps.  cuts: the elements'
+// cut plans (aasm_writer_append_cuts), or nullptr
+static int writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, const aasm_cuts *cuts, int64_t contig0) {
     if (!w || !paf || !out || contig0 != w->next_contig || contig0 + out->n_contigs > paf->n_contigs()) return AASM_E_INVAL;
     if (!paf->has_cs) { set_last_error("PAF was generated without cs strings"); return AASM_E_INVAL; }
     if (w->failed) return AASM_E_IO;
     const int64_t C = out->n_contigs;
+    if (cuts) {
+        const int64_t nm = out->main_off[C], na = out->alt_off[C], ne = out->all_elem_off[out->all_path_off[C]];
+        if (cuts->n_main != nm || cuts->n_alt != na || cuts->n_all != ne || (nm && !cuts->main) || (na && !cuts->alt) || (ne && !cuts->all)) {
+            set_last_error("cut plans are not parallel to the result's element lists");
+            return AASM_E_INVAL;
+        }
+    }
     // upper estimate of a contig's output bytes: every element costs its record's cs tag + the 14 other columns
     auto bytes_prefix = [&](const int64_t *off, const aasm_out_elem *el, int64_t extra_name) {
         std::vector<int64_t> wp((size_t)C + 1, 0);
@@ -1053,7 +1084,7 @@ int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out
         const std::vector<int64_t> wp = bytes_prefix(out->main_off, out->main_elems, 0);
         rcs[0] = append_rounds(w->fd[0], w->off[0], w->path[0].c_str(), C, wp, w->bufs[0], 0, [&](int64_t c, std::string &buf, std::string &err) {
             for (int64_t k = out->main_off[c]; k < out->main_off[c + 1]; k++) {
-                const int r = emit_line(*paf, contig0 + c, paf->ctg_name[contig0 + c], out->main_elems[k], buf, err);
+                const int r = emit_line(*paf, contig0 + c, paf->ctg_name[contig0 + c], out->main_elems[k], cuts ? cuts->main + k : nullptr, buf, err);
                 if (r != AASM_OK) return r;
             }
             return (int)AASM_OK;
@@ -1066,7 +1097,7 @@ int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out
             const std::vector<int64_t> wp = bytes_prefix(out->alt_off, out->alt_elems, 0);
             rcs[1] = append_rounds(w->fd[1], w->off[1], w->path[1].c_str(), C, wp, w->bufs[1], side_threads, [&](int64_t c, std::string &buf, std::string &err) {
                 for (int64_t k = out->alt_off[c]; k < out->alt_off[c + 1]; k++) {
-                    const int r = emit_line(*paf, contig0 + c, paf->ctg_name[contig0 + c], out->alt_elems[k], buf, err);
+                    const int r = emit_line(*paf, contig0 + c, paf->ctg_name[contig0 + c], out->alt_elems[k], cuts ? cuts->alt + k : nullptr, buf, err);
                     if (r != AASM_OK) return r;
                 }
                 return (int)AASM_OK;
@@ -1083,7 +1114,7 @@ int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out
                     ++cnt;
                     const std::string name = paf->ctg_name[contig0 + c] + "." + std::to_string(cnt);
                     for (int64_t k = out->all_elem_off[pth]; k < out->all_elem_off[pth + 1]; k++) {
-                        const int r = emit_line(*paf, contig0 + c, name, out->all_elems[k], buf, err);
+                        const int r = emit_line(*paf, contig0 + c, name, out->all_elems[k], cuts ? cuts->all + k : nullptr, buf, err);
                         if (r != AASM_OK) return r;
                     }
                 }
@@ -1101,6 +1132,14 @@ int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out
     for (int i = 0; i < 3; i++)
         if (rcs[i] != AASM_OK) { w->failed = true; set_last_error(errs[i]); return rcs[i]; }   // (the main file's error first: file order of the reference's writers)
     return AASM_OK;
+}
+
+extern "C" {
+
+int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, int64_t contig0) { return writer_append(w, paf, out, nullptr, contig0); }
+int aasm_writer_append_cuts(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, const aasm_cuts *cuts, int64_t contig0) {
+    if (!cuts) return AASM_E_INVAL;
+    return writer_append(w, paf, out, cuts, contig0);
 }
 
 // the files of a session that ended with rc: kept if rc is AASM_OK, else removed, rc's message kept

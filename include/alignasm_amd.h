@@ -317,6 +317,38 @@ int  aasm_result_sizes(aasm_result *res, aasm_out_sizes *sz);
  * device waits for the exports in flight before it reuses the workspace; the caller's buffers are never touched again.  */
 int  aasm_result_export(aasm_result *res, const aasm_out_sizes *sz, const aasm_dev_out *dst, void *stream);
 
+/* ---- cut plans: what a PAF row needs beyond an element's coordinates (get_edited_paf_data, src/paf_data.cpp:125-220) ------------
+ * A re-cut record's cs tag is three pieces: [":" head_keep] + ONE stretch of the record's own tag + [":" tail_keep] (only the
+ * first and the last kept ':' run can lose bases; every other operation stays or goes whole).  A plan holds the stretch as byte
+ * offsets, so a row costs its writer one copy and no walk over the tag.                                                       */
+typedef struct aasm_cut_plan {          /* 48 bytes, 8-byte aligned */
+    int64_t keep_lo, keep_hi;           /* byte offsets inside the record's own tag (from its 'c' of "cs:Z:") of the operations kept whole: one stretch [keep_lo, keep_hi); equal = none */
+    int64_t head_keep, tail_keep;       /* bases left of a shortened first / last ':' run in TEXT order; 0 = none */
+    int32_t mat_num, aln_len;           /* PafEditData's, with the reference's int32 arithmetic */
+    int32_t flags;                      /* AASM_CUT_* */
+    int32_t reserved;                   /* 0 */
+} aasm_cut_plan;
+#define AASM_CUT_IS_CUT      0x1   /* 0: the element spans the whole record, take the record's own tag and columns 10 / 11; every other field is 0 */
+#define AASM_CUT_IRREGULAR   0x2   /* a kept ':' run is not written as std::to_string writes it (":007"): mat_num / aln_len hold, the text must be rendered run by run */
+#define AASM_CUT_E_TAG       0x10  /* malformed tag met during the walk */
+#define AASM_CUT_E_INS_CLIP  0x20  /* "Alignment was clipped inside a cs insert" (paf_data.cpp:153-164) */
+#define AASM_CUT_E_EDIT      0x40  /* "Edited cs tag does not match ..." (:209-218) */
+#define AASM_CUT_E_RECORD    0x80  /* ctg_index outside the element's contig */
+/* A plan with an error flag holds that flag (and AASM_CUT_IS_CUT for the three walk errors) and zeros.  Precedence is the host
+ * codec's: tag, insert clip, edit check; the walk stops once its cursor has left the edited interval, so a malformed operation
+ * behind that point is not reported (the solve that produced the elements has already rejected such a tag, AASM_E_PARSE).      */
+typedef struct aasm_dev_cuts { aasm_cut_plan *main, *alt, *all; } aasm_dev_cuts;   /* DEVICE, caller-owned: [n_main], [n_alt], [n_all_elems] */
+
+/* The plans of every element of an exported result, on the device: a pure function over device arrays (no aasm_result, no
+ * workspace).  dev_in: the view aasm_upload_batch returned, with cs_text / rec_cs_off (a batch uploaded with rng_* arrays has no
+ * tags on the device); sz, dev_out: what aasm_result_export filled.  An element's record is ctg_rec_off[c] + ctg_index, c from
+ * main_off / alt_off, for .all from all_elem_off -> path -> all_path_off.  Asynchronous on `stream` (a hipStream_t of `device`;
+ * NULL = the null stream): no host wait, no read-back, no allocation; behind an export on the same stream nothing is needed in
+ * between.  AASM_E_INVAL (nothing enqueued) when dev_in has no cs text, when sz does not fit dev_in, or when an array that is
+ * not empty is NULL, host memory, memory of another device or not 8-byte aligned.  Errors of one element go into its flags.   */
+int  aasm_cut_plans_device(const aasm_batch_in *dev_in, const aasm_out_sizes *sz, const aasm_dev_out *dev_out,
+                           const aasm_dev_cuts *dst, int device, void *stream);
+
 /* Upload a host batch once and solve it repeatedly (benchmark path: inputs resident in
  * HBM before the timed region).  dev_view receives device pointers for aasm_solve_device. */
 typedef struct aasm_upload aasm_upload;
@@ -384,6 +416,13 @@ typedef struct aasm_writer aasm_writer;
 int  aasm_writer_open(const char *main_path, const char *alt_path, const char *all_path, aasm_writer **w);
 int  aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, int64_t contig0);
 int  aasm_writer_close(aasm_writer *w, int commit);
+/* aasm_writer_append with the rows' mat_num, aln_len and tag pieces taken from cut plans (aasm_cut_plans_device, fetched to the
+ * host) instead of a walk over every re-cut record's tag; the files are byte for byte those of aasm_writer_append.  A plan with
+ * AASM_CUT_IRREGULAR is rendered by the walk as before; one with an error flag fails the append with the host codec's code and
+ * message for that error; counts that are not out's, a plan that disagrees with its element about being cut, or a stretch outside
+ * the record's tag give AASM_E_INVAL.                                                                                          */
+typedef struct aasm_cuts { int64_t n_main, n_alt, n_all; aasm_cut_plan *main, *alt, *all; } aasm_cuts;   /* HOST arrays, parallel to aasm_batch_out's element lists */
+int  aasm_writer_append_cuts(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, const aasm_cuts *cuts, int64_t contig0);
 /* get_overlap_range (paf_data.cpp:90): returns #ranges or <0; arrays may be NULL      */
 int64_t aasm_cs_match_ranges(const char *cs, int64_t cs_len, int aln_fwd,
                              int64_t qry_str, int64_t qry_end, int64_t ref_str, int64_t ref_end,
