@@ -66,6 +66,11 @@ def _load():
     lib.aasm_paf_n_contigs.restype = C.c_int64
     lib.aasm_cs_match_ranges.restype = C.c_int64
     lib.aasm_cs_edit.restype = C.c_int64
+    # the device reader: (text, len, flags, device, aasm_paf **, aasm_upload **, aasm_batch_in *) / (path, flags, device, ...)
+    lib.aasm_paf_parse_device.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aasm_paf_parse_device.restype = C.c_int
+    lib.aasm_paf_read_device.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aasm_paf_read_device.restype = C.c_int
     return lib
 
 
@@ -78,6 +83,7 @@ EXPORTED = [
     "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
+    "aasm_paf_parse_device", "aasm_paf_read_device",
 ]
 
 
@@ -143,7 +149,7 @@ def sssp_dial(g_voff, rowptr, col, cost, src, lim=2, device=0):
 
 
 def debug_counter(name):
-    """Process-wide diagnostic counter: "range_splits", "device_mallocs", "stream_syncs"."""
+    """Process-wide diagnostic counter: "range_splits", "device_mallocs", "stream_syncs", "read_slow_rows", "read_host_fallbacks"."""
     return int(LIB.aasm_debug_counter(name.encode()))
 
 
@@ -186,6 +192,24 @@ class Paf:
         else:
             _check(LIB.aasm_synth_paf_range(C.byref(cfg), C.c_int64(int(first)), C.c_int64(int(n_contigs - first if count is None else count)), C.byref(h)))
         return Paf(h)
+
+    @staticmethod
+    def parse_device(text: bytes, device=0, _flags=0):
+        """The device reader (aasm_paf_parse_device): PAF text in host memory -> (Paf, DeviceBatch).  The rows are framed and parsed
+        on the GPU; the batch is resident in its cs form, as DeviceBatch(Paf.parse(text, device_ranges=True)) would leave it, and
+        the Paf equals that parse.  _flags: AASM_READ_H_WEAK_HASH (tests)."""
+        h, up, view = C.c_void_p(), C.c_void_p(), BatchIn()
+        _check(LIB.aasm_paf_parse_device(text, len(text), int(_flags), int(device), C.byref(h), C.byref(up), C.byref(view)))
+        paf = Paf(h)
+        return paf, DeviceBatch._from_upload(up, view, device, paf)
+
+    @staticmethod
+    def read_device(path, device=0, _flags=0):
+        """parse_device on a file (aasm_paf_read_device: the file is mapped, not copied)."""
+        h, up, view = C.c_void_p(), C.c_void_p(), BatchIn()
+        _check(LIB.aasm_paf_read_device(os.fsencode(path), int(_flags), int(device), C.byref(h), C.byref(up), C.byref(view)))
+        paf = Paf(h)
+        return paf, DeviceBatch._from_upload(up, view, device, paf)
 
     def merge_alt(self, text: bytes, alt_baseline=0.5):
         """--alt: merge a second PAF (sub-contig re-alignments), alignasm.cpp:186-332."""
@@ -290,6 +314,14 @@ class DeviceBatch:
         _check(LIB.aasm_upload_batch(C.byref(view), int(device), C.byref(self._up), C.byref(self.dev_view)))
         self.n_contigs = int(view.n_contigs)
         self.n_records = int(view.n_records)
+
+    @classmethod
+    def _from_upload(cls, up, dev_view, device, keep=None):
+        """A batch some other entry left on the device (the device reader): the upload handle and its view."""
+        self = object.__new__(cls)
+        self._keep, self.device, self._up, self.dev_view = keep, device, up, dev_view
+        self.n_contigs, self.n_records = int(dev_view.n_contigs), int(dev_view.n_records)
+        return self
 
     def solve(self, max_paths=10000, non_skip_linkable=False, timing=False, keep_debug=False, stream=None, **hooks):
         """hooks: _abi.HOOKS, except the two aasm_solve_device never reads (the range limit, device wrap)."""

@@ -18,10 +18,15 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include "aasm_pipeline.h"
 #include "aasm_ksw.h"
 #include "aasm_cut.h"
+#include "aasm_read.h"
 #include "aasm_paf.hpp"
 
 namespace aasm {
@@ -69,6 +74,11 @@ AASM_KSW_KERNELS(K)
 #define K(id, sym, block, lanes, lds, ...) \
     __global__ void __launch_bounds__(block) sym(CutArgs a) { AASM_SMEM(lds); AASM_KCTX((int64_t)blockIdx.x, smem); __VA_ARGS__(k, a); }
 AASM_CUT_KERNELS(K)
+#undef K
+// the device reader (aasm_paf_parse_device; bodies in aasm_read.h)
+#define K(id, sym, block, lanes, ...) \
+    __global__ void __launch_bounds__(block) sym(ReadArgs a) { AASM_KCTX((int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
+AASM_READ_KERNELS(K)
 #undef K
 
 // ---- T1 truth tables on the device (test entry aasm_debug_predicates) ------------------
@@ -295,7 +305,7 @@ static void drain_exports(DevCtx &cx) {
 }
 static DevCtx g_ctx[16];
 static std::mutex g_init_mu;
-static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0};
+static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0}, g_n_read_slow_rows{0}, g_n_read_fallbacks{0};
 
 static std::string hip_err(const char *what, hipError_t e) {
     return std::string(what) + ": " + hipGetErrorString(e);
@@ -1016,6 +1026,8 @@ int64_t aasm_debug_counter(const char *name) {
     if (n == "range_splits") return g_n_range_splits.load();
     if (n == "device_mallocs") return g_n_device_mallocs.load();
     if (n == "stream_syncs") return g_n_stream_syncs.load();
+    if (n == "read_slow_rows") return g_n_read_slow_rows.load();
+    if (n == "read_host_fallbacks") return g_n_read_fallbacks.load();
     return -1;
 }
 
@@ -1106,6 +1118,149 @@ void aasm_upload_free(aasm_upload *up) {
     hipSetDevice(up->device);
     for (void *p : up->ptrs) hipFree(p);
     delete up;
+}
+
+// ---- the device reader (aasm_read.h): plain hipMalloc blocks (what it hands out goes into an aasm_upload), the context's stream
+// and its single-pass scan.  AASM_READ_TIMING: the stages' wall times (a wait on the stream at every stage's end) on stderr.
+namespace {
+struct ReadGpu {
+    DevCtx &cx;
+    GpuBackend scans;                                               // (attached: it allocates nothing and leaves the arena alone)
+    hipError_t e = hipSuccess;
+    bool oom = false;
+    std::vector<void *> blocks;
+    const bool timing = std::getenv("AASM_READ_TIMING") != nullptr;
+    const char *stage_name = nullptr;
+    std::chrono::steady_clock::time_point stage_t0;
+    explicit ReadGpu(DevCtx &c) : cx(c), scans(c, c.stream, GpuBackend::Attach{}) {}
+    ~ReadGpu() { for (void *p : blocks) hipFree(p); }
+    bool ok() const { return e == hipSuccess && !oom && !scans.failed(); }
+    int code() const { return oom ? AASM_E_NOMEM : AASM_E_HIP; }
+    std::string why() const { return oom ? "out of device memory (device reader)" : e != hipSuccess ? hip_err("device reader", e) : std::string(last_error_text()); }
+    void *alloc(size_t n) {
+        if (!ok()) return nullptr;
+        void *p = nullptr;
+        const hipError_t r = hipMalloc(&p, n ? n : 8);
+        if (r != hipSuccess) { (void)hipGetLastError(); if (r == hipErrorOutOfMemory) oom = true; else e = r; return nullptr; }
+        blocks.push_back(p);
+        return p;
+    }
+    void release(void *p) {
+        auto it = std::find(blocks.begin(), blocks.end(), p);
+        if (it == blocks.end()) return;
+        blocks.erase(it);
+        hipFree(p);
+    }
+    void keep(void *p) { auto it = std::find(blocks.begin(), blocks.end(), p); if (it != blocks.end()) blocks.erase(it); }
+    void h2d(void *d, const void *h, size_t n) {
+        if (!ok() || n == 0) return;
+        e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, cx.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(cx.stream);
+    }
+    void d2h(void *h, const void *d, size_t n) {
+        if (!ok() || n == 0) return;
+        e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, cx.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(cx.stream);
+        scans.scan_stalled();
+    }
+    void fill32(void *p, int32_t v, int64_t count) { if (ok() && count > 0) e = hipMemsetD32Async((hipDeviceptr_t)p, v, (size_t)count, cx.stream); }
+    void scan_i32(const int32_t *in, int64_t n, int64_t *out) { if (ok()) scans.scan_i32(in, n, out); }
+    void scan_u8(const uint8_t *in, int64_t n, int64_t *out) { if (ok()) scans.scan_u8(in, n, out); }
+    void launch_read(int kr, int64_t nblocks, int nthreads, const ReadArgs &a) {
+        if (!ok()) return;
+        const char *name = "";
+        if (timing) e = hipStreamSynchronize(cx.stream);
+        const auto t0 = std::chrono::steady_clock::now();
+        switch (kr) {
+#define K(id, sym, ...) case id: name = #sym; hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, cx.stream, a); break;
+            AASM_READ_KERNELS(K)
+#undef K
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (timing && e == hipSuccess) {
+            e = hipStreamSynchronize(cx.stream);
+            std::fprintf(stderr, "aasm read kernel: %-20s %9.3f ms (%lld blocks)\n", name, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, (long long)nblocks);
+        }
+    }
+    void stage(const char *name) {
+        if (!timing) return;
+        if (ok()) e = hipStreamSynchronize(cx.stream);
+        const auto now = std::chrono::steady_clock::now();
+        if (stage_name) std::fprintf(stderr, "aasm read stage: %-14s %9.3f ms\n", stage_name, std::chrono::duration<double>(now - stage_t0).count() * 1e3);
+        stage_name = name; stage_t0 = now;
+    }
+};
+}  // namespace
+
+int aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view) {
+    if (paf_out) *paf_out = nullptr;
+    if (up_out) *up_out = nullptr;
+    if (!text || len < 0 || (up_out == nullptr) != (dev_view == nullptr) || (!paf_out && !up_out)) { set_last_error("aasm_paf_parse_device: bad argument"); return AASM_E_INVAL; }
+    int rc = ctx_init(device);
+    if (rc != AASM_OK) return rc;
+    DevCtx &cx = g_ctx[device];
+    aasm_paf *paf = paf_out ? new aasm_paf() : nullptr;
+    ReadOut o;
+    std::string why;
+    {
+        std::lock_guard<std::mutex> lk(cx.mu);                      // (the scans' scratch words are the context's)
+        hipSetDevice(device);
+        ReadGpu be(cx);
+        rc = read_run(be, text, len, flags, paf, up_out != nullptr, o);
+        if (rc < 0) {
+            why = be.why();
+            // a scan that did not run to its end leaves its words behind (solve_on_device does the same)
+            (void)hipDeviceSynchronize();
+            if (cx.d_scratch) (void)hipMemset(cx.d_scratch, 0, cx.d_scratch_cap * 8);
+            cx.pinned[SCAN_STALL_SLOT] = 0;
+            (void)hipGetLastError();
+        }
+        if (rc == AASM_OK && up_out) {
+            aasm_upload *up = new aasm_upload();
+            up->device = device;
+            up->ptrs = {o.ctg_rec_off, o.qry_str, o.qry_end, o.ref_str, o.ref_end, o.qry_total, o.ref_chr, o.aln_fwd, o.map_qul, o.rec_rng_off, o.cs_text, o.rec_cs_off};
+            aasm_batch_in &v = up->view;
+            std::memset(&v, 0, sizeof v);
+            v.n_contigs = o.C; v.n_records = o.R; v.n_ranges = o.n_ranges;
+            v.ctg_rec_off = o.ctg_rec_off; v.qry_str = o.qry_str; v.qry_end = o.qry_end; v.ref_str = o.ref_str; v.ref_end = o.ref_end; v.qry_total = o.qry_total;
+            v.ref_chr = o.ref_chr; v.aln_fwd = o.aln_fwd; v.map_qul = o.map_qul; v.rec_rng_off = o.rec_rng_off; v.cs_text = o.cs_text; v.rec_cs_off = o.rec_cs_off;
+            *dev_view = v;
+            *up_out = up;
+        }
+    }
+    if (rc == AASM_OK) {
+        g_n_read_slow_rows.store(o.slow_rows);
+        if (paf_out) *paf_out = paf;
+        return AASM_OK;
+    }
+    delete paf;
+    if (rc < 0) { set_last_error("aasm_paf_parse_device: " + why); return rc; }
+    // a text the device does not take: not a hot path, and the host reader's code and message are the contract
+    g_n_read_fallbacks++;
+    return read_host_verdict(text, len);
+}
+
+int aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view) {
+    if (!path) return AASM_E_INVAL;
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) { set_last_error(std::string("cannot open ") + path); return AASM_E_IO; }
+    struct stat st;
+    if (::fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {             // pipes etc.: read into memory
+        std::string data;
+        char buf[1 << 16];
+        ssize_t n;
+        while ((n = ::read(fd, buf, sizeof buf)) > 0) data.append(buf, (size_t)n);
+        ::close(fd);
+        return aasm_paf_parse_device(data.data(), (int64_t)data.size(), flags, device, paf_out, up_out, dev_view);
+    }
+    if (st.st_size == 0) { ::close(fd); return aasm_paf_parse_device("", 0, flags, device, paf_out, up_out, dev_view); }
+    void *m = ::mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    ::close(fd);
+    if (m == MAP_FAILED) { set_last_error(std::string("cannot map ") + path); return AASM_E_IO; }
+    ::madvise(m, (size_t)st.st_size, MADV_WILLNEED);
+    const int rc = aasm_paf_parse_device((const char *)m, (int64_t)st.st_size, flags, device, paf_out, up_out, dev_view);
+    ::munmap(m, (size_t)st.st_size);
+    return rc;
 }
 
 // concatenate per-range results (contiguous contig ranges cut[d]..cut[d+1]) in contig order

@@ -38,6 +38,7 @@ namespace aasm {
 static thread_local std::string g_last_error;
 void set_last_error(const std::string &msg) { g_last_error = msg; }
 const char *last_error_cstr() { return g_last_error.c_str(); }
+const char *last_error_text() { return g_last_error.c_str(); }
 
 // ---- short-form cs:Z codec ----------------------------------------------------------------
 // One scanner for everything the reference does with a cs tag (tokenizer paf_data.cpp:29-72,
@@ -378,6 +379,15 @@ static Rec record_of(const Row &w, int32_t chr, int32_t row, uint8_t type) {
     r.mat_num = (int32_t)w.mat; r.aln_len = (int32_t)w.aln; r.row_index = row;
     r.aln_fwd = w.fwd ? 1 : 0; r.map_qul = (uint8_t)w.mq; r.cord_type = type;
     return r;
+}
+
+bool read_slow_row(const char *s, const char *e, ReadRowCols &o) {
+    Row w;
+    if (parse_row(s, e, w) != ROW_OK) return false;
+    const Rec r = record_of(w, 0, 0, 0);
+    o.qry_str = r.qry_str; o.qry_end = r.qry_end; o.ref_str = r.ref_str; o.ref_end = r.ref_end; o.qry_total = r.qry_total; o.ref_total = r.ref_total;
+    o.mat_num = r.mat_num; o.aln_len = r.aln_len; o.aln_fwd = r.aln_fwd; o.map_qul = r.map_qul;
+    return true;
 }
 
 // ---- parallel reader -------------------------------------------------------------------

@@ -56,9 +56,13 @@ struct aasm_paf {
 namespace aasm {
 // cs codec (own implementation of the behaviour of paf_data.cpp:19-220)
 void set_last_error(const std::string &msg);
+const char *last_error_text();
 // message of the tokenizer / get_overlap_range for one record (used when the device reports a bad cs tag)
 std::string cs_error_message(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end, int64_t ref_str, int64_t ref_end);
 int host_threads();                          // aasm_set_host_threads (0 = all hardware threads), resolved
+// the device reader's slow path (aasm_read.h): one line without its line end through the host's parse_row + record_of; false: no row
+struct ReadRowCols { int64_t qry_str, qry_end, ref_str, ref_end, qry_total, ref_total; int32_t mat_num, aln_len; uint8_t aln_fwd, map_qul; };
+bool read_slow_row(const char *s, const char *e, ReadRowCols &out);
 // aasm_shard.cpp: per-contig cost estimate and the contiguous cost-balanced partition built on it
 void contig_costs(const aasm_batch_in *in, double *cost);
 void partition_by_cost(const double *cost, int64_t C, int n_shards, int64_t *cuts);

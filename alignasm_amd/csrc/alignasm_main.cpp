@@ -24,7 +24,7 @@
 
 static void usage(std::ostream &os) {
     os << "Usage: alignasm [--help] [--version] [--thread THREAD] [--alt PAF_ALT_LOC] [--alt_baseline ALT_BASELINE] "
-          "[--non_skip_linkable] [--max-paths K] [--gpus N] [--device D] [--timing] [--host-ranges] PAF_LOC\n\n"
+          "[--non_skip_linkable] [--max-paths K] [--gpus N] [--device D] [--timing] [--host-ranges] [--device-reader] PAF_LOC\n\n"
           "Positional arguments:\n  PAF_LOC              Location of PAF file [required]\n\n"
           "Optional arguments:\n  -h, --help           shows help message and exits\n  -v, --version        prints version information and exits\n"
           "  -t, --thread THREAD  Number of host threads for reading / writing PAF [default: all]\n"
@@ -35,7 +35,8 @@ static void usage(std::ostream &os) {
           "  --gpus N             shard contigs over N GPUs of this node [default: 1]\n"
           "  --device D           first HIP device ordinal [default: 0]\n"
           "  --timing             print read / solve / write wall time to stderr\n"
-          "  --host-ranges        build the cs match ranges in the reader instead of on the GPU\n";
+          "  --host-ranges        build the cs match ranges in the reader instead of on the GPU\n"
+          "  --device-reader      frame and parse the PAF rows on the GPU (not with --host-ranges)\n";
 }
 
 int main(int argc, char **argv) {
@@ -45,7 +46,7 @@ int main(int argc, char **argv) {
     opts.max_paths = 10000;
     int gpus = 1;
     double alt_baseline = 0.5;
-    bool bad = false, use_alt = false, timing = false, host_ranges = false;
+    bool bad = false, use_alt = false, timing = false, host_ranges = false, device_reader = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *what) -> const char * {
@@ -57,6 +58,7 @@ int main(int argc, char **argv) {
         else if (a == "-t" || a == "--thread") aasm_set_host_threads(std::atoi(need("--thread")));
         else if (a == "--timing") timing = true;
         else if (a == "--host-ranges") host_ranges = true;
+        else if (a == "--device-reader") device_reader = true;
         else if (a == "-a" || a == "--alt") alt_loc = need("--alt");
         else if (a == "-b" || a == "--alt_baseline") alt_baseline = std::atof(need("--alt_baseline"));
         else if (a == "--non_skip_linkable") opts.non_skip_linkable = 1;
@@ -67,6 +69,7 @@ int main(int argc, char **argv) {
         else if (paf_loc.empty()) paf_loc = a;
         else { std::cerr << "Maximum number of positional arguments exceeded\n"; bad = true; }
     }
+    if (host_ranges && device_reader) { std::cerr << "--device-reader: not with --host-ranges\n"; bad = true; }
     if (bad || paf_loc.empty()) { usage(std::cerr); return 1; }                 // alignasm.cpp:59-65
     std::filesystem::path p{paf_loc};
     if (p.extension() != ".paf") {                                              // :67-72
@@ -101,8 +104,14 @@ int main(int argc, char **argv) {
     }
     aasm_paf *paf = nullptr;
     // the reader only indexes the rows; the cs tags are turned into match ranges on the GPU
-    int rc = aasm_paf_read_opts(std::filesystem::absolute(p).c_str(), host_ranges ? 0 : AASM_READ_DEVICE_RANGES, &paf);
+    // --device-reader: the rows are framed and parsed on the GPU, which leaves the batch resident (up, dev_view) beside the container
+    aasm_upload *up = nullptr;
+    aasm_batch_in dev_view;
+    int rc = device_reader ? aasm_paf_read_device(std::filesystem::absolute(p).c_str(), 0, opts.device, &paf, &up, &dev_view)
+                           : aasm_paf_read_opts(std::filesystem::absolute(p).c_str(), host_ranges ? 0 : AASM_READ_DEVICE_RANGES, &paf);
+    if (rc != AASM_OK && device_reader && rc != AASM_E_PARSE && rc != AASM_E_IO) { std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; return 2; }
     if (rc != AASM_OK) { std::cerr << aasm_last_error() << "\n"; return 1; }    // e.g. "Missing cs:Z tag ..." (:165-168)
+    if (up && (use_alt || gpus > 1)) { aasm_upload_free(up); up = nullptr; }    // the merge changes the records, shards are uploaded per GPU: on from the container
     if (use_alt) {
         rc = aasm_paf_merge_alt(paf, std::filesystem::absolute(alt_loc).c_str(), alt_baseline);
         if (rc != AASM_OK) { std::cerr << aasm_last_error() << "\n"; aasm_paf_free(paf); return 1; }
@@ -119,7 +128,33 @@ int main(int argc, char **argv) {
     double upload_s = 0, device_s = 0, fetch_s = 0, solve_busy_s = 0, write_busy_s = 0;
     int64_t n_internal = 0;
     clk::time_point t2 = t1;
-    if (gpus <= 1 && view.n_contigs >= 64 && view.n_records >= (1 << 16)) {
+    bool done = false;
+    if (up) {
+        // ---- the resident batch is solved in place and fetched.  Out of device memory, or a tag the device rejects (a bad file is no
+        //      hot path): the batch is freed and the range path below runs from the container, with its messages and exit codes.
+        aasm_result *res = nullptr;
+        aasm_batch_out out;
+        std::memset(&out, 0, sizeof out);
+        rc = aasm_solve_device(&dev_view, &opts, nullptr, &res);
+        const auto ts = clk::now();
+        if (rc == AASM_OK) rc = aasm_result_fetch(res, &out);
+        aasm_result_free(res);
+        aasm_upload_free(up);
+        if (rc == AASM_OK) {
+            t2 = clk::now();
+            device_s = secs(t1, ts); fetch_s = secs(ts, t2); solve_busy_s = secs(t1, t2);
+            if (out.stats.n_internal_errors) std::cerr << "alignasm: " << out.stats.n_internal_errors << " contig(s) hit an internal error state\n";
+            std::cout << "Write output PAF file" << std::endl;                       // :487
+            rc = aasm_paf_write_outputs(paf, &out, f_main.c_str(), f_alt.c_str(), f_all.c_str());
+            if (rc != AASM_OK) std::cerr << "alignasm: writing outputs failed: " << aasm_last_error() << "\n";
+            write_busy_s = secs(t2, clk::now());
+            done = true;
+        } else if (rc != AASM_E_NOMEM && rc != AASM_E_PARSE) {
+            std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; aasm_paf_free(paf); return 2;
+        }
+    }
+    if (done) {
+    } else if (gpus <= 1 && view.n_contigs >= 64 && view.n_records >= (1 << 16)) {
         // ---- one GPU: the file goes through in contig ranges of about equal record counts; while the GPU solves range k
         //      (upload -> K0 .. K9 -> fetch) the host threads format and write the rows of range k - 1.  The three outputs
         //      are appended to in contig order (aasm_writer_*), so the bytes are those of the one-piece path.

@@ -367,7 +367,7 @@ int  aasm_reserve_workspace(int device, int64_t bytes);
 int64_t aasm_debug_fetch(aasm_result *res, const char *name, void *dst, int64_t dst_bytes);
 /* Process-wide diagnostic counters (tests / tuning): "range_splits" (contig ranges halved after an
  * out-of-memory), "device_mallocs" (hipMalloc calls of the arenas), "stream_syncs" (host waits on a
- * pipeline stream).  Unknown name: -1.                                                         */
+ * pipeline stream), "read_slow_rows" / "read_host_fallbacks" (aasm_paf_parse_device).  Unknown name: -1.                                                         */
 int64_t aasm_debug_counter(const char *name);
 /* Test entry for row T1: the device's PafDistance predicates (paf_data.hpp:142-168) on n pairs of
  * {qry, ref, anom, qul_nonzero, qul_total} tuples.  out[i] bit 0: a < b in CALC_SUM mode, bit 1: a < b in
@@ -400,6 +400,24 @@ int  aasm_paf_parse_mem(const char *text, int64_t len, aasm_paf **paf);
 #define AASM_READ_DEVICE_RANGES 1
 int  aasm_paf_read_opts(const char *path, int flags, aasm_paf **paf);
 int  aasm_paf_parse_mem_opts(const char *text, int64_t len, int flags, aasm_paf **paf);
+/* The device reader: host text in, a resident batch in the cs form out (cs_text / rec_cs_off, rng_* NULL: ready for
+ * aasm_solve_device and aasm_cut_plans_device) and the container the writers need.  The device frames the rows and parses the
+ * twelve columns itself; the host copies the tags into the container from its own text, at offsets the device computed.
+ *   text      HOST memory, the bytes of a PAF file (aasm_paf_read_device: the file is mapped).
+ *   *paf      equal, field for field, to aasm_paf_parse_mem_opts(text, len, AASM_READ_DEVICE_RANGES, ...).  paf may be NULL: no
+ *             container is built.
+ *   *up       owns every device array; release with aasm_upload_free.  *dev_view: what aasm_upload_batch(aasm_paf_batch(paf)) gives.
+ *             up and dev_view may both be NULL: only the container is built.
+ * Errors: AASM_E_INVAL (NULL text, negative len, one of up / dev_view alone, nothing asked for), AASM_E_NODEVICE, AASM_E_NOMEM /
+ * AASM_E_HIP (a failed HIP call is not retried).  A text the device finds fault with (fewer than 12 columns, no cs:Z: tag, a number
+ * strtoll does not take whole, a row too long, no rows) is read again by the host reader, whose code and message are returned:
+ * the first bad row in file order, a malformed tag in an earlier row included.  A malformed tag in an otherwise well-formed
+ * file is reported by the solve, as with AASM_READ_DEVICE_RANGES.  Numbers off the fast path ([-] and 1 - 18 digits) are
+ * resolved by the host, row by row.  aasm_debug_counter: "read_slow_rows" (such rows in the last device read),
+ * "read_host_fallbacks" (device reads that reran the host reader).                                                        */
+#define AASM_READ_H_WEAK_HASH 0x100   /* test hook, 0 in production: the reference-name hash is (length & 3) */
+int  aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view);
+int  aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view);
 /* --alt merge of a second PAF of sub-contig re-alignments (alignasm.cpp:186-332) */
 int  aasm_paf_merge_alt(aasm_paf *paf, const char *alt_path, double alt_baseline);
 int  aasm_paf_merge_alt_mem(aasm_paf *paf, const char *text, int64_t len, double alt_baseline);

@@ -1,0 +1,153 @@
+"""Texts for the device reader's tests (tests/test_read_cpu.py, tests/test_gpu_read.py): what aasm_paf_parse_device must read as
+the host reader does.  A case is {name, text, oracle, slow, weak}:
+  oracle  the independent reader (oracle/paf_io_oracle.py) models this text, so its arrays are compared too.  It splits lines on
+          '\\n' alone, takes numbers with Python's int() and keeps them unbounded, and checks every tag against the coordinates;
+          where a case needs what it does not model, the case's comment says so and the host reader alone is the yardstick.
+  slow    rows whose numbers are off the device's fast path ([-] and 1 - 18 digits): exactly these the host may patch.
+  weak    run again with AASM_READ_H_WEAK_HASH (reference names collide all the time).
+Nothing here depends on the product: the texts are built from bytes."""
+import re
+
+TILE = 16384                      # AASM_READ_TILE (asserted by the CPU tier)
+GOOD = b":10*ac:5+gg:3-t:2"
+
+# the tag list of tests/test_cs_device.py
+TAGS = [
+    b":10*ac:5+gg:3-t:2", b":1", b"*ag", b"+" + b"acgt" * 40 + b":7", b":5-" + b"t" * 150 + b":9*ct:123456", b":" + b"9" * 7 + b"+a",
+    (b":12*ac" * 30) + b":4", b":3" + b"+a:1" * 70, b":007*ac:00000000000000000000005+GG:0012",
+]
+
+
+def consumed(cs):
+    q = r = 0
+    for op in re.findall(rb":[0-9]+|\*[A-Za-z][A-Za-z]|[+-][A-Za-z]+", cs):
+        if op[:1] == b":": q += int(op[1:]); r += int(op[1:])
+        elif op[:1] == b"*": q += 1; r += 1
+        elif op[:1] == b"+": q += len(op) - 1
+        else: r += len(op) - 1
+    return q, r
+
+
+def row(name=b"ctg1", cs=GOOD, fwd=True, qs=100, ref=b"chr1", rs=1000, tags=None, eol=b"\n", **over):
+    """One PAF row whose coordinates fit the tag.  tags: the whole tag list (default tp + the cs tag); over: raw bytes for the
+    columns qtot, qs, qe, strand, rtot, rs, re, mat, aln, mq."""
+    ql, rl = consumed(cs)
+    f = {"qtot": b"100000", "qs": b"%d" % qs, "qe": b"%d" % (qs + ql), "strand": b"+" if fwd else b"-", "rtot": b"5000000",
+         "rs": b"%d" % rs, "re": b"%d" % (rs + rl), "mat": b"10", "aln": b"10", "mq": b"60"}
+    f.update(over)
+    if tags is None:
+        tags = [b"tp:A:P", b"cs:Z:" + cs]
+    return b"\t".join([name, f["qtot"], f["qs"], f["qe"], f["strand"], ref, f["rtot"], f["rs"], f["re"], f["mat"], f["aln"], f["mq"]] + list(tags)) + eol
+
+
+def fill(n, seed=0, eol=b"\n", name=None):
+    """Valid rows of exactly n bytes together (n >= 200), contigs of three rows, four reference names, both strands."""
+    out, left, i = [], n, seed
+    while left > 0:
+        nm = name or b"ctg%d" % (i // 3)
+        r = row(nm, TAGS[i % 3], fwd=bool(i % 2), qs=100 + 50 * (i % 90), ref=b"chr%d" % (i % 4), eol=eol)
+        if left < len(r) + 120:                                      # the last row: padded by a tag behind the cs tag to fit
+            base = row(nm, GOOD, qs=7, ref=b"chrL", tags=[b"tp:A:P", b"cs:Z:" + GOOD, b"zz:Z:"], eol=eol)
+            assert left >= len(base), (n, left)
+            r = row(nm, GOOD, qs=7, ref=b"chrL", tags=[b"tp:A:P", b"cs:Z:" + GOOD, b"zz:Z:" + b"x" * (left - len(base))], eol=eol)
+        out.append(r)
+        left -= len(r)
+        i += 1
+    text = b"".join(out)
+    assert len(text) == n
+    return text
+
+
+def case(name, text, oracle=True, slow=0, weak=False):
+    return {"name": name, "text": text, "oracle": oracle, "slow": slow, "weak": weak}
+
+
+def valid_cases(synth_text):
+    """synth_text: a file of several hundred KB whose rows cross every kind of edge (Paf.synth(200, 50, ...).to_text())."""
+    c = []
+    one = row()
+    # ---- line framing
+    c.append(case("one_row", one))
+    c.append(case("one_row_no_newline", one[:-1]))
+    c.append(case("blank_lines", b"\n\n" + one + b"\n" + row(b"ctg2") + b"\n\n\n" + row(b"ctg2", qs=400) + b"\n"))
+    # CR: the oracle splits on '\n' alone and would keep the '\r' in the last tag
+    c.append(case("crlf_lines", fill(3000, eol=b"\r\n"), oracle=False))
+    c.append(case("lone_cr_line", one + b"\r\n" + row(b"ctg2") + b"\r\n\r\n" + row(b"ctg3"), oracle=False))
+    c.append(case("lone_cr_last_byte", one + row(b"ctg2") + b"\r", oracle=False))
+    c.append(case("cr_then_eof_on_row", one + row(b"ctg2")[:-1] + b"\r", oracle=False))
+    c.append(case("newline_last_byte_of_tile", fill(TILE) + fill(700, 5)))          # = a row start exactly on a tile edge
+    c.append(case("newline_first_byte_of_tile", fill(TILE + 1) + fill(700, 5)))
+    c.append(case("row_start_on_second_edge", fill(TILE - 300) + fill(TILE + 300, 7) + fill(900, 3)))
+    c.append(case("crlf_split_by_tile_edge", fill(TILE + 1, eol=b"\r\n") + fill(600, 2, eol=b"\r\n"), oracle=False))   # '\r' the tile's last byte
+    c.append(case("crlf_ends_tile", fill(TILE, eol=b"\r\n") + fill(600, 2), oracle=False))
+    for extra in (1, 7, 8, 9, 15, 16, 17):
+        c.append(case("len_tile_plus_%d" % extra, fill(TILE + extra)))
+        c.append(case("len_tile_plus_%d_open" % extra, fill(TILE + extra + 1)[:-1]))                                  # no final newline
+    c.append(case("synth_file", synth_text))
+    # ---- tags
+    c.append(case("cs_first", row(tags=[b"cs:Z:" + GOOD, b"tp:A:P"]) + row(b"ctg2", tags=[b"cs:Z:" + GOOD])))
+    c.append(case("cs_behind_ten_tags", row(tags=[b"t%d:i:%d" % (i, i) for i in range(10)] + [b"cs:Z:" + GOOD]) + row(b"ctg2")))
+    c.append(case("two_cs_tags", row(tags=[b"cs:Z:" + GOOD, b"cs:Z::99"]) + row(b"ctg2", tags=[b"tp:A:P", b"cs:Z:" + GOOD, b"cs:Z::1:1:1"])))
+    c.append(case("near_tags", row(tags=[b"xcs:Z::5", b"cs:Z", b"cs:z::7", b"cs:Z:" + GOOD]) + row(b"ctg2", tags=[b"cs:Z", b"acs:Z::3:3", b"cs:Z:" + GOOD])))
+    c.append(case("bare_cs", row(cs=b"") + row(b"ctg2", cs=b"", fwd=False) + row(b"ctg2", qs=300)))
+    rows = []
+    for k, cs in enumerate(TAGS):
+        for fwd in (True, False):
+            rows.append(row(b"ctg%d" % (k // 2), cs, fwd, qs=1000 * (len(rows) + 1)))
+    c.append(case("cs_device_tag_list", b"".join(rows)))
+    # ---- numbers
+    c.append(case("negative_and_18_digits", row(rtot=b"-5") + row(qtot=b"1" + b"0" * 17, qs=300) + row(b"ctg2", rtot=b"-" + b"9" * 18)))
+    # strtoll's leniency: the oracle's int() is another (it also takes "5 "), and it does not saturate
+    c.append(case("slow_numbers", row(rtot=b"+5") + row(qtot=b" 5", qs=300) + row(b"ctg2", rtot=b"1" + b"0" * 18) + row(b"ctg2", qtot=b"9" * 25, qs=300) + row(b"ctg3"),
+                  oracle=False, slow=4))
+    c.append(case("slow_row_last_no_newline", row() + row(b"ctg2", rtot=b"+7")[:-1], oracle=False, slow=1))
+    # the oracle keeps Python ints: no truncation to 32 / 8 bits
+    c.append(case("truncating_columns", row(mat=b"%d" % ((1 << 32) + 7)) + row(aln=b"%d" % (1 << 31), qs=300) + row(b"ctg2", mq=b"300") + row(b"ctg2", mq=b"-1", qs=300), oracle=False))
+    c.append(case("minus_strand", row(fwd=False) + row(fwd=False, qs=300) + row(b"ctg2")))
+    # an empty strand column is '-' to the product (record_of); the oracle indexes its first character
+    c.append(case("empty_strand", row(strand=b"") + row(b"ctg2", strand=b"+x") + row(b"ctg2", strand=b"*", qs=300), oracle=False))
+    # ---- contigs
+    c.append(case("ctg1_then_ctg10", row(b"ctg1") + row(b"ctg10") + row(b"ctg10", qs=300) + row(b"ctg1", qs=300) + row(b"ctg", qs=500)))
+    c.append(case("name_comes_back", row(b"a") + row(b"b") + row(b"a", qs=300) + row(b"a", qs=500) + row(b"b", qs=300)))
+    c.append(case("one_row_contigs", b"".join(row(b"c%d" % i, qs=100 + i) for i in range(150))))
+    c.append(case("contig_spans_three_tiles", row(b"first") + fill(2 * TILE + 700, 3, name=b"wide") + row(b"last")))
+    # ---- reference names, each again under the weak hash
+    c.append(case("refs_reverse_alphabetical", b"".join(row(b"ctg%d" % (i // 4), qs=100 + i, ref=b"chr" + bytes([ord("z") - i % 7])) for i in range(40)), weak=True))
+    c.append(case("refs_more_than_64", b"".join(row(b"ctg%d" % (i // 5), qs=100 + i, ref=b"ref_%d" % ((i * 37) % 90)) for i in range(400)), weak=True))
+    c.append(case("refs_shared_prefix", b"".join(row(b"ctg%d" % (i // 3), qs=100 + i, ref=b"chromosome_%c%c" % (65 + i % 5, 65 + (i // 5) % 3)) for i in range(60)), weak=True))
+    c.append(case("refs_runs_and_returns", b"".join(row(b"ctg%d" % (i // 6), qs=100 + i, ref=(b"chrB", b"chrB", b"chrA", b"chrB", b"", b"chrA")[i % 6]) for i in range(36)), weak=True))
+    names = [x["name"] for x in c]
+    assert len(set(names)) == len(names)
+    return c
+
+
+def error_cases():
+    """(name, text): the reader's code and message are the host reader's - the first bad row in file order."""
+    good = fill(1500)
+    few = b"\t".join([b"ctgX", b"1000", b"1", b"2", b"+", b"chr1", b"9", b"1", b"2", b"3", b"4"]) + b"\n"      # 11 columns
+    no_tag = row(b"ctgN", tags=[b"tp:A:P", b"xcs:Z::5", b"cs:Z"])
+    twelve = row(b"ctgT", tags=[])
+    bad_tag = row(b"ctgB", tags=[b"tp:A:P", b"cs:Z::10?:5"])
+    e = [
+        ("too_few_columns", good + few + good),
+        ("no_cs_tag", good + no_tag + good),
+        ("twelve_columns_no_tags", good + twelve),
+        ("number_5x", good + row(b"ctgX", rtot=b"5x") + good),
+        ("number_trailing_blank", good + row(b"ctgX", qtot=b"5 ") + good),
+        ("number_empty_field", good + row(b"ctgX", mq=b"") + good),
+        ("number_lone_minus", good + row(b"ctgX", mat=b"-") + good),
+        ("later_kind_first", fill(TILE // 2) + no_tag + fill(2 * TILE, 3) + few + good),                            # two kinds, different tiles
+        ("number_before_columns", fill(TILE // 2) + row(b"ctgX", aln=b"1e3") + fill(2 * TILE, 3) + few + good),
+        ("columns_before_number", fill(TILE // 2) + few + fill(2 * TILE, 3) + row(b"ctgX", aln=b"1e3") + good),
+        ("fault_in_last_row", good + few),
+        ("fault_in_last_row_no_newline", good + no_tag[:-1]),
+        ("bad_tag_before_column_fault", good + bad_tag + good + few + good),                                          # the earlier row's tag is the error
+        ("empty_text", b""),
+        ("only_blank_lines", b"\n\r\n\n"),
+    ]
+    return e
+
+
+def bad_tag_only():
+    """A file whose only defect is a malformed tag: reads fine, fails in the solve."""
+    return fill(1500) + row(b"ctgB", tags=[b"tp:A:P", b"cs:Z::10?:5"]) + fill(900, 4)

@@ -10,6 +10,7 @@ ap.add_argument("--contigs", type=int, default=500); ap.add_argument("--recs", t
 ap.add_argument("--k", type=int, default=4); ap.add_argument("--seed", type=int, default=21)
 ap.add_argument("--dir", default="/tmp/aasm_e2e"); ap.add_argument("--threads", default="0", help="host threads (-t); a comma list runs the command once per value")
 ap.add_argument("--quiet", type=int, default=0, help="1: only the timing line of each run")
+ap.add_argument("--device-reader", action="store_true", help="pass --device-reader: the rows are framed and parsed on the GPU (its stages: AASM_READ_TIMING)")
 a = ap.parse_args()
 os.makedirs(a.dir, exist_ok=True)
 path = os.path.join(a.dir, "synth.paf")
@@ -23,11 +24,13 @@ for thr in [int(x) for x in str(a.threads).split(",")]:
     cmd = [os.path.join(ROOT, "alignasm_amd", "alignasm"), path, "--max-paths", str(a.k), "--timing"]
     if thr:
         cmd += ["-t", str(thr)]
+    if a.device_reader:
+        cmd += ["--device-reader"]
     for rep in range(2):                   # second run: file in the page cache, GPU context warm-up is per process
         for o in outs:                     # to NEW files (replacing a 3 GB file frees its page cache inside rename())
             if os.path.exists(o): os.remove(o)
         t = time.time()
-        r = subprocess.run(cmd, capture_output=True, text=True, env=(dict(os.environ) if a.quiet else dict(os.environ, AASM_IO_TIMING="1")))
+        r = subprocess.run(cmd, capture_output=True, text=True, env=(dict(os.environ) if a.quiet else dict(os.environ, AASM_IO_TIMING="1", **({"AASM_READ_TIMING": "1"} if a.device_reader else {}))))
         lines = r.stderr.strip().splitlines()
         if a.quiet: lines = [l for l in lines if l.startswith("alignasm timing")]
         print(f"threads {thr} run {rep}: rc={r.returncode} wall {time.time() - t:.2f}s | {' / '.join(lines)}", flush=True)
