@@ -14,8 +14,8 @@ AASM_OK = 0
 AASM_E_INVAL, AASM_E_NODEVICE, AASM_E_HIP, AASM_E_NOMEM = -1, -2, -3, -4
 AASM_E_OVERFLOW, AASM_E_INTERNAL, AASM_E_PARSE, AASM_E_IO = -5, -6, -7, -8
 
-# reader flags (aasm_paf_read_opts, aasm_paf_parse_device); AASM_READ_H_WEAK_HASH: test hook of the device reader, 0 in production
-AASM_READ_DEVICE_RANGES, AASM_READ_H_WEAK_HASH = 1, 0x100
+# reader flags (aasm_paf_read_opts, aasm_paf_parse_device); AASM_READ_H_*: test hooks of the device reader, 0 in production
+AASM_READ_DEVICE_RANGES, AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS = 1, 0x100, 0x200
 
 _IN_ARRAYS = [
     ("ctg_rec_off", np.int64), ("qry_str", np.int64), ("qry_end", np.int64), ("ref_str", np.int64),

@@ -197,7 +197,7 @@ class Paf:
     def parse_device(text: bytes, device=0, _flags=0):
         """The device reader (aasm_paf_parse_device): PAF text in host memory -> (Paf, DeviceBatch).  The rows are framed and parsed
         on the GPU; the batch is resident in its cs form, as DeviceBatch(Paf.parse(text, device_ranges=True)) would leave it, and
-        the Paf equals that parse.  _flags: AASM_READ_H_WEAK_HASH (tests)."""
+        the Paf equals that parse.  _flags: AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS (tests)."""
         h, up, view = C.c_void_p(), C.c_void_p(), BatchIn()
         _check(LIB.aasm_paf_parse_device(text, len(text), int(_flags), int(device), C.byref(h), C.byref(up), C.byref(view)))
         paf = Paf(h)

@@ -320,7 +320,8 @@ struct ReadOut {
 // text: HOST memory.  paf: the container to fill, or nullptr; want_dev: hand the batch's arrays out in `out` (else they are freed).
 // Returns AASM_OK, AASM_READ_FALLBACK, or the backend's failure as AASM_E_NOMEM / AASM_E_HIP through be.code().
 template <class B> int read_run(B &be, const char *text, int64_t len, int flags, aasm_paf *paf, bool want_dev, ReadOut &out) {
-    auto blocks_for = [](int64_t items, int per_block) { return std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, AASM_READ_MAX_BLOCKS)); };
+    const int64_t max_blocks = (flags & AASM_READ_H_FEW_BLOCKS) ? 3 : AASM_READ_MAX_BLOCKS;   // (the hook: fewer blocks than items)
+    auto blocks_for = [&](int64_t items, int per_block) { return std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, max_blocks)); };
     auto i64s = [&](int64_t n) { return (int64_t *)be.alloc((size_t)n * 8); };
     auto i32s = [&](int64_t n) { return (int32_t *)be.alloc((size_t)n * 4); };
     auto u8s = [&](int64_t n) { return (uint8_t *)be.alloc((size_t)n); };

@@ -416,6 +416,7 @@ int  aasm_paf_parse_mem_opts(const char *text, int64_t len, int flags, aasm_paf 
  * resolved by the host, row by row.  aasm_debug_counter: "read_slow_rows" (such rows in the last device read),
  * "read_host_fallbacks" (device reads that reran the host reader).                                                        */
 #define AASM_READ_H_WEAK_HASH 0x100   /* test hook, 0 in production: the reference-name hash is (length & 3) */
+#define AASM_READ_H_FEW_BLOCKS 0x200  /* test hook, 0 in production: every reader grid is capped at 3 blocks (grid-stride loops) */
 int  aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view);
 int  aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view);
 /* --alt merge of a second PAF of sub-contig re-alignments (alignasm.cpp:186-332) */

@@ -5,6 +5,7 @@ the host reader does.  A case is {name, text, oracle, slow, weak}:
           where a case needs what it does not model, the case's comment says so and the host reader alone is the yardstick.
   slow    rows whose numbers are off the device's fast path ([-] and 1 - 18 digits): exactly these the host may patch.
   weak    run again with AASM_READ_H_WEAK_HASH (reference names collide all the time).
+few_blocks(case): run again on the device with AASM_READ_H_FEW_BLOCKS (the emulation caps its grids for every case).
 Nothing here depends on the product: the texts are built from bytes."""
 import re
 
@@ -62,6 +63,69 @@ def case(name, text, oracle=True, slow=0, weak=False):
     return {"name": name, "text": text, "oracle": oracle, "slow": slow, "weak": weak}
 
 
+def long_tag(L):
+    return b":5+" + b"a" * L + b":7"
+
+
+# tags without a row start inside: a tile's worth less 200, a tile, a tile and a byte, three tiles and five, 1 MiB (64 tiles)
+LONG = [("tile_minus_200", TILE - 200), ("tile", TILE), ("tile_plus_1", TILE + 1), ("three_tiles_plus_5", 3 * TILE + 5), ("1mib", 1 << 20)]
+BIG = {"qtot": b"9000000"}                # (a query long enough for the long tags)
+
+
+def slow_text(n_rows, every, bad=None):
+    """n_rows rows, all different, row i off the fast path (three forms in turn) where i % every == 0; bad: the number of the slow
+    row (from 1) whose rtot no reader takes."""
+    rows, k = [], 0
+    for i in range(n_rows):
+        over = {}
+        if i % every == 0:
+            k += 1
+            over = ({"rtot": b"+%d" % (5000000 + i)}, {"qtot": b" %d" % (100000 + i)}, {"rtot": b"1" + b"%018d" % i})[k % 3]
+            if k == bad:
+                over = {"rtot": b"5x"}
+        rows.append(row(b"ctg%d" % (i // 7), TAGS[i % 3], fwd=bool(i % 2), qs=100 + 13 * i, ref=b"chr%d" % (i % 5), rs=1000 + 7 * i, **over))
+    return b"".join(rows), k
+
+
+def long_cases():
+    """Rows of kilobytes to a megabyte: tiles without a row start, tags and names across tile edges."""
+    c = []
+    crlf = b"\r\n"
+    for name, L in LONG:
+        cs = long_tag(L)
+        c.append(case("long_%s_only" % name, row(b"ctgL", cs, **BIG)))
+        c.append(case("long_%s_between" % name, fill(1000) + row(b"ctgL", cs, fwd=False, **BIG) + fill(1000, 5)))
+        c.append(case("long_%s_last_open" % name, fill(1000) + row(b"ctgL", cs, **BIG)[:-1]))
+        c.append(case("long_%s_crlf" % name, fill(1000, eol=crlf) + row(b"ctgL", cs, eol=crlf, **BIG) + fill(700, 2, eol=crlf), oracle=False))   # (CR: see crlf_lines)
+    cs = long_tag(3 * TILE + 5)
+    c.append(case("long_second_cs_ignored", fill(700) + row(b"ctgL", tags=[b"tp:A:P", b"cs:Z:" + GOOD, b"cs:Z:" + long_tag(1 << 20)]) + fill(700, 4)))
+    c.append(case("long_behind_long_other_tag", fill(700) + row(b"ctgL", cs, tags=[b"zz:Z:" + b"x" * (3 * TILE + 5), b"cs:Z:" + cs], **BIG) + row(b"ctgL", qs=300) + fill(700, 4)))
+    c.append(case("long_70000_colons", row(b"ctgL", b":1*ac" * 70000, **BIG) + row(b"ctgL", qs=300000, **BIG) + row(b"ctgM", b":1*ac" * 70000, fwd=False, **BIG) + row(b"ctgM")))
+    # ---- names
+    q40, r40 = b"Q" * 39 + b"q", b"R" * 39 + b"r"
+    a = row(q40) + row(q40, qs=300)                                  # the second row's query name lies on [TILE - 20, TILE + 20)
+    b = row(b"ctgR", ref=r40) + row(b"ctgR", qs=300, ref=r40)        # the second row's reference name on [2 * TILE - 20, 2 * TILE + 20)
+    head = fill(TILE - 20 - len(a) // 2) + a
+    head += fill(2 * TILE - 20 - len(head) - len(b) // 2 - b.index(r40))
+    c.append(case("names_straddle_tile_edges", head + b + row(b"ctgR", qs=500) + row(b"ctgR", qs=700, ref=r40) + fill(500, 3), weak=True))
+    n5, r5 = b"n" * 4999, b"r" * 4999
+    c.append(case("contig_names_5000_differ_in_last_byte", row(n5 + b"a") + row(n5 + b"a", qs=300) + row(n5 + b"b") + row(n5 + b"b", qs=300) + row(n5 + b"a", qs=500)))
+    c.append(case("ref_names_5000_differ_in_last_byte", b"".join(row(b"ctg%d" % (i // 4), qs=100 + i, ref=r5 + (b"a", b"b", b"b", b"a", b"c")[i % 5]) for i in range(20)), weak=True))
+    # an empty contig name: the oracle takes "" for "no contig yet" (alignasm.cpp:117) and merges such a contig with the next one
+    c.append(case("empty_query_name", row(b"") + row(b"", qs=300) + row(b"ctg2") + row(b"", qs=500) + row(b"ctg2", qs=300), oracle=False))
+    # ---- a row start in every tile, nothing else in it; then contigs of one row
+    per_tile = []
+    for i in range(20):
+        base = row(b"tile%d" % (i // 2), GOOD, qs=100 + 40 * i, tags=[b"tp:A:P", b"cs:Z:" + GOOD, b"zz:Z:"])
+        per_tile.append(row(b"tile%d" % (i // 2), GOOD, qs=100 + 40 * i, tags=[b"tp:A:P", b"cs:Z:" + GOOD, b"zz:Z:" + b"x" * (TILE - len(base))]))
+    c.append(case("long_one_row_per_tile", b"".join(per_tile) + b"".join(row(b"c%d" % i, qs=100 + i, ref=b"chr%d" % (i % 3)) for i in range(200))))
+    # ---- slow rows up to and beyond the bulk download of the row starts (read_run: n_slow > 64); see slow_numbers for the oracle
+    for n_rows, every in ((640, 10), (650, 10), (600, 2)):
+        text, k = slow_text(n_rows, every)
+        c.append(case("slow_rows_%d" % k, text, oracle=False, slow=k))
+    return c
+
+
 def valid_cases(synth_text):
     """synth_text: a file of several hundred KB whose rows cross every kind of edge (Paf.synth(200, 50, ...).to_text())."""
     c = []
@@ -116,9 +180,17 @@ def valid_cases(synth_text):
     c.append(case("refs_more_than_64", b"".join(row(b"ctg%d" % (i // 5), qs=100 + i, ref=b"ref_%d" % ((i * 37) % 90)) for i in range(400)), weak=True))
     c.append(case("refs_shared_prefix", b"".join(row(b"ctg%d" % (i // 3), qs=100 + i, ref=b"chromosome_%c%c" % (65 + i % 5, 65 + (i // 5) % 3)) for i in range(60)), weak=True))
     c.append(case("refs_runs_and_returns", b"".join(row(b"ctg%d" % (i // 6), qs=100 + i, ref=(b"chrB", b"chrB", b"chrA", b"chrB", b"", b"chrA")[i % 6]) for i in range(36)), weak=True))
+    c += long_cases()
     names = [x["name"] for x in c]
     assert len(set(names)) == len(names)
     return c
+
+
+def few_blocks(c):
+    """Is the case read again with every grid capped at 3 blocks (AASM_READ_H_FEW_BLOCKS)?  Where that makes blocks take a second
+    item: more than 3 tiles, more than 3 * 256 rows; and the cases named for it."""
+    return (len(c["text"]) > 3 * TILE or c["text"].count(b"\n") > 768 or c["name"].startswith("long_")
+            or c["name"] in ("synth_file", "refs_more_than_64"))
 
 
 def error_cases():
@@ -142,6 +214,7 @@ def error_cases():
         ("fault_in_last_row", good + few),
         ("fault_in_last_row_no_newline", good + no_tag[:-1]),
         ("bad_tag_before_column_fault", good + bad_tag + good + few + good),                                          # the earlier row's tag is the error
+        ("slow_row_70_of_100_is_5x", slow_text(700, 7, bad=70)[0]),                                                   # behind 69 rows the host resolves
         ("empty_text", b""),
         ("only_blank_lines", b"\n\r\n\n"),
     ]

@@ -18,9 +18,9 @@ VIEW_ARRAYS = {
 }
 
 
-def build_emul(out_dir):
-    """tests/host_emul_read built into out_dir -> (library, path of the sanitizer program)."""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "host_emul_read"), f"OUT={out_dir}"], check=True)
+def build_emul(out_dir, san=True):
+    """tests/host_emul_read built into out_dir -> (library, path of the sanitizer program); san = False: the library alone."""
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "host_emul_read"), f"OUT={out_dir}"] + ([] if san else [f"{out_dir}/libaasm_emul_read.so"]), check=True)
     lib = C.CDLL(os.path.join(str(out_dir), "libaasm_emul_read.so"))
     lib.emr_parse_device.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emr_free.argtypes = [C.c_void_p]

@@ -1,9 +1,11 @@
 """GPU tier of the device reader: aasm_paf_parse_device (kernels aasm_read_* on the MI355X) on every case of tests/read_cases.py
-against the host reader, the I/O oracle and an uploaded batch; the error contract; parse_device -> solve -> fetch -> cut plans ->
+against the host reader, the I/O oracle and an uploaded batch, the large and long-row ones again with capped grids; the pipe path of
+aasm_paf_read_device; the error contract; parse_device -> solve -> fetch -> cut plans ->
 written files end to end; `alignasm --device-reader`; device memory after a read."""
 import ctypes as C
 import os
 import subprocess
+import threading
 
 import numpy as np
 import pytest
@@ -46,7 +48,10 @@ def test_device_reader_equals_host_reader_oracle_and_upload(T, cases, name):
     host = api.Paf.parse(case["text"], device_ranges=True)
     up = api.DeviceBatch(host)                                       # what aasm_upload_batch gives for the host-read container
     want_dev = X.view_arrays(up.dev_view, fetch)
-    for flags in (0, _abi.AASM_READ_H_WEAK_HASH) if case["weak"] else (0,):
+    modes = [0] + ([_abi.AASM_READ_H_WEAK_HASH] if case["weak"] else [])
+    if RC.few_blocks(case):                                          # 3 blocks per grid: the grid-stride loops, wave operations inside
+        modes += [f | _abi.AASM_READ_H_FEW_BLOCKS for f in modes]
+    for flags in modes:
         before = api.debug_counter("read_host_fallbacks")
         paf, db = api.Paf.parse_device(case["text"], _flags=flags)
         assert api.debug_counter("read_host_fallbacks") == before   # conditions, not measurements: the device did the work ...
@@ -60,6 +65,8 @@ def test_device_reader_equals_host_reader_oracle_and_upload(T, cases, name):
 
 def test_case_list_is_complete(cases):
     assert sorted(_case_ids()) == sorted(c["name"] for c in cases)
+    few = [c["name"] for c in cases if RC.few_blocks(c)]
+    assert {"synth_file", "refs_more_than_64", "long_one_row_per_tile", "long_1mib_only", "ref_names_5000_differ_in_last_byte"} <= set(few)
 
 
 def test_device_reader_halves(T, cases):
@@ -75,6 +82,30 @@ def test_device_reader_halves(T, cases):
     assert api.LIB.aasm_paf_parse_device(text, len(text), 0, 0, C.byref(h), None, None) == 0
     only = api.Paf(h)
     assert only.to_text() == paf.to_text()
+
+
+@pytest.mark.parametrize("which", ["tiny", "long_1mib_between"])
+def test_read_device_from_a_pipe(T, cases, which, tmp_path):
+    """aasm_paf_read_device on what is no regular file: read into memory, then the same as parse_device on those bytes."""
+    api = T.api()
+    fetch = X.hip_fetcher(api)
+    text = open(os.path.join(G, "files", "tiny.paf"), "rb").read() if which == "tiny" else next(c for c in cases if c["name"] == which)["text"]
+    fifo = str(tmp_path / "in.paf")
+    os.mkfifo(fifo)
+
+    def write():
+        with open(fifo, "wb") as f:
+            f.write(text)
+    writer = threading.Thread(target=write, daemon=True)
+    writer.start()
+    paf, db = api.Paf.read_device(fifo)                              # (opens the pipe first of all, which lets the writer go)
+    writer.join(10)
+    assert not writer.is_alive()
+    want_paf, want_db = api.Paf.parse_device(text)
+    assert X.diff_views(X.view_arrays(want_paf.view()), X.view_arrays(paf.view())) == [] and paf.to_text() == want_paf.to_text()
+    assert X.diff_views(X.view_arrays(want_db.dev_view, fetch), X.view_arrays(db.dev_view, fetch)) == []
+    assert X.diff_views(X.host_read(api, text)[1], X.view_arrays(db.dev_view, fetch)) == []
+    db.close(); want_db.close()
 
 
 # ---- 2. errors ----------------------------------------------------------------------------------------------------------------

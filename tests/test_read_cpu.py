@@ -35,6 +35,7 @@ def test_header_declares_the_device_reader():
     assert re.search(r"int\s+aasm_paf_parse_device\s*\(\s*const\s+char\s*\*\s*text\s*,\s*int64_t\s+len\s*," + tail, src)
     assert re.search(r"int\s+aasm_paf_read_device\s*\(\s*const\s+char\s*\*\s*path\s*," + tail, src)
     assert re.search(r"#define\s+AASM_READ_H_WEAK_HASH\s+0x100\b", src) and _abi.AASM_READ_H_WEAK_HASH == 0x100
+    assert re.search(r"#define\s+AASM_READ_H_FEW_BLOCKS\s+0x200\b", src) and _abi.AASM_READ_H_FEW_BLOCKS == 0x200
     assert re.search(r"#define\s+AASM_READ_DEVICE_RANGES\s+1\b", src) and _abi.AASM_READ_DEVICE_RANGES == 1
     assert re.search(r"#define\s+AASM_ABI_VERSION\s+3\b", src)
 
@@ -86,6 +87,16 @@ def test_case_list_is_what_the_kernels_assume(emr, cases):
     assert wide.rindex(b"wide\t") - wide.index(b"wide\t") > 2 * RC.TILE
     for extra in (1, 7, 8, 9, 15, 16, 17):
         assert len(by["len_tile_plus_%d" % extra]) == RC.TILE + extra == len(by["len_tile_plus_%d_open" % extra])
+    edges = by["names_straddle_tile_edges"]
+    assert edges[RC.TILE - 21:RC.TILE + 21] == b"\n" + b"Q" * 39 + b"q\t" and edges[2 * RC.TILE - 21:2 * RC.TILE + 21] == b"\t" + b"R" * 39 + b"r\t"
+    per_tile = by["long_one_row_per_tile"]
+    assert [per_tile[:20 * RC.TILE].count(b"\n", t * RC.TILE, (t + 1) * RC.TILE) for t in range(20)] == [1] * 20
+    assert all(per_tile[(t + 1) * RC.TILE - 1] == 10 for t in range(20))
+    big = by["long_1mib_only"]
+    assert big.count(b"\n") == 1 and len(big) > 64 * RC.TILE
+    for name, tiles in (("slow_rows_64", 3), ("slow_rows_65", 3), ("slow_rows_300", 2)):        # the slow rows lie in several tiles
+        starts = [m.start() for m in re.finditer(rb"\t[+ ][0-9]+\t|\t1[0-9]{18}\t", by[name])]
+        assert len(starts) == int(name.rsplit("_", 1)[1]) and len({s // RC.TILE for s in starts}) >= tiles
 
 
 def _case_ids():
@@ -190,7 +201,8 @@ def test_framing_cases_under_the_address_sanitizer(T, emr, cases, tmp_path):
     _, san = emr
     framing = cases[:[c["name"] for c in cases].index("synth_file")]
     framing += [c for c in cases if c["name"] in ("bare_cs", "slow_row_last_no_newline", "contig_spans_three_tiles", "refs_more_than_64")]
-    assert len(framing) >= 26
+    framing += [c for c in cases if c["name"].startswith("long_") or c["name"] in ("names_straddle_tile_edges", "empty_query_name", "slow_rows_65")]
+    assert len(framing) >= 53
     paths, want = [], []
     for c in framing:
         p = tmp_path / (c["name"] + ".paf")
