@@ -239,3 +239,164 @@ def golden_case_batch(api, golden, file_level, accepted_text):
     for t in tmp:                                                    # the element order elements() produces
         where["main"] += t["main"]; where["alt"] += t["alt"]; where["all"] += t["all"][0] + t["all"][1]
     return paf, rows, elements(per), where
+
+
+# ---- hand-made lists for the kernel's chunk loop (tests/test_cuts_cpu.py in the emulation, tests/test_gpu_cuts.py on the card) ----
+CHUNK = 2048                                                         # AASM_CUT_CHUNK (the emulation library reports it: emc_chunk)
+EDGE_SIZES = (1, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK, 2 * CHUNK + 1)
+# elements per contig (main, alt), cycled until the list is full: offsets meet both chunk edges, with contigs of no element on them
+CONTIG_PATTERN = (1, 0, CHUNK - 2, 1, 0, 0, 1, CHUNK - 1, 0, 1)
+# elements per .all path: empty paths, path ends on the edges, and (the second one) paths that straddle them
+PATH_PATTERNS = ((0, 1, 1500, CHUNK - 1501, 0, 0, 1, 1300, CHUNK - 1301, 0, 1), (3, 0, 2000, 100, 0, 1945, 60, 0, 1))
+EDGE_CONTIGS, EDGE_RECORDS = 24, 3
+
+
+def _split(n, pattern):
+    """n items dealt into pieces of the pattern's sizes, cycled; the empty pieces in between are kept."""
+    out, k = [], 0
+    while n > 0:
+        out.append(min(n, pattern[k % len(pattern)]))
+        n -= out[-1]
+        k += 1
+    return out
+
+
+def edge_text(T, paf_line):
+    """A small file of EDGE_CONTIGS contigs x EDGE_RECORDS records made from valid cs-codec rows -> (text, rows, per row a pool of
+    re-cut clips with exact reference coordinates, every one accepted or refused by the host codec alone)."""
+    import random
+    import cs_cases as G
+    rng = random.Random(2048)
+    rows, pools = [], []
+    for row in G.rows(31, 200, 0):
+        got = T.product_cs_ranges(row)
+        if got[0] == "err" or row["qe"] - row["qs"] < 3 or len(row["cs"]) > 400:
+            continue
+        pool = [c for c in G.clips(rng, row, [(a, b, c) for a, b, c, _ in got[1]], 12) if (c[0], c[1]) != (row["qs"], row["qe"])]
+        if len(pool) >= 4:
+            rows.append(row); pools.append(pool)
+        if len(rows) == EDGE_CONTIGS * EDGE_RECORDS:
+            break
+    assert len(rows) == EDGE_CONTIGS * EDGE_RECORDS
+    text = b"".join(paf_line(r, "e%d" % (i // EDGE_RECORDS)) for i, r in enumerate(rows))
+    return text, rows, pools
+
+
+def edge_lists(rows, pools, n_main, n_alt, n_all, mode, variant=0):
+    """Result arrays with exactly n_main / n_alt / n_all elements laid out by CONTIG_PATTERN and PATH_PATTERNS[variant].
+    mode: "cut" (every element re-cut), "none" (every element spans its record), "mixed"."""
+    import random
+    rng = random.Random("%d %d %d %s %d" % (n_main, n_alt, n_all, mode, variant))
+
+    def element(c):
+        i = rng.randrange(EDGE_RECORDS)
+        row, pool = rows[c * EDGE_RECORDS + i], pools[c * EDGE_RECORDS + i]
+        if mode == "none" or (mode == "mixed" and rng.random() < 0.5):
+            return (row["qs"], row["qe"], row["rs"], row["re"], i)
+        return tuple(rng.choice(pool)) + (i,)
+    per = [{"main": [], "alt": [], "all": []} for _ in range(EDGE_CONTIGS)]
+    for k, n in (("main", n_main), ("alt", n_alt)):
+        sizes = _split(n, CONTIG_PATTERN)
+        assert len(sizes) <= EDGE_CONTIGS - 2
+        for c, m in enumerate(sizes):                                # (contig 0 ... ; the last two contigs hold nothing)
+            per[c + (1 if k == "alt" else 0)][k] = [element(c + (1 if k == "alt" else 0)) for _ in range(m)]
+    paths = _split(n_all, PATH_PATTERNS[variant])
+    c = 0
+    for p in range(0, len(paths), 2):                                # two paths per contig, every third contig without any
+        if c % 3 == 2:
+            c += 1
+        per[c]["all"] = [[element(c) for _ in range(m)] for m in paths[p:p + 2]]
+        c += 1
+    assert c <= EDGE_CONTIGS
+    return elements(per)
+
+
+def edge_cases():
+    """(n_main, n_alt, n_all, mode, variant): every list at every size of EDGE_SIZES in every mode."""
+    out = []
+    for m, mode in enumerate(("cut", "none", "mixed")):
+        for s in range(len(EDGE_SIZES)):
+            out.append((EDGE_SIZES[s], EDGE_SIZES[(s + 2) % 6], EDGE_SIZES[(s + 4) % 6], mode, (s + m) % 2))
+    return out
+
+
+def check_by_key(T, va, out, plans):
+    """check_against_host on one element of every distinct (record, clip); every other element's plan equals its
+    representative's byte for byte.  Returns check_against_host's counts (of the representatives)."""
+    rec = record_of(out, va["ctg_rec_off"])
+    which = {}
+    for k in LISTS:
+        if not len(out[k]):
+            continue
+        key = np.stack([rec[k], out[k]["qs"], out[k]["qe"], out[k]["rs"], out[k]["re"]], 1)
+        _, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+        p = np.ascontiguousarray(plans[k]).view(np.int64).reshape(-1, 6)
+        assert np.array_equal(p, p[first[inverse.reshape(-1)]]), k
+        which[k] = [int(i) for i in first]
+    return check_against_host(T, va, out, plans, which)
+
+
+RECORD_PLAN = np.array([0, 0, 0, 0, 0, AASM_CUT_E_RECORD], np.int64).tobytes()
+
+
+def record_fault_lists(rows, pools):
+    """-> (good, bad, where): lists of 2 * CHUNK + 1 elements each, and the same with ctg_index -1 or the contig's record count
+    at where[list]: the first and the last element of both chunks and a few inside.  The last main element belongs to the
+    file's last contig, where the record index of the second kind is n_records."""
+    good = edge_lists(rows, pools, 2 * CHUNK + 1, 2 * CHUNK + 1, 2 * CHUNK + 1, "mixed", 0)
+    off, last = good["main_off"], rows[(EDGE_CONTIGS - 1) * EDGE_RECORDS]
+    off[(off == off[-1]) & (np.arange(len(off)) < EDGE_CONTIGS)] = off[-1] - 1
+    good["main"][-1] = (last["qs"], last["qe"], last["rs"], last["re"], 0, 0)
+    bad = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in good.items()}
+    where = {}
+    for k in LISTS:
+        where[k] = [0, CHUNK - 1, CHUNK, 2 * CHUNK - 1, 777, 2 * CHUNK, 1, 3000]
+        for j, i in enumerate(where[k]):
+            bad[k]["ctg_index"][i] = -1 if j % 2 == 0 else EDGE_RECORDS
+    return good, bad, where
+
+
+def check_record_faults(good_plans, bad_plans, where):
+    for k in LISTS:
+        g = np.ascontiguousarray(good_plans[k]).view(np.int64).reshape(-1, 6)
+        b = np.ascontiguousarray(bad_plans[k]).view(np.int64).reshape(-1, 6)
+        assert len(b) == 2 * CHUNK + 1
+        for i in where[k]:
+            assert b[i].tobytes() == RECORD_PLAN, (k, i, b[i])       # flags exactly 0x80, every other word 0
+        keep = np.ones(len(b), bool)
+        keep[where[k]] = False
+        assert np.array_equal(g[keep], b[keep]), k                   # the neighbours' plans are untouched
+
+
+def damaged_corpus():
+    """The rows and clips of the damaged-tag test: a few valid tags, every damaged one (both strands); ten clips per row."""
+    import random
+    import cs_cases as G
+    rng = random.Random(77)
+    rows = [r for r in G.rows(5, 60, 400)]
+    rows = rows[:60] + rows[2 * (60 + len(G.ODD_VALID)):]
+    per = []
+    for r in rows:
+        qs, qe = r["qs"], r["qe"]
+        cl = [(qs, qe), (qs + 1, qe), (qs, qe - 1), (qs - 1, qe + 1), (qe, qs)]
+        for _ in range(5):
+            a = rng.randint(qs, qe)
+            cl.append((a, rng.randint(a, qe)))
+        per.append({"main": [(a, b, r["rs"], r["re"], 0) for a, b in cl]})
+    return rows, per
+
+
+def random_clip_corpus(T, n_valid=700, n_clips=5):
+    """tests/cs_cases.py's rows the host codec takes, with their random clips (ends on matched bases, anywhere, inconsistent
+    reference spans) as main elements of one-record contigs -> (rows, per_contig)."""
+    import random
+    import cs_cases as G
+    rng = random.Random(20261017)
+    rows, per = [], []
+    for row in G.rows(rng.randrange(1 << 30), n_valid, 0):
+        got = T.product_cs_ranges(row)
+        if got[0] == "err":
+            continue
+        rows.append(row)
+        per.append({"main": [tuple(cl) + (0,) for cl in G.clips(rng, row, [(a, b, c) for a, b, c, _ in got[1]], n_clips)]})
+    return rows, per

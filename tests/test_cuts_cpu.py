@@ -15,7 +15,7 @@ import pytest
 import cs_cases as G
 import cuts_testlib as X
 from alignasm_amd import _abi
-from test_cs_ref import _accepted_text, _file_level
+from test_cs_ref import _accepted_text, _file_level, _paf_line
 from test_export_cpu import CASE_IDS, CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -158,6 +158,62 @@ def test_emulated_kernel_equals_the_real_reference_codec_live(T, emc):
     assert sum(n["cut"].values()) > 1500 and n["err"] > 100, n
 
 
+def edge_file(T):
+    """-> (Paf with the tags in its view, rows, clip pools) of the chunk-edge cases."""
+    text, rows, pools = X.edge_text(T, _paf_line)
+    return T.api().Paf.parse(text, device_ranges=True), rows, pools
+
+
+def assert_edge_case(T, va, out, plans, case):
+    n_main, n_alt, n_all, mode, _ = case
+    assert (len(out["main"]), len(out["alt"]), len(out["all"])) == (n_main, n_alt, n_all)
+    n_cut = sum(int((plans[k]["flags"] & _abi.AASM_CUT_IS_CUT != 0).sum()) for k in X.LISTS)
+    total = n_main + n_alt + n_all
+    assert n_cut == (total if mode == "cut" else 0 if mode == "none" else n_cut) and (mode != "mixed" or 0.3 * total < n_cut < 0.7 * total)
+    n = X.check_by_key(T, va, out, plans)
+    assert n["elements"] > 0 and (mode == "none" or n["cut"] > 0)
+
+
+@pytest.mark.parametrize("case", X.edge_cases(), ids=lambda c: "%d_%d_%d_%s" % c[:4])
+def test_emulated_kernel_at_the_chunk_edges(T, emc, case):
+    """Lists of 1, 2047, 2048, 2049, 4096 and 4097 elements, all cut (the LDS list fills to exactly a chunk), none cut and mixed;
+    contigs without elements on the chunk edges, .all paths that end on them or straddle them, empty paths; one block per chunk
+    and one block for all of them.  Every plan against the host codec."""
+    assert emc[0].emc_chunk() == X.CHUNK
+    paf, rows, pools = edge_file(T)
+    out = X.edge_lists(rows, pools, *case)
+    va = X.view_arrays(paf.view())
+    plans = X.emul_plans(emc[0], paf.view(), out)
+    assert_edge_case(T, va, out, plans, case)
+    again = X.emul_plans(emc[0], paf.view(), out, 1)
+    for k in X.LISTS:
+        assert again[k].tobytes() == plans[k].tobytes()
+
+
+def test_emulated_kernel_flags_elements_outside_their_contig(T, emc):
+    """AASM_CUT_E_RECORD: ctg_index -1 and ctg_index = the contig's record count (in the last contig: record n_records), as the
+    first and the last element of a chunk and inside: flags exactly 0x80, every other word 0, the neighbours untouched."""
+    paf, rows, pools = edge_file(T)
+    good, bad, where = X.record_fault_lists(rows, pools)
+    va = X.view_arrays(paf.view())
+    assert X.record_of(bad, va["ctg_rec_off"])["main"][-1] == len(rows) == paf.view().n_records
+    for max_blocks in (0, 1):
+        gp = X.emul_plans(emc[0], paf.view(), good, max_blocks)
+        X.check_record_faults(gp, X.emul_plans(emc[0], paf.view(), bad, max_blocks), where)
+    assert not any(int(f) & _abi.AASM_CUT_E_RECORD for k in X.LISTS for f in gp[k]["flags"])
+
+
+def test_emulated_kernel_equals_the_host_codec_on_random_clips(T, emc):
+    """tests/cs_cases.py's random clips (ends on matched bases, anywhere in the record, inconsistent reference spans) of 1 400
+    accepted rows against the host codec: the corpus the live-reference test runs where the reference is built."""
+    rows, per = X.random_clip_corpus(T)
+    out = X.elements(per)
+    rb = X.RowsBatch(rows)
+    va = {**rb.a, "ref_str": np.array([r["rs"] for r in rows], np.int64), "ref_end": np.array([r["re"] for r in rows], np.int64)}
+    n = X.check_against_host(T, va, out, X.emul_plans(emc[0], rb.view, out))
+    assert n["cut"] > 1500 and n["errors"] > 100 and n["irregular"] > 0, n
+
+
 # ---- 3. the kernel against the host codec on solver output -------------------------------------------------------------------
 def solved_case(T, case):
     nc, nr, seed, K, dense, dup, shuf, heavy, nsl = case
@@ -213,18 +269,8 @@ def test_planned_writer_reads_the_plans(T, emc, tmp_path):
 
 # ---- 5. damaged tags under the host address sanitizer -------------------------------------------------------------------------
 def test_damaged_tags_stay_inside_the_tag_under_the_sanitizer(T, emc, tmp_path):
-    rng = random.Random(77)
-    rows = [r for r in G.rows(5, 60, 400)]
-    rows = rows[:60] + rows[2 * (60 + len(G.ODD_VALID)):]           # a few valid ones, every damaged one (both strands)
+    rows, per = X.damaged_corpus()
     assert set(G.DAMAGED) <= {r["cs"] for r in rows} and len(rows) > 800
-    per = []
-    for r in rows:
-        qs, qe = r["qs"], r["qe"]
-        cl = [(qs, qe), (qs + 1, qe), (qs, qe - 1), (qs - 1, qe + 1), (qe, qs)]
-        for _ in range(5):
-            a = rng.randint(qs, qe)
-            cl.append((a, rng.randint(a, qe)))
-        per.append({"main": [(a, b, r["rs"], r["re"], 0) for a, b in cl]})
     out = X.elements(per)
     rb = X.RowsBatch(rows)
     plans = X.emul_plans(emc[0], rb.view, out)["main"]

@@ -125,3 +125,27 @@ def test_device_dijkstra_rejects_bad_input(T):
     with pytest.raises(api.AlignasmError) as e:
         api.sssp_dijkstra([0, 2], [0, 1, 1], [1], [-5, 1, 0, 0, 1], [0])
     assert e.value.code == -5
+
+
+@pytest.mark.gpu
+def test_device_dijkstra_takes_the_heap_retry(T):
+    """tests/test_sssp_cpu.py's heap_retry_graph(): the heap holds more entries than the E + 2 of the driver's first run (DESIGN.md,
+    `dijkstra_run`: "heap sized E + 2 per graph, rerun at 4x / 16x / 64x"), which overflows; the run with four times the room
+    finishes.  Alone, and in a batch beside graphs that fit the first run, against the oracle's d and prev.  The entry reports no
+    retry, so that one is taken follows only from the host model of the queue (_heap_peak) and that documented room: were the
+    driver to give its first run more room, this test would go on passing without the retry."""
+    from test_sssp_cpu import _heap_peak, batch, heap_retry_graph
+    api = T.api()
+    n, rp, col, w, src = heap_retry_graph()
+    first_run = len(col) + 2                               # the documented room of the first run
+    assert first_run < _heap_peak(n, rp, col, w, src) <= 4 * first_run
+    do, po = run(T.oracle(), "oracle_", n, rp, col, w, src)
+    d, prev = api.sssp_dijkstra([0, n], rp, col, w, [src])
+    assert np.array_equal(d, do) and np.array_equal(prev, po)
+    assert d[3][3] == 1 and prev[3] == 1                   # the leaves carry the improved ratio
+    small = cases()[:4]
+    voff, rowptr, cl, ww, s = batch(small + [(n, rp, col, w, src)] + small[:2])
+    d, prev = api.sssp_dijkstra(voff, rowptr, cl, ww, s)
+    for i, (n1, rp1, c1, w1, s1) in enumerate(small + [(n, rp, col, w, src)] + small[:2]):
+        do1, po1 = run(T.oracle(), "oracle_", n1, rp1, c1, w1, s1)
+        assert np.array_equal(d[voff[i]:voff[i + 1]], do1) and np.array_equal(prev[voff[i]:voff[i + 1]], po1), i

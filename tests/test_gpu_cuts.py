@@ -1,17 +1,24 @@
 """GPU tier of the cut plans: aasm_cut_plans_device (kernel aasm_cut_plans on the MI355X) against the vectors recorded from the
 reference's get_edited_paf_data and against the host codec on solver output, through DeviceBatch -> solve -> to_torch(cuts=batch);
 the planned writer on plans fetched from the device; one full-size run; the entry's argument checks; plans across a later solve
-and on a side stream."""
+and on a side stream; hand-made lists at the chunk edges, more chunks than blocks (the grid-stride loop), elements outside their contig,
+damaged tags and random clips."""
 import numpy as np
 import pytest
 
 import cuts_testlib as X
 from alignasm_amd import _abi
-from test_cs_ref import _accepted_text, _file_level
-from test_cuts_cpu import assert_fixture_was_covered, check_recorded
+from test_cs_ref import _accepted_text, _file_level, _paf_line
+from test_cuts_cpu import assert_edge_case, assert_fixture_was_covered, check_recorded, edge_file
 from test_export_cpu import CASE_IDS, CASES
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def emc(tmp_path_factory):
+    """The emulated kernel, what the device plans of damaged tags are compared with."""
+    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_gpu"))[0]
 
 
 @pytest.fixture(scope="module")
@@ -211,3 +218,117 @@ def test_export_and_cut_on_a_side_stream_while_the_default_stream_is_busy(T, tor
     torch.cuda.synchronize()
     assert bool(torch.isfinite(a).all())
     res.close(); db.close()
+
+
+# ---- the chunk loop, on hand-made lists ---------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def edges(T, torch):
+    paf, rows, pools = edge_file(T)
+    db = T.api().DeviceBatch(paf)
+    yield paf, rows, pools, db, X.view_arrays(paf.view())
+    db.close()
+
+
+@pytest.mark.parametrize("case", X.edge_cases(), ids=lambda c: "%d_%d_%d_%s" % c[:4])
+def test_device_kernel_at_the_chunk_edges(T, torch, edges, case):
+    """The emulation tier's cases (test_emulated_kernel_at_the_chunk_edges) with 256 lanes per block: the ballot compaction and
+    the LDS atomic fill the list to exactly a chunk, one short of it and one into the next.  Every plan against the host codec."""
+    paf, rows, pools, db, va = edges
+    out = X.edge_lists(rows, pools, *case)
+    assert_edge_case(T, va, out, X.device_plans(T.api(), db, out), case)
+
+
+def test_device_kernel_flags_elements_outside_their_contig(T, torch, edges):
+    """AASM_CUT_E_RECORD on the card: ctg_index -1 and ctg_index = the contig's record count (in the last contig: record
+    n_records), first and last in a chunk and inside: flags exactly 0x80, every other word 0, the neighbours untouched."""
+    paf, rows, pools, db, va = edges
+    good, bad, where = X.record_fault_lists(rows, pools)
+    assert X.record_of(bad, va["ctg_rec_off"])["main"][-1] == len(rows) == db.n_records
+    X.check_record_faults(X.device_plans(T.api(), db, good), X.device_plans(T.api(), db, bad), where)
+
+
+def test_more_chunks_than_blocks_take_the_grid_stride_loop(T, torch):
+    """The recorded-vector batch with every contig's main, alt and .all elements tiled until the three lists hold more than
+    4 400 chunks of 2 048 elements (the grid is capped at 4 096 blocks): blocks take a second chunk with the LDS list and the
+    search bounds of the first, and for some of them (asserted below) the first chunk is of main or alt and the second of .all.
+    The plans equal the un-tiled run's, gathered through the same index, byte for byte (on the device: the arrays hold
+    0.9 GB)."""
+    api = T.api()
+    paf, rows, out, where = X.golden_case_batch(api, X.golden_cs(T), _file_level, _accepted_text)
+    db = api.DeviceBatch(paf)
+    small = X.device_plans(api, db, out)
+    n_small = sum(len(out[k]) for k in X.LISTS)
+    t = (4400 * X.CHUNK) // n_small + 1
+    C = out["n_contigs"]
+    idx = {}
+    for k in ("main", "alt"):
+        o = out[k + "_off"]
+        idx[k] = np.concatenate([np.tile(np.arange(o[c], o[c + 1]), t) for c in range(C)])
+    po, eo = out["all_path_off"], out["all_elem_off"]
+    path_idx = np.concatenate([np.tile(np.arange(po[c], po[c + 1]), t) for c in range(C)])     # every contig's paths, t times
+    lens = np.diff(eo)[path_idx]
+    big_eo = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    idx["all"] = (np.repeat(eo[path_idx] - big_eo[:-1], lens) + np.arange(big_eo[-1])).astype(np.int64)
+    offs = {"main_off": out["main_off"] * t, "alt_off": out["alt_off"] * t, "all_path_off": po * t, "all_elem_off": big_eo}
+    ch0 = np.cumsum([0] + [-(-len(idx[k]) // X.CHUNK) for k in X.LISTS])      # list l owns the chunks [ch0[l], ch0[l + 1])
+    n_chunks, blocks = int(ch0[3]), 4096                                       # AASM_CUT_MAX_BLOCKS
+    assert n_chunks > blocks + 256 and all(len(idx[k]) > 2 * X.CHUNK for k in X.LISTS)
+    second = np.arange(blocks, n_chunks)                                       # block b's second chunk is chunk b + 4096
+    l_first, l_second = np.searchsorted(ch0, second - blocks, "right") - 1, np.searchsorted(ch0, second, "right") - 1
+    assert ((l_first < 2) & (l_second == 2)).any()                             # blocks go from main or alt on to .all, whose search starts at the paths
+    dev = torch.device("cuda", db.device)
+    el_small = {k: torch.from_numpy(np.ascontiguousarray(out[k]).view(np.int64).reshape(-1, 5)).to(dev) for k in X.LISTS}
+    p_small = {k: torch.from_numpy(np.ascontiguousarray(small[k]).view(np.int64).reshape(-1, 6)).to(dev) for k in X.LISTS}
+    ix = {k: torch.from_numpy(idx[k]).to(dev) for k in X.LISTS}
+    el = {k: el_small[k][ix[k]].contiguous() for k in X.LISTS}
+    t_off = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).to(dev) for k, v in offs.items()}
+    plans = {k: torch.full((len(idx[k]), 6), 0x5a5a5a5a5a5a5a5a, dtype=torch.int64, device=dev) for k in X.LISTS}
+    sizes = _abi.OutSizes(C, len(idx["main"]), len(idx["alt"]), len(big_eo) - 1, len(idx["all"]))
+    dev_out = _abi.DevOut(t_off["main_off"].data_ptr(), t_off["alt_off"].data_ptr(), t_off["all_path_off"].data_ptr(), t_off["all_elem_off"].data_ptr(),
+                          el["main"].data_ptr(), el["alt"].data_ptr(), el["all"].data_ptr(), None)
+    st = torch.cuda.current_stream(dev)
+    rc = api.cut_plans_raw(db.dev_view, sizes, dev_out, _abi.DevCuts(*(plans[k].data_ptr() for k in X.LISTS)), db.device, st.cuda_stream)
+    assert rc == 0, (rc, api.LIB.aasm_last_error())
+    st.synchronize()
+    for k in X.LISTS:
+        assert bool(torch.equal(plans[k], p_small[k][ix[k]])), k
+    db.close()
+
+
+def test_device_kernel_equals_the_emulation_on_damaged_tags(T, torch, emc):
+    """The damaged-tag corpus and clips of the sanitizer test, the rows the reader takes with device ranges (the others lack the
+    'cs:Z:' prefix, a reader error): the device plans equal the emulated kernel's byte for byte."""
+    api = T.api()
+    rows, per = X.damaged_corpus()
+    taken = []
+    for i, r in enumerate(rows):
+        try:
+            api.Paf.parse(_paf_line(r, "d"), device_ranges=True).close()
+            taken.append(i)
+        except api.AlignasmError:
+            pass
+    assert len(taken) >= 800 and len(rows) - len(taken) >= 20
+    paf = api.Paf.parse(b"".join(_paf_line(rows[i], "d%d" % i) for i in taken), device_ranges=True)
+    assert paf.n_contigs == len(taken)
+    out = X.elements([per[i] for i in taken])
+    want = X.emul_plans(emc, paf.view(), out)
+    db = api.DeviceBatch(paf)
+    got = X.device_plans(api, db, out)
+    db.close()
+    assert got["main"].tobytes() == want["main"].tobytes() and len(want["main"]) == 10 * len(taken)
+    f = want["main"]["flags"]
+    assert (f & _abi.AASM_CUT_E_TAG != 0).sum() > 100 and (f & _abi.AASM_CUT_ERRORS == 0).sum() >= len(taken)
+
+
+def test_device_kernel_equals_the_host_codec_on_random_clips(T, torch):
+    """tests/cs_cases.py's random clips of 1 400 accepted rows (ends on matched bases, anywhere, inconsistent reference spans)
+    against the host codec."""
+    api = T.api()
+    rows, per = X.random_clip_corpus(T)
+    paf = api.Paf.parse(b"".join(_paf_line(r, "r%d" % i) for i, r in enumerate(rows)), device_ranges=True)
+    assert paf.n_contigs == len(rows)
+    out = X.elements(per)
+    db = api.DeviceBatch(paf)
+    n = X.check_against_host(T, X.view_arrays(paf.view()), out, X.device_plans(api, db, out))
+    db.close()
+    assert n["cut"] > 1500 and n["errors"] > 100 and n["irregular"] > 0, n
