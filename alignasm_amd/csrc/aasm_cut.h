@@ -214,12 +214,16 @@ AASM_DEV void kb_cut_plan(const KCtx &k, const CutArgs &a) {
     }
 }
 
-// The cut kernels: K(id, symbol, block, lanes, LDS bytes, body) as AASM_PIPELINE_KERNELS' LDS rows, body called as body(k, a).
+// The cut kernels (row shapes: aasm_dev.h; no register budget), body called as body(k, a).  All rows are KL rows: expanded as
+// AASM_CUT_KERNELS(K, KL) or with one macro, AASM_CUT_KERNELS(X), they go to the last macro given.
 // One lane per block in the host emulation: the body's barriers and its LDS list need the block's threads one after the other.
-#define AASM_CUT_KERNELS(K) \
-    K(KC_PLAN, aasm_cut_plans, 256, 1, AASM_CUT_LDS_BYTES, kb_cut_plan)
-enum CutKern { AASM_CUT_KERNELS(AASM_ROW_ID) };
-constexpr int cut_block[] = {AASM_CUT_KERNELS(AASM_ROW_BLOCK)};
+#define AASM_CUT_ROWS(KL) \
+    KL(KC_PLAN, aasm_cut_plans, 256, 1, AASM_CUT_LDS_BYTES, 0, kb_cut_plan)
+#define AASM_CUT_SECOND(K, KL, ...) KL
+#define AASM_CUT_KERNELS(...) AASM_CUT_ROWS(AASM_CUT_SECOND(__VA_ARGS__, __VA_ARGS__))
+enum CutKern { AASM_CUT_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
+constexpr int cut_block[] = {AASM_CUT_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
+AASM_KERNEL_BODY(run_cut_body, AASM_CUT_KERNELS, CutArgs)
 #define AASM_CUT_MAX_BLOCKS 4096         // 256-thread blocks: beyond 16 per CU the chunks are taken grid-stride
 
 // The arguments of a call whose arrays the caller has checked; false: the sizes do not fit the batch.

@@ -8,6 +8,7 @@
 //    arithmetic/indexing logic can be diffed against the oracle on a box without a GPU.
 //    That build is test infrastructure only; the product library never contains it.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(AASM_HOST_EMUL)
@@ -35,12 +36,29 @@ struct KCtx {
 };
 #define AASM_LDS_BYTES 6144   // 6 KB per single-wave block -> 26 blocks per CU by LDS
 
-// The kernel tables (AASM_PIPELINE_KERNELS, AASM_PACK_KERNELS, AASM_SSSP_KERNELS, AASM_KSW_KERNELS): one row per kernel, from which
-// the ids, the __global__ definitions and launches (aasm_gpu.hip) and the host emulation's launches are generated.  A row's lanes
-// are the threads of a block the host emulation runs: ALL_LANES (thread-per-item bodies), 1 (wave-per-item bodies: a wave is one
-// lane there) or one per wave.  A body that the emulation replaces is written AASM_EMUL_OR(host body, device body).
+// The kernel tables (AASM_PIPELINE_KERNELS, AASM_PACK_KERNELS, AASM_SSSP_KERNELS, AASM_KSW_KERNELS, AASM_CUT_KERNELS,
+// AASM_READ_KERNELS): a macro TABLE(K, KL) with one row per kernel, in id order, from which the ids, the block sizes, the body
+// dispatcher, the __global__ definitions and launches (aasm_gpu.hip) and the host emulation's launches (tests/host_emul/emul_launch.h) are generated:
+//   K(id, sym, block, lanes, body)               a plain kernel
+//   KL(id, sym, block, lanes, lds, waves, body)  one whose blocks keep a working set in LDS
+// id     the enumerator that names the kernel in launches (the row's index in its table)
+// sym    the __global__'s name, as profilers show it
+// block  the threads of every launch, and the kernel's __launch_bounds__
+// lanes  the threads of a block the host emulation runs: ALL_LANES (thread-per-item bodies), 1 (wave-per-item bodies: a wave is one
+//        lane there) or one per wave
+// lds    bytes of LDS per block, behind k.lds (nullptr in a K row)
+// waves  the waves per SIMD the kernel's registers are budgeted for (5: <= 96 VGPRs, 6: <= 80); 0: no budget, block alone bounds it
+// body   called as body(k, args) with the family's argument struct; last, so that a template-id's commas need no parentheses.
+//        A body that the emulation replaces is written AASM_EMUL_OR(host body, device body).
+// A table whose rows are all of one kind may also be expanded with that one macro, TABLE(X).
 #define AASM_ROW_ID(id, ...) id,
 #define AASM_ROW_BLOCK(id, sym, block, ...) block,
+#define AASM_ROW_CASE(id, sym, block, lanes, ...) case id: __VA_ARGS__(kb_k, kb_a); break;
+#define AASM_ROWL_CASE(id, sym, block, lanes, lds, waves, ...) case id: __VA_ARGS__(kb_k, kb_a); break;
+// name(id, k, args): the body of row `id`, for the __global__ kernels and the host emulation; defined behind each table (a table
+// cannot be expanded inside one of its own rows, so the dispatcher is a function)
+#define AASM_KERNEL_BODY(name, TABLE, Args) \
+    AASM_DEV void name(int id, const KCtx &kb_k, const Args &kb_a) { switch (id) { TABLE(AASM_ROW_CASE, AASM_ROWL_CASE) } }
 constexpr int ALL_LANES = 0;
 constexpr int emul_lanes(int block, int lanes) { return lanes == ALL_LANES ? block : lanes; }
 #if defined(AASM_HOST_EMUL)

@@ -1,7 +1,7 @@
 // aasm_gpu.hip -- gfx950 backend of the pipeline + the C-ABI entry points that touch the GPU.
 //
-// * one named __global__ per row of the kernel tables (aasm_pipeline.h, aasm_sssp.h, aasm_ksw.h; bodies: aasm_kernels.h), so
-//   rocprofv3 --kernel-trace shows `aasm_k6_rev_sweep` etc.;
+// * one named __global__ per row of the kernel tables (row shapes: aasm_dev.h; tables: aasm_pipeline.h, aasm_sssp.h, aasm_ksw.h,
+//   aasm_cut.h, aasm_read.h), from ONE generator, so rocprofv3 --kernel-trace shows `aasm_k6_rev_sweep` etc., and ONE launch (launch_row);
 // * the generic graph entries (dijkstra, Dial, k shortest walks): bodies, argument checks and host drivers in aasm_sssp.h and
 //   aasm_ksw.h, run here through one backend (GraphGpu);
 // * exclusive scans (count -> offsets): ONE launch each, single pass with decoupled look-back (aasm_scan_chain);
@@ -42,44 +42,62 @@ __device__ inline int64_t xcd_bid(int64_t b, int64_t g, int on) {
     const int64_t g8 = g & ~(int64_t)7;
     return b < g8 ? (b & 7) * (g8 >> 3) + (b >> 3) : b;
 }
-// one __global__ per row of the kernel tables; k, its thread's KCtx: block `bid` of the launch's work, `lds` the block's LDS or nullptr
+// One __global__ per row of a kernel table: sym(the family's parameters) runs the row's body as its thread's KCtx k, for block `bid`
+// of the launch's work, with the block's LDS (KL rows) or nullptr.  What the kernels of a table share is its family, named by
+// AASM_FAMILY while the table is expanded: the parameter list, the block's work item, the argument of the bodies, and how the body is
+// called - AASM_DIRECT, or AASM_BY_ID through run_kernel_body for the pipeline, 14 of whose kernels compile to other code when called directly.
 #define AASM_KCTX(bid, lds) KCtx k{(int)threadIdx.x, (int)blockDim.x, bid, (int64_t)gridDim.x, (int)(threadIdx.x & 63), lds}
 #define AASM_SMEM(bytes) __shared__ __attribute__((aligned(16))) char smem[bytes]
 #define AASM_XCD_BID xcd_bid((int64_t)blockIdx.x, (int64_t)gridDim.x, w.xcd_map)
-#define K(id, sym, block, lanes, ...) \
-    __global__ void __launch_bounds__(block) sym(WS w) { AASM_KCTX(AASM_XCD_BID, nullptr); run_kernel_body(id, k, w); }
-#define KL(id, sym, block, lanes, lds, waves, ...) \
-    __global__ void __launch_bounds__(block, waves) sym(WS w) { AASM_SMEM(lds); AASM_KCTX(AASM_XCD_BID, smem); run_kernel_body(id, k, w); }
+#define AASM_DIRECT(arg, id, ...) __VA_ARGS__(k, arg)
+#define AASM_BY_ID(arg, id, ...) run_kernel_body(id, k, arg)
+#define AASM_GLOBAL(params, bid, arg, call, bounds, sym, smem_decl, lds, id, ...) \
+    __global__ void bounds sym params { smem_decl AASM_KCTX(bid, lds); call(arg, id, __VA_ARGS__); }
+#define AASM_GLOBAL_OF(...) AASM_GLOBAL(__VA_ARGS__)
+#define K(id, sym, block, lanes, ...) AASM_GLOBAL_OF(AASM_FAMILY, __launch_bounds__(block), sym, , nullptr, id, __VA_ARGS__)
+#define KL(id, sym, block, lanes, lds, waves, ...) AASM_GLOBAL_OF(AASM_FAMILY, __launch_bounds__(block, waves), sym, AASM_SMEM(lds);, smem, id, __VA_ARGS__)
+// the pipeline (bodies: aasm_kernels.h, aasm_enum.h)
+#define AASM_FAMILY (WS w), AASM_XCD_BID, w, AASM_BY_ID
 AASM_PIPELINE_KERNELS(K, KL)
-#undef K
-#undef KL
+#undef AASM_FAMILY
 // the device-side export of a result (aasm_result_sizes / aasm_result_export)
-#define K(id, sym, block, lanes, ...) \
-    __global__ void __launch_bounds__(block) sym(PackArgs a) { AASM_KCTX((int64_t)blockIdx.x, nullptr); run_pack_body(id, k, a); }
-AASM_PACK_KERNELS(K)
-#undef K
-// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, K5 Dial) and aasm_ksw.h (★K: a launch covers the graphs [g0, g0 + grid))
-#define K(id, sym, block, lanes, ...) \
-    __global__ void __launch_bounds__(block) sym(SsspArgs a) { AASM_KCTX((int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
-#define KL(id, sym, block, lanes, lds, ...) \
-    __global__ void __launch_bounds__(block) sym(SsspArgs a) { AASM_SMEM(lds); AASM_KCTX((int64_t)blockIdx.x, smem); __VA_ARGS__(k, a); }
+#define AASM_FAMILY (PackArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_PACK_KERNELS(K, KL)
+#undef AASM_FAMILY
+// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, K5 Dial) ...
+#define AASM_FAMILY (SsspArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_SSSP_KERNELS(K, KL)
+#undef AASM_FAMILY
+// ... and aasm_ksw.h (★K: a launch covers the graphs [g0, g0 + grid))
+#define AASM_FAMILY (int64_t g0, KswArgs a), g0 + (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_KSW_KERNELS(K, KL)
+#undef AASM_FAMILY
+// the cut plans of an exported result (aasm_cut_plans_device; body in aasm_cut.h)
+#define AASM_FAMILY (CutArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_CUT_KERNELS(K, KL)
+#undef AASM_FAMILY
+// the device reader (aasm_paf_parse_device; bodies in aasm_read.h)
+#define AASM_FAMILY (ReadArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_READ_KERNELS(K, KL)
+#undef AASM_FAMILY
 #undef K
 #undef KL
-#define K(id, sym, block, lanes, ...) \
-    __global__ void __launch_bounds__(block) sym(int64_t g0, KswArgs a) { AASM_KCTX(g0 + (int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
-AASM_KSW_KERNELS(K)
+
+// The rows of a table as {__global__, its name, its block size}, by id, and the launch of one: `nblocks` blocks of `nthreads`
+// threads (0: the row's own block size) on stream s; the caller reads hipGetLastError.  An id outside the table launches nothing.
+template <class... P> struct KernelSym { void (*fn)(P...); const char *name; int block; };
+#define K(id, sym, block, ...) {sym, #sym, block},
+static const KernelSym<WS> pipeline_syms[] = {AASM_PIPELINE_KERNELS(K, K)};
+static const KernelSym<PackArgs> pack_syms[] = {AASM_PACK_KERNELS(K, K)};
+static const KernelSym<SsspArgs> sssp_syms[] = {AASM_SSSP_KERNELS(K, K)};
+static const KernelSym<int64_t, KswArgs> ksw_syms[] = {AASM_KSW_KERNELS(K, K)};
+static const KernelSym<CutArgs> cut_syms[] = {AASM_CUT_KERNELS(K, K)};
+static const KernelSym<ReadArgs> read_syms[] = {AASM_READ_KERNELS(K, K)};
 #undef K
-// the cut plans of an exported result (aasm_cut_plans_device; body in aasm_cut.h)
-#define K(id, sym, block, lanes, lds, ...) \
-    __global__ void __launch_bounds__(block) sym(CutArgs a) { AASM_SMEM(lds); AASM_KCTX((int64_t)blockIdx.x, smem); __VA_ARGS__(k, a); }
-AASM_CUT_KERNELS(K)
-#undef K
-// the device reader (aasm_paf_parse_device; bodies in aasm_read.h)
-#define K(id, sym, block, lanes, ...) \
-    __global__ void __launch_bounds__(block) sym(ReadArgs a) { AASM_KCTX((int64_t)blockIdx.x, nullptr); __VA_ARGS__(k, a); }
-AASM_READ_KERNELS(K)
-#undef K
+template <size_t N, class... P> static void launch_row(const KernelSym<P...> (&rows)[N], int id, int64_t nblocks, int nthreads, hipStream_t s, const P &...args) {
+    if ((size_t)id >= N) return;
+    hipLaunchKernelGGL(rows[id].fn, dim3((unsigned)nblocks), dim3((unsigned)(nthreads ? nthreads : rows[id].block)), 0, s, args...);
+}
 
 // ---- T1 truth tables on the device (test entry aasm_debug_predicates) ------------------
 // One thread per pair (a, b) of 5-int64 PafDistance tuples {qry, ref, anom, qul_nonzero, qul_total}.
@@ -364,15 +382,6 @@ static int ctx_init(int device) {
     return AASM_OK;
 }
 
-// a pipeline kernel on stream s (the caller reads hipGetLastError)
-static void launch_kernel(int kn, int64_t nblocks, int nthreads, hipStream_t s, const WS &w) {
-    switch (kn) {
-#define K(id, sym, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, s, w); break;
-        AASM_PIPELINE_KERNELS(K, K)
-#undef K
-    }
-}
-
 struct GpuBackend {
     static constexpr bool host_emulation = false;
     DevCtx &cx;
@@ -475,24 +484,15 @@ struct GpuBackend {
     void zero(void *p, size_t n) { add_fill(p, 0, n, false); }
     void fill_byte(void *p, int v, size_t n) { add_fill(p, v, n, false); }
     void fill_ff(void *p, size_t n) { add_fill(p, 0xFF, n, false); }
-    void launch(int kn, int64_t nblocks, int nthreads, const WS &w) {
+    template <class A, size_t N> void launch_on(const KernelSym<A> (&rows)[N], int id, int64_t nblocks, int nthreads, const A &a) {
         flush_zero();
         if (fail || nblocks <= 0) return;
-        launch_kernel(kn, nblocks, nthreads, stream, w);
+        launch_row(rows, id, nblocks, nthreads, stream, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) hip_fail("kernel launch", e);
     }
-    void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) {
-        flush_zero();
-        if (fail || nblocks <= 0) return;
-        switch (kp) {
-#define K(id, sym, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, stream, a); break;
-            AASM_PACK_KERNELS(K)
-#undef K
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) hip_fail("kernel launch", e);
-    }
+    void launch(int kn, int64_t nblocks, int nthreads, const WS &w) { launch_on(pipeline_syms, kn, nblocks, nthreads, w); }
+    void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) { launch_on(pack_syms, kp, nblocks, nthreads, a); }
     template <class T> void scan_t(const T *in, int64_t n, int64_t *out) {
         flush_zero();
         if (fail) return;
@@ -608,20 +608,12 @@ struct GraphGpu {
     bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
         if (e != hipSuccess) return false;
         if (g1 <= g0) return true;
-        switch (kid) {
-#define K(id, sym, block, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)(g1 - g0)), dim3(block), 0, stream, g0, a); break;
-            AASM_KSW_KERNELS(K)
-#undef K
-        }
+        launch_row(ksw_syms, kid, g1 - g0, 0, stream, g0, a);
         return launched();
     }
     bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
         if (e != hipSuccess) return false;
-        switch (kid) {
-#define K(id, sym, block, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)n_graphs), dim3(block), 0, stream, a); break;
-            AASM_SSSP_KERNELS(K, K)
-#undef K
-        }
+        launch_row(sssp_syms, kid, n_graphs, 0, stream, a);
         return launched();
     }
     int err() {
@@ -892,11 +884,7 @@ struct CutGpu {
     hipStream_t stream;
     hipError_t err = hipSuccess;
     void launch_cut(int kc, int64_t nblocks, int nthreads, const CutArgs &a) {
-        switch (kc) {
-#define K(id, sym, ...) case id: hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, stream, a); break;
-            AASM_CUT_KERNELS(K)
-#undef K
-        }
+        launch_row(cut_syms, kc, nblocks, nthreads, stream, a);
         err = hipGetLastError();
     }
 };
@@ -978,7 +966,7 @@ int aasm_debug_sort_replay(const int64_t *rec_off, int64_t n_contigs, const int6
     w.prof_heap = (int64_t *)filled((size_t)n_contigs * 64, 0);
 #endif
     if (!m.ok) return be.err();
-    launch_kernel(KN_SORT_FIX, n_contigs, kern_block[KN_SORT_FIX], be.stream, w);
+    launch_row(pipeline_syms, KN_SORT_FIX, n_contigs, 0, be.stream, w);
     if (!be.launched() || !be.d2h(perm_out, w.perm, (size_t)R * 4)) return be.err();
 #if defined(AASM_KPROF)
     {                                                                // diagnostic build: mean cycles per section over the contigs
@@ -1168,18 +1156,13 @@ struct ReadGpu {
     void scan_u8(const uint8_t *in, int64_t n, int64_t *out) { if (ok()) scans.scan_u8(in, n, out); }
     void launch_read(int kr, int64_t nblocks, int nthreads, const ReadArgs &a) {
         if (!ok()) return;
-        const char *name = "";
         if (timing) e = hipStreamSynchronize(cx.stream);
         const auto t0 = std::chrono::steady_clock::now();
-        switch (kr) {
-#define K(id, sym, ...) case id: name = #sym; hipLaunchKernelGGL(sym, dim3((unsigned)nblocks), dim3((unsigned)nthreads), 0, cx.stream, a); break;
-            AASM_READ_KERNELS(K)
-#undef K
-        }
+        launch_row(read_syms, kr, nblocks, nthreads, cx.stream, a);
         if (e == hipSuccess) e = hipGetLastError();
         if (timing && e == hipSuccess) {
             e = hipStreamSynchronize(cx.stream);
-            std::fprintf(stderr, "aasm read kernel: %-20s %9.3f ms (%lld blocks)\n", name, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, (long long)nblocks);
+            std::fprintf(stderr, "aasm read kernel: %-20s %9.3f ms (%lld blocks)\n", (unsigned)kr < KR_N ? read_syms[kr].name : "", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, (long long)nblocks);
         }
     }
     void stage(const char *name) {

@@ -2,7 +2,7 @@
 // (k_shortest_walks.hpp:177-249) with is_dag = true, or with is_dag = false, negative_edge = false under AASM_KSW_CYCLES, and
 // kth_shortest_walk_recover() (:252-290), one workgroup per graph.
 //
-// Kernel bodies (KCtx style, so tests/host_emul_graphs compiles them for one lane on the host):
+// Kernel bodies (KCtx style, so tests/host_emul/graphs_emul.cpp compiles them for one lane on the host):
 //   kb_ksw_tree   reversed CSR in the reference's list order (:180-183), Kahn order of the reversed graph (:132-156) fused
 //                 with the DAG relaxation to the sink (:160-175; strict `>` in CALC_SUM order), the best EDGE beside best,
 //                 cycle detection, the children of every tree vertex in ascending u (:191-194), the BFS from the sink, the
@@ -512,16 +512,17 @@ static inline void ksw_free_out(aasm_ksw_out *o) {
     memset(o, 0, sizeof(*o));
 }
 
-// The k-walk kernels, one 64-lane workgroup per graph of [g0, g1): K(id, symbol, block, lanes, body) as AASM_PIPELINE_KERNELS
-// (aasm_pipeline.h); body(k, a)
-#define AASM_KSW_KERNELS(K)                         \
+// The k-walk kernels, one 64-lane workgroup per graph of [g0, g1) (row shapes: aasm_dev.h); body(k, a)
+#define AASM_KSW_KERNELS(K, ...)                    \
     K(KSW_K_TREE, aasm_ksw_tree, 64, 1, kb_ksw_tree)   \
     K(KSW_K_TREE_CYC, aasm_ksw_tree_cyc, 64, 1, kb_ksw_tree_cyc) \
     K(KSW_K_HEAP, aasm_ksw_heap, 64, 1, kb_ksw_heap)   \
     K(KSW_K_ENUM, aasm_ksw_enum, 64, 1, kb_ksw_enum)   \
     K(KSW_K_COUNT, aasm_ksw_count, 64, 1, kb_ksw_count) \
     K(KSW_K_FILL, aasm_ksw_fill, 64, 1, kb_ksw_fill)
-enum { AASM_KSW_KERNELS(AASM_ROW_ID) };
+enum { AASM_KSW_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
+constexpr int ksw_block[] = {AASM_KSW_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
+AASM_KERNEL_BODY(run_ksw_body, AASM_KSW_KERNELS, KswArgs)
 
 // Backend BE: void *alloc(size_t) (nullptr = out of memory; freed with the backend), size_t mark() / release(mark) (free what
 // was allocated since), bool h2d(dst, src, n), bool d2h(dst, src, n), bool launch_from(kernel, g0, g1, args) (blocks for the

@@ -21,10 +21,9 @@
 namespace aasm {
 
 enum Kern {
-// The pipeline's kernels, in id order: K(id, symbol, block, lanes, body) for a plain kernel, KL(id, symbol, block, lanes, LDS bytes,
-// waves, body) for one whose blocks keep a working set in LDS, with its registers budgeted for `waves` waves per SIMD (5: <= 96 VGPRs,
-// 6: <= 80): residency per CU is min(4 * waves, 160 KB / LDS bytes) blocks, and these kernels are latency-bound, so it is throughput.
-// block: the threads of every launch (and the kernel's __launch_bounds__); lanes: see aasm_dev.h; body: called as body(k, w).
+// The pipeline's kernels, in id order (row shapes: aasm_dev.h); bodies are called as body(k, w).  A KL row's registers are budgeted
+// for `waves` waves per SIMD: residency per CU is min(4 * waves, 160 KB / LDS bytes) blocks, and these kernels are latency-bound, so it
+// is throughput.
 // (The table stands inside the enum of its ids, so that the enum's text still lists every id in order for readers of this header.)
 #define AASM_PIPELINE_KERNELS(K, KL)                                                                                                  \
     K(KN_CS_RANGES, aasm_k0_cs_ranges, 256, ALL_LANES, kb_cs_ranges)                                                                  \
@@ -93,17 +92,7 @@ enum Kern {
     AASM_PIPELINE_KERNELS(AASM_ROW_ID, AASM_ROW_ID)
 };
 constexpr int kern_block[] = {AASM_PIPELINE_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
-
-// a kernel's body by id, for the host emulation and the __global__ kernels (called directly, 14 of the bodies inline into other code)
-AASM_DEV void run_kernel_body(int kn, const KCtx &k, const WS &w) {
-    switch (kn) {
-#define K(id, sym, block, lanes, ...) case id: __VA_ARGS__(k, w); break;
-#define KL(id, sym, block, lanes, lds, waves, ...) case id: __VA_ARGS__(k, w); break;
-        AASM_PIPELINE_KERNELS(K, KL)
-#undef K
-#undef KL
-    }
-}
+AASM_KERNEL_BODY(run_kernel_body, AASM_PIPELINE_KERNELS, WS)
 
 // A launch of `nblocks` blocks of the kernel's own size: backends take (kernel, blocks, threads, args), and every launch but
 // AASM_H2_LAUNCH_FAILURE's (run_pipeline) goes through here.
@@ -657,27 +646,19 @@ int fetch_results(B &be, const WS &w, const PipelineSizes &sz, aasm_batch_out *o
 
 
 // ---- device-side export (aasm_result_sizes / aasm_result_export): fetch_results' arrays built on the device ----------------
-// Backends provide alloc / zero / fill_ff / scan_i32 / read_i64s as for the pipeline, and launch_pack(kernel, blocks, threads,
-// PackArgs).
+// Backends provide alloc / zero / fill_ff / scan_i32 / read_i64s as for the pipeline, and launch_pack(kernel, blocks, threads, PackArgs).
 // The scratch is carved out of the result's workspace when the result is made (pack_alloc, behind run_pipeline);
 // sizes = count -> scan -> place -> scan -> ONE read-back, run once per result: exports in flight read that scratch, so a later
 // sizes call answers from the cached sizes and never rebuilds it; export = two launches, no read-back.
-// The pack kernels: K(id, symbol, block, lanes, body) as AASM_PIPELINE_KERNELS, body called as body(k, a).
-#define AASM_PACK_KERNELS(K)                                    \
+// The pack kernels (row shapes: aasm_dev.h), body called as body(k, a).
+#define AASM_PACK_KERNELS(K, ...)                               \
     K(KP_COUNT, aasm_pack_count, 256, ALL_LANES, kb_pack_count) \
     K(KP_PLACE, aasm_pack_place, 256, ALL_LANES, kb_pack_place) \
     K(KP_FLAT, aasm_pack_flat, 256, ALL_LANES, kb_pack_flat)    \
     K(KP_ALL, aasm_pack_all, 256, ALL_LANES, kb_pack_all)
-enum PackKern { AASM_PACK_KERNELS(AASM_ROW_ID) };
-constexpr int pack_block[] = {AASM_PACK_KERNELS(AASM_ROW_BLOCK)};
-// a pack kernel's body by id
-AASM_DEV void run_pack_body(int kp, const KCtx &k, const PackArgs &a) {
-    switch (kp) {
-#define K(id, sym, block, lanes, ...) case id: __VA_ARGS__(k, a); break;
-        AASM_PACK_KERNELS(K)
-#undef K
-    }
-}
+enum PackKern { AASM_PACK_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
+constexpr int pack_block[] = {AASM_PACK_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
+AASM_KERNEL_BODY(run_pack_body, AASM_PACK_KERNELS, PackArgs)
 template <class B> void launch(B &be, int kp, int64_t nblocks, const PackArgs &a) { be.launch_pack(kp, nblocks, pack_block[kp], a); }
 #define AASM_PACK_MAX_BLOCKS 2048   // 256-thread blocks of the copies: 8 waves per CU of the 256 (grid-stride beyond)
 

@@ -19,7 +19,7 @@
 //               name up and takes the number: chr_map's first-appearance order (alignasm.cpp:119-123).
 //   pack        tag lengths scanned into rec_cs_off, ':' counts into rec_rng_off; sixteen lanes per tag copy it into cs_text.
 // No load touches a byte outside [0, len): wide loads are taken only where their bytes are inside the text.
-// The driver (read_run) is shared by the product backend (aasm_gpu.hip) and the 1-lane host emulation (tests/host_emul_read).
+// The driver (read_run) is shared by the product backend (aasm_gpu.hip) and the 1-lane host emulation (tests/host_emul/read_emul.cpp).
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -284,9 +284,9 @@ AASM_DEV void kb_read_pack(const KCtx &k, const ReadArgs &a) {
     }
 }
 
-// The reader's kernels: K(id, symbol, block, lanes, body), body called as body(k, a).  One lane per block in the host emulation:
+// The reader's kernels (row shapes: aasm_dev.h), body called as body(k, a).  One lane per block in the host emulation:
 // every body strides by k.nthreads, and a wave is one lane there.
-#define AASM_READ_KERNELS(K) \
+#define AASM_READ_KERNELS(K, ...) \
     K(KR_COUNT, aasm_read_count, 64, 1, kb_read_count) \
     K(KR_STARTS, aasm_read_starts, 64, 1, kb_read_starts) \
     K(KR_ROWS, aasm_read_rows, 256, 1, kb_read_rows) \
@@ -295,8 +295,9 @@ AASM_DEV void kb_read_pack(const KCtx &k, const ReadArgs &a) {
     K(KR_CHR_LIST, aasm_read_chr_list, 256, 1, kb_read_chr_list) \
     K(KR_REF_IDS, aasm_read_ref_ids, 256, 1, kb_read_ref_ids) \
     K(KR_PACK, aasm_read_pack, 256, 1, kb_read_pack)
-enum ReadKern { AASM_READ_KERNELS(AASM_ROW_ID) KR_N };
-constexpr int read_block[] = {AASM_READ_KERNELS(AASM_ROW_BLOCK)};
+enum ReadKern { AASM_READ_KERNELS(AASM_ROW_ID, AASM_ROW_ID) KR_N };
+constexpr int read_block[] = {AASM_READ_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
+AASM_KERNEL_BODY(run_read_body, AASM_READ_KERNELS, ReadArgs)
 #define AASM_READ_MAX_BLOCKS 8192        // beyond 32 per CU the items are taken grid-stride
 
 // ---- driver ----------------------------------------------------------------------------------------------------------------

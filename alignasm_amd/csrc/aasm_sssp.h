@@ -1,6 +1,6 @@
 // aasm_sssp.h -- single-source shortest paths over a batch of caller graphs, and the checks of the layout that aasm_sssp_dijkstra,
 // aasm_sssp_dial and aasm_k_shortest_walks share (include/alignasm_amd.h), run on the host before a device is touched.
-// Kernel bodies in KCtx style, so tests/host_emul_graphs compiles them for one lane on the host: kb_sssp_dijkstra, the solver's
+// Kernel bodies in KCtx style, so tests/host_emul/graphs_emul.cpp compiles them for one lane on the host: kb_sssp_dijkstra, the solver's
 // dijkstra() (row ★J), and kb_sssp_dial, Dial's bucketed BFS (row K5); host drivers dijkstra_run / dial_run as ksw_run (aasm_ksw.h).
 #pragma once
 #include "aasm_dev.h"
@@ -318,12 +318,14 @@ template <class BE> struct DevMem {
     }
 };
 
-// The SSSP kernels, one 64-lane workgroup per graph: K(id, symbol, block, lanes, body) as AASM_PIPELINE_KERNELS (aasm_pipeline.h),
-// KL(id, symbol, block, lanes, LDS bytes, body) for Dial's, which keeps its buckets in LDS (no waves-per-SIMD bound); body(k, a).
+// The SSSP kernels, one 64-lane workgroup per graph (row shapes: aasm_dev.h); body(k, a).  Dial's keeps its buckets in LDS, with no
+// register budget.
 #define AASM_SSSP_KERNELS(K, KL)                                     \
     K(SSSP_K_DIJKSTRA, aasm_sssp_dijkstra_kernel, 64, 1, kb_sssp_dijkstra) \
-    KL(SSSP_K_DIAL, aasm_sssp_dial_kernel, 64, 1, sizeof(DialLds), kb_sssp_dial)
+    KL(SSSP_K_DIAL, aasm_sssp_dial_kernel, 64, 1, sizeof(DialLds), 0, kb_sssp_dial)
 enum { AASM_SSSP_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
+constexpr int sssp_block[] = {AASM_SSSP_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
+AASM_KERNEL_BODY(run_sssp_body, AASM_SSSP_KERNELS, SsspArgs)
 
 // Backend BE: ksw_run's contract (aasm_ksw.h), with bool launch(kernel, n_graphs, SsspArgs) for the SSSP kernels (one block
 // per graph of the whole batch).  why: the message of a failure the driver itself finds.

@@ -5,7 +5,8 @@ Loads the CHECKERS (never used by the product):
   oracle/_ref/libaasm_ref_algos*.so       the real reference's algorithm headers (optional;
                                           built only where /root/reference exists, the
                                           prebuilt files travel to the GPU box)
-  tests/host_emul/libaasm_emul.so         1-lane host build of the product's kernel bodies
+  tests/host_emul/libaasm_emul.so         1-lane host build of the product's kernel bodies (its other families' libraries
+                                          and sanitizer programs are built where a test asks: build_emul)
 and the PRODUCT through alignasm_amd.api (libalignasm_amd.so, C-ABI).
 """
 import ctypes as C
@@ -23,7 +24,8 @@ REF_MONO_SO = os.path.join(ROOT, "oracle", "_ref", "libaasm_ref_algos_mono.so")
 REF_CS_SO = os.path.join(ROOT, "oracle", "_ref", "libaasm_ref_cs.so")
 REF_PREFIX_SO = os.path.join(ROOT, "oracle", "_ref", "libaasm_ref_prefix.so")
 REF_PREFIX_MONO_SO = os.path.join(ROOT, "oracle", "_ref", "libaasm_ref_prefix_mono.so")
-EMUL_SO = os.path.join(ROOT, "tests", "host_emul", "libaasm_emul.so")
+EMUL_DIR = os.path.join(ROOT, "tests", "host_emul")
+EMUL_SO = os.path.join(EMUL_DIR, "libaasm_emul.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 _i64p = C.POINTER(C.c_int64)
@@ -37,6 +39,15 @@ def _ensure(path, make_dir):
     if not os.path.exists(path):
         subprocess.run(["make", "-s", "-C", make_dir], check=True)
     return path
+
+
+def build_emul(name, out_dir=EMUL_DIR, san=None):
+    """tests/host_emul's Makefile for lib<name>.so, and for the sanitizer program `san` beside it where one is named, into out_dir
+    -> the loaded library, or (library, path of the program)."""
+    targets = [os.path.join(str(out_dir), f) for f in (f"lib{name}.so", san) if f]
+    subprocess.run(["make", "-s", "-C", EMUL_DIR, f"OUT={out_dir}"] + targets, check=True)
+    lib = C.CDLL(targets[0])
+    return (lib, targets[1]) if san else lib
 
 
 _cache = {}
@@ -53,7 +64,7 @@ def oracle():
 
 def emul():
     if "e" not in _cache:
-        lib = C.CDLL(_ensure(EMUL_SO, os.path.join(ROOT, "tests", "host_emul")))
+        lib = C.CDLL(EMUL_SO) if os.path.exists(EMUL_SO) else build_emul("aasm_emul")
         lib.emul_debug_fetch.restype = C.c_int64
         lib.emul_last_bad_record.restype = C.c_int64
         lib.emul_launch_log.restype = C.c_int64

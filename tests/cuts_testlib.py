@@ -4,24 +4,22 @@ import ctypes as C
 import gzip
 import json
 import os
-import subprocess
 
 import numpy as np
 
+import aasm_testlib
 from alignasm_amd._abi import (AASM_CUT_E_EDIT, AASM_CUT_E_INS_CLIP, AASM_CUT_E_RECORD, AASM_CUT_E_TAG, AASM_CUT_ERRORS, AASM_CUT_IRREGULAR, AASM_CUT_IS_CUT, AASM_E_INVAL,
                                AASM_E_PARSE, CUT_DT, OUT_ELEM_DTYPE, BatchIn, BatchOut, DevCuts,
                                DevOut, OutSizes, render_cut)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LISTS = ("main", "alt", "all")
 
 
 def build_emul(out_dir):
-    """tests/host_emul_cuts built into out_dir -> (library, path of the sanitizer program)."""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "host_emul_cuts"), f"OUT={out_dir}"], check=True)
-    lib = C.CDLL(os.path.join(str(out_dir), "libaasm_emul_cuts.so"))
+    """tests/host_emul/cuts_emul.cpp built into out_dir -> (library, path of the sanitizer program)."""
+    lib, san = aasm_testlib.build_emul("aasm_emul_cuts", out_dir, san="cuts_emul_san")
     lib.emc_chunk.restype = C.c_int64
-    return lib, os.path.join(str(out_dir), "cuts_emul_san")
+    return lib, san
 
 
 def golden_cs(T):

@@ -1,4 +1,4 @@
-// tests/host_emul_cuts/cuts_emul.cpp -- TEST INFRASTRUCTURE ONLY.
+// tests/host_emul/cuts_emul.cpp -- TEST INFRASTRUCTURE ONLY.
 //
 // The cut-plan kernel (alignasm_amd/csrc/aasm_cut.h: kb_cut_plan, launched by cut_launch) compiled for the HOST with one lane
 // per block, so the CPU tier can check it against the recorded reference vectors and the host codec.
@@ -12,30 +12,16 @@
 #include <vector>
 
 #include "../../alignasm_amd/csrc/aasm_cut.h"
+#include "emul_launch.h"
 
 using namespace aasm;
 
 namespace {
+AASM_EMUL_ROWS(cut_rows, AASM_CUT_KERNELS);
 struct EmuCut {
-    int64_t max_blocks;
+    int64_t max_blocks;                                              // (fewer blocks than chunks: the grid-stride loop)
     void launch_cut(int kc, int64_t nblocks, int nthreads, const CutArgs &a) {
-        alignas(16) static char lds[AASM_CUT_LDS_BYTES];
-        int lanes = 0;
-        switch (kc) {
-#define K(id, sym, block, l, ...) case id: lanes = emul_lanes(nthreads, l); break;
-            AASM_CUT_KERNELS(K)
-#undef K
-        }
-        if (max_blocks > 0 && nblocks > max_blocks) nblocks = max_blocks;      // (fewer blocks than chunks: the grid-stride loop)
-        for (int64_t b = 0; b < nblocks; b++)
-            for (int t = 0; t < lanes; t++) {
-                const KCtx k{t, lanes, b, nblocks, 0, lds};
-                switch (kc) {
-#define K(id, sym, block, l, ldsb, ...) case id: __VA_ARGS__(k, a); break;
-                    AASM_CUT_KERNELS(K)
-#undef K
-                }
-            }
+        emul_launch(cut_rows, kc, nthreads, 0, nblocks, max_blocks, [&](const KCtx &k) { run_cut_body(kc, k, a); });
     }
 };
 int run(const aasm_batch_in *in, const aasm_out_sizes *sz, const aasm_dev_out *out, const aasm_dev_cuts *dst, int64_t max_blocks) {

@@ -13,21 +13,13 @@
 #include <vector>
 
 #include "../../alignasm_amd/csrc/aasm_pipeline.h"
+#include "emul_launch.h"
 
 using namespace aasm;
 
 namespace {
-alignas(16) char g_lds[65536];                    // the LDS of every emulated block
-#define K(...)
-#define KL(id, sym, block, lanes, lds, ...) static_assert((lds) <= sizeof(g_lds), #sym ": LDS beyond the emulation's buffer");
-AASM_PIPELINE_KERNELS(K, KL)
-#undef K
-#undef KL
-// a launch on the host: its blocks one after the other, in each `lanes` threads one after the other
-template <class Body> void emulate(int64_t nblocks, int lanes, Body body) {
-    for (int64_t b = 0; b < nblocks; b++)
-        for (int t = 0; t < lanes; t++) body(KCtx{t, lanes, b, nblocks, 0, g_lds});
-}
+AASM_EMUL_ROWS(pipeline_rows, AASM_PIPELINE_KERNELS);
+AASM_EMUL_ROWS(pack_rows, AASM_PACK_KERNELS);
 
 struct EmuBackend {
     static constexpr bool host_emulation = true;
@@ -53,22 +45,10 @@ struct EmuBackend {
     // nthreads: the table's block size (AASM_H2_LAUNCH_FAILURE's 4 096 is an invalid launch: logged, nothing runs)
     void launch(int kn, int64_t nblocks, int nthreads, const WS &w) {
         launches.insert(launches.end(), {kn, nblocks, nthreads});
-        int lanes = 0;
-        switch (kn) {
-#define K(id, sym, block, l, ...) case id: lanes = emul_lanes(nthreads, l); break;
-            AASM_PIPELINE_KERNELS(K, K)
-#undef K
-        }
-        if (nthreads <= 1024) emulate(nblocks, lanes, [&](const KCtx &k) { run_kernel_body(kn, k, w); });
+        if (nthreads <= 1024) emul_launch(pipeline_rows, kn, nthreads, 0, nblocks, 0, [&](const KCtx &k) { run_kernel_body(kn, k, w); });
     }
     void launch_pack(int kp, int64_t nblocks, int nthreads, const PackArgs &a) {
-        int lanes = 0;
-        switch (kp) {
-#define K(id, sym, block, l, ...) case id: lanes = emul_lanes(nthreads, l); break;
-            AASM_PACK_KERNELS(K)
-#undef K
-        }
-        emulate(nblocks, lanes, [&](const KCtx &k) { run_pack_body(kp, k, a); });
+        emul_launch(pack_rows, kp, nthreads, 0, nblocks, 0, [&](const KCtx &k) { run_pack_body(kp, k, a); });
     }
     void scan_i32(const int32_t *in, int64_t n, int64_t *out) { int64_t s = 0; for (int64_t i = 0; i < n; i++) { out[i] = s; s += in[i]; } out[n] = s; }
     void scan_i32_pair(const int32_t *a, int64_t *oa, const int32_t *b, int64_t *ob, int64_t n) { scan_i32(a, n, oa); scan_i32(b, n, ob); }

@@ -1,9 +1,9 @@
-// tests/host_emul_export/export_emul.cpp -- TEST INFRASTRUCTURE ONLY.
+// tests/host_emul/export_emul.cpp -- TEST INFRASTRUCTURE ONLY.
 //
 // The device-side export of a result (pack_sizes + pack_export, aasm_pipeline.h; kernels kb_pack_*) run by the 1-lane host
 // emulation on the workspace of an emulated solve, beside fetch_results on the same workspace: the test compares the two.
-// Reuses tests/host_emul/emul.cpp (its backend and solve) unchanged.
-#include "../host_emul/emul.cpp"
+// Reuses emul.cpp (its backend and solve) unchanged.
+#include "emul.cpp"
 
 namespace {
 PackWS g_pk;

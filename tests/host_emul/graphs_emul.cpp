@@ -1,4 +1,4 @@
-// tests/host_emul_graphs/graphs_emul.cpp -- TEST INFRASTRUCTURE ONLY.
+// tests/host_emul/graphs_emul.cpp -- TEST INFRASTRUCTURE ONLY.
 //
 // The generic graph entries - dijkstra and Dial (alignasm_amd/csrc/aasm_sssp.h), k shortest walks (aasm_ksw.h) - with the
 // product's argument checks and host drivers, compiled for the HOST: a workgroup runs as its one working lane (nthreads = 1),
@@ -10,10 +10,13 @@
 #include <vector>
 
 #include "../../alignasm_amd/csrc/aasm_ksw.h"
+#include "emul_launch.h"
 
 using namespace aasm;
 
 namespace {
+AASM_EMUL_ROWS(ksw_rows, AASM_KSW_KERNELS);
+AASM_EMUL_ROWS(sssp_rows, AASM_SSSP_KERNELS);
 struct GraphEmu {
     std::vector<void *> blocks;
     ~GraphEmu() { for (void *p : blocks) free(p); }
@@ -29,30 +32,12 @@ struct GraphEmu {
     bool h2d(void *d, const void *h, size_t n) { memcpy(d, h, n); return true; }
     bool d2h(void *h, const void *d, size_t n) { memcpy(h, d, n); return true; }
     bool sync() { return true; }
-    // the blocks of a launch one after the other, each with LDS of its own (poisoned: catches reads of never-written cells), and in
-    // each block `lanes` threads one after the other
-    template <class Body> static void emulate(int64_t g0, int64_t g1, int lanes, size_t lds_bytes, Body body) {
-        for (int64_t b = g0; b < g1; b++) {
-            std::vector<char> lds(lds_bytes, (char)0xA5);
-            for (int t = 0; t < lanes; t++) body(KCtx{t, lanes, b, g1 - g0, 0, lds_bytes ? lds.data() : nullptr});
-        }
-    }
     bool launch_from(int kid, int64_t g0, int64_t g1, const KswArgs &a) {
-        switch (kid) {
-#define K(id, sym, block, lanes, ...) case id: emulate(g0, g1, emul_lanes(block, lanes), 0, [&](const KCtx &k) { __VA_ARGS__(k, a); }); break;
-            AASM_KSW_KERNELS(K)
-#undef K
-        }
+        emul_launch(ksw_rows, kid, ksw_block[kid], g0, g1 - g0, 0, [&](const KCtx &k) { run_ksw_body(kid, k, a); });
         return true;
     }
     bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
-        switch (kid) {
-#define KL(id, sym, block, lanes, lds, ...) case id: emulate(0, n_graphs, emul_lanes(block, lanes), lds, [&](const KCtx &k) { __VA_ARGS__(k, a); }); break;
-#define K(id, sym, block, lanes, ...) KL(id, sym, block, lanes, 0, __VA_ARGS__)
-            AASM_SSSP_KERNELS(K, KL)
-#undef K
-#undef KL
-        }
+        emul_launch(sssp_rows, kid, sssp_block[kid], 0, n_graphs, 0, [&](const KCtx &k) { run_sssp_body(kid, k, a); });
         return true;
     }
     int err() { return AASM_E_NOMEM; }

@@ -1,4 +1,4 @@
-// tests/host_emul_read/read_emul.cpp -- TEST INFRASTRUCTURE ONLY.
+// tests/host_emul/read_emul.cpp -- TEST INFRASTRUCTURE ONLY.
 //
 // The device reader (alignasm_amd/csrc/aasm_read.h: the kernel bodies and their driver read_run) compiled for the HOST with one
 // lane per block, together with the host codec (aasm_paf.cpp) it shares the slow path and the container with, so the CPU tier can
@@ -14,12 +14,14 @@
 #include <vector>
 
 #include "../../alignasm_amd/csrc/aasm_read.h"
+#include "emul_launch.h"
 
 using namespace aasm;
 
 namespace {
+AASM_EMUL_ROWS(read_rows, AASM_READ_KERNELS);
 struct EmuRead {
-    int64_t max_blocks;
+    int64_t max_blocks;                                              // (fewer blocks than items: the grid-stride loops)
     std::vector<void *> blocks;
     ~EmuRead() { for (void *p : blocks) std::free(p); }
     bool ok() const { return true; }
@@ -35,22 +37,7 @@ struct EmuRead {
     void scan_u8(const uint8_t *in, int64_t n, int64_t *out) { scan(in, n, out); }
     void stage(const char *) {}
     void launch_read(int kr, int64_t nblocks, int nthreads, const ReadArgs &a) {
-        int lanes = 0;
-        switch (kr) {
-#define K(id, sym, block, l, ...) case id: lanes = emul_lanes(nthreads, l); break;
-            AASM_READ_KERNELS(K)
-#undef K
-        }
-        if (max_blocks > 0 && nblocks > max_blocks) nblocks = max_blocks;      // (fewer blocks than items: the grid-stride loops)
-        for (int64_t b = 0; b < nblocks; b++)
-            for (int t = 0; t < lanes; t++) {
-                const KCtx k{t, lanes, b, nblocks, 0, nullptr};
-                switch (kr) {
-#define K(id, sym, block, l, ...) case id: __VA_ARGS__(k, a); break;
-                    AASM_READ_KERNELS(K)
-#undef K
-                }
-            }
+        emul_launch(read_rows, kr, nthreads, 0, nblocks, max_blocks, [&](const KCtx &k) { run_read_body(kr, k, a); });
     }
 };
 struct EmuBatch { std::vector<void *> ptrs; };

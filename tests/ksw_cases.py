@@ -1,11 +1,11 @@
 """Shared pieces of the k-shortest-walks tests (tests/test_ksw_cpu.py, tests/test_gpu_ksw.py): graph batches, the host
-emulation of aasm_ksw.h (tests/host_emul_graphs), the per-graph oracle / reference, and one comparison for all of them."""
+emulation of aasm_ksw.h (tests/host_emul/graphs_emul.cpp), the per-graph oracle / reference, and one comparison for all of them."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import aasm_testlib
 from alignasm_amd._abi import AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, KswOut, ksw_inputs, unpack_ksw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,9 +15,8 @@ LIM = 1 << 39
 
 
 def build_emul(out_dir):
-    """The host emulation of the generic graph entries (tests/host_emul_graphs): emk_k_shortest_walks, emk_sssp_dijkstra, emk_sssp_dial."""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "host_emul_graphs"), f"OUT={out_dir}"], check=True)
-    lib = C.CDLL(os.path.join(str(out_dir), "libaasm_emul_graphs.so"))
+    """The host emulation of the generic graph entries (tests/host_emul/graphs_emul.cpp): emk_k_shortest_walks, emk_sssp_dijkstra, emk_sssp_dial."""
+    lib = aasm_testlib.build_emul("aasm_emul_graphs", out_dir)
     for fn in (lib.emk_k_shortest_walks, lib.emk_sssp_dijkstra, lib.emk_sssp_dial):
         fn.restype = C.c_int
     return lib

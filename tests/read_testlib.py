@@ -2,13 +2,12 @@
 numpy arrays (host or device memory), the comparisons against the host reader and the I/O oracle."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import aasm_testlib
 from alignasm_amd._abi import BatchIn, _np_from
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # name -> (dtype, length from (C, R, cs bytes)); rng_* stay NULL in the cs form
 VIEW_ARRAYS = {
     "ctg_rec_off": (np.int64, lambda c, r, t: c + 1), "qry_str": (np.int64, lambda c, r, t: r), "qry_end": (np.int64, lambda c, r, t: r),
@@ -19,9 +18,10 @@ VIEW_ARRAYS = {
 
 
 def build_emul(out_dir, san=True):
-    """tests/host_emul_read built into out_dir -> (library, path of the sanitizer program); san = False: the library alone."""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "host_emul_read"), f"OUT={out_dir}"] + ([] if san else [f"{out_dir}/libaasm_emul_read.so"]), check=True)
-    lib = C.CDLL(os.path.join(str(out_dir), "libaasm_emul_read.so"))
+    """tests/host_emul/read_emul.cpp built into out_dir -> (library, path of the sanitizer program); san = False: the library alone
+    (and None)."""
+    built = aasm_testlib.build_emul("aasm_emul_read", out_dir, san="read_emul_san" if san else None)
+    lib, prog = built if san else (built, None)
     lib.emr_parse_device.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emr_free.argtypes = [C.c_void_p]
     lib.emr_counter.restype = C.c_int64
@@ -31,7 +31,7 @@ def build_emul(out_dir, san=True):
     lib.aasm_paf_batch.argtypes = [C.c_void_p, C.c_void_p]
     lib.aasm_paf_to_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.aasm_paf_write_outputs.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
-    return lib, os.path.join(str(out_dir), "read_emul_san")
+    return lib, prog
 
 
 def host_fetch(ptr, n, dtype):

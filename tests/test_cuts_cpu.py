@@ -1,5 +1,5 @@
 """CPU tier of the cut plans (aasm_cut_plans_device / aasm_writer_append_cuts): the C-ABI surface and the ctypes mirrors, the
-kernel body (1-lane host emulation, tests/host_emul_cuts) against vectors recorded from the reference's get_edited_paf_data and
+kernel body (1-lane host emulation, tests/host_emul/cuts_emul.cpp) against vectors recorded from the reference's get_edited_paf_data and
 against the host codec on solver output, the planned writer byte for byte against the walking one, and damaged tags under a host
 address sanitizer."""
 import ctypes as C

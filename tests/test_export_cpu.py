@@ -96,11 +96,8 @@ def test_one_hip_runtime_per_process(order):
 
 # ---- the pack kernels, emulated, against fetch_results on the same workspace -------------------------------------------
 @pytest.fixture(scope="module")
-def emx(tmp_path_factory):
-    out = tmp_path_factory.mktemp("emul_export")
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "host_emul_export"), f"OUT={out}"], check=True)
-    lib = C.CDLL(str(out / "libaasm_emul_export.so"))
-    return lib
+def emx(tmp_path_factory, T):
+    return T.build_emul("aasm_emul_export", tmp_path_factory.mktemp("emul_export"))
 
 
 def _emulated_export_and_fetch(emx, T, hb, K, nsl=False, **hooks):

@@ -1,5 +1,5 @@
 """CPU tier of aasm_k_shortest_walks (row ★K): the C-ABI surface and its argument checks through the product library, and
-the kernels of alignasm_amd/csrc/aasm_ksw.h with their host driver (1-lane host emulation, tests/host_emul_graphs) against the
+the kernels of alignasm_amd/csrc/aasm_ksw.h with their host driver (1-lane host emulation, tests/host_emul/graphs_emul.cpp) against the
 real reference's numbers in ref_algos.npz and against the oracle's restatement on random DAGs."""
 import ctypes as C
 import os

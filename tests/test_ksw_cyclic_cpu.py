@@ -1,5 +1,5 @@
 """CPU tier of aasm_k_shortest_walks with AASM_KSW_CYCLES (the solver's is_dag = false): the kernels of
-alignasm_amd/csrc/aasm_ksw.h with their host driver (1-lane host emulation, tests/host_emul_graphs) against the real reference's
+alignasm_amd/csrc/aasm_ksw.h with their host driver (1-lane host emulation, tests/host_emul/graphs_emul.cpp) against the real reference's
 runs recorded in ref_ksw_cyclic.npz, against the plain-Python checker (tests/ksw_cyclic_checker.py) on random cyclic graphs, and
 against a brute force that shares nothing with the heaps; the checker itself against the reference; the guards and the surface."""
 import ctypes as C

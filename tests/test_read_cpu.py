@@ -1,5 +1,5 @@
 """CPU tier of the device reader (aasm_paf_parse_device / aasm_paf_read_device): the C-ABI surface and the ctypes signatures, the
-kernel bodies and their driver (1-lane host emulation, tests/host_emul_read) on every case of tests/read_cases.py against the
+kernel bodies and their driver (1-lane host emulation, tests/host_emul/read_emul.cpp) on every case of tests/read_cases.py against the
 I/O oracle and the host reader, the error contract, and the framing cases under a host address sanitizer."""
 import ctypes as C
 import os

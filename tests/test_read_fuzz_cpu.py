@@ -1,4 +1,4 @@
-"""Differential fuzzing of the device reader, CPU tier: the 1-lane emulation (tests/host_emul_read) against the host reader on the
+"""Differential fuzzing of the device reader, CPU tier: the 1-lane emulation (tests/host_emul/read_emul.cpp) against the host reader on the
 random texts of tests/read_fuzz.py.  For any byte string both take the text and give the same container and batch, or both refuse
 it with the same code and message; AASM_E_INTERNAL never appears.  What the corpus must contain is asserted on the host reader's
 verdicts alone, so that a change to the generator cannot turn the run into all-accepts or all-rejects unnoticed."""

@@ -1,31 +1,26 @@
 """CPU tier of the generic SSSP entries, aasm_sssp_dijkstra (row ★J) and aasm_sssp_dial (row K5): the kernels of
-alignasm_amd/csrc/aasm_sssp.h with their host drivers (1-lane host emulation, tests/host_emul_graphs) against the recorded reference
+alignasm_amd/csrc/aasm_sssp.h with their host drivers (1-lane host emulation, tests/host_emul/graphs_emul.cpp) against the recorded reference
 vectors (ref_algos.npz, ref_dial.npz) and the oracle, and the argument checks of all three graph entries through the product
 library, which run before any device is touched."""
 import ctypes as C
 import heapq
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import ksw_cases as KC
 import test_dial as TD
 import test_dijkstra as TJ
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 DIAL_WIN = 256
 
 
 @pytest.fixture(scope="module")
 def emk(tmp_path_factory):
-    """tests/host_emul_graphs, built on demand"""
-    out = tmp_path_factory.mktemp("emul_graphs")
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "host_emul_graphs"), f"OUT={out}"], check=True)
-    lib = C.CDLL(os.path.join(str(out), "libaasm_emul_graphs.so"))
-    lib.emk_sssp_dijkstra.restype = lib.emk_sssp_dial.restype = C.c_int
-    return lib
+    """tests/host_emul/graphs_emul.cpp, built on demand"""
+    return KC.build_emul(tmp_path_factory.mktemp("emul_graphs"))
 
 
 def _P(a):
