@@ -149,6 +149,25 @@ class Cuts(C.Structure):
     _fields_ = [("n_main", C.c_int64), ("n_alt", C.c_int64), ("n_all", C.c_int64), ("main", C.c_void_p), ("alt", C.c_void_p), ("all", C.c_void_p)]
 
 
+# ---- output rows on the device (aasm_rows_sizes_device / aasm_rows_format_device / aasm_writer_append_device) -------------------------
+AASM_ROWS_E_PLAN, AASM_ROWS_E_STRETCH, AASM_ROWS_H_FEW_BLOCKS = 0x100, 0x200, 0x200
+
+
+class RowCols(C.Structure):
+    """aasm_row_cols: DEVICE arrays of what an output row prints beyond BatchIn (aasm_paf_upload_rows)."""
+    _fields_ = [("n_chr", C.c_int64)] + [(n, C.c_void_p) for n in ("ref_total", "mat_num", "aln_len", "row_index", "cord_type", "names", "ctg_name_off", "chr_name_off")]
+
+
+class DevRows(C.Structure):
+    """aasm_dev_rows: caller-owned DEVICE row offsets, one more entry than DevOut's element lists."""
+    _fields_ = [(n, C.c_void_p) for n in ("main_off", "alt_off", "all_off")]
+
+
+class RowsInfo(C.Structure):
+    """aasm_rows_info: what aasm_rows_sizes_device returns."""
+    _fields_ = [("bytes", C.c_int64 * 3), ("n_flagged", C.c_int64), ("bad_elem", C.c_int64), ("bad_list", C.c_int32), ("bad_flags", C.c_int32)]
+
+
 def render_cut(plan, tag):
     """The cs tag of a row from its plan and the record's own tag (both str or both bytes); plans without AASM_CUT_IRREGULAR."""
     if not int(plan["flags"]) & AASM_CUT_IS_CUT:

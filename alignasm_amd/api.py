@@ -14,8 +14,8 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_E_INVAL, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, CUT_DT, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
-                   HostBatch, KswOut, Opts, OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
+from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, CUT_DT, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+                   DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AASM_LIB_OVERRIDE") or os.path.join(_HERE, "libalignasm_amd.so")   # override: diagnostic builds (tools/)
@@ -84,6 +84,7 @@ EXPORTED = [
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
     "aasm_paf_parse_device", "aasm_paf_read_device",
+    "aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device",
 ]
 
 
@@ -257,6 +258,27 @@ class Paf:
             raise AlignasmError(rc, msg)
         _check(rc2)
 
+    def write_outputs_device(self, db, res, main_path, alt_path, all_path, piece_bytes=0):
+        """The three output files with the rows formatted on the device (aasm_writer_append_device).  db: the DeviceBatch of this
+        container (its tags on the device); res: a DeviceResult solved from it, or the dict of its to_torch(cuts=db).  Errors as
+        write_outputs: a row that cannot be formatted raises with the host codec's code and message and leaves no file behind."""
+        d = res if isinstance(res, dict) else res.to_torch(cuts=db)
+        if "main_cut" not in d:
+            raise AlignasmError(AASM_E_INVAL, "write_outputs_device: the result dict holds no cut plans (to_torch(cuts=...))")
+        sizes, dst, dc = _dev_structs(d)
+        cols = db.row_cols()
+        w = C.c_void_p()
+        _check(LIB.aasm_writer_open(os.fsencode(main_path), os.fsencode(alt_path), os.fsencode(all_path), C.byref(w)))
+        import torch
+        torch.cuda.synchronize(db.device)                            # (the writer runs on the library's own streams)
+        rc = LIB.aasm_writer_append_device(w, self._h, C.byref(db.dev_view), C.byref(cols), C.byref(sizes), C.byref(dst), C.byref(dc), C.c_int64(0),
+                                           C.c_int64(int(piece_bytes)), int(db.device))
+        msg = (LIB.aasm_last_error() or b"").decode(errors="replace")
+        rc2 = LIB.aasm_writer_close(w, 1 if rc == AASM_OK else 0)     # (a failed append leaves no file behind)
+        if rc != AASM_OK:
+            raise AlignasmError(rc, msg)
+        _check(rc2)
+
     def close(self):
         if self._h:
             LIB.aasm_paf_free(self._h)
@@ -333,7 +355,21 @@ class DeviceBatch:
         _check(LIB.aasm_solve_device(C.byref(self.dev_view), C.byref(opts), C.c_void_p(stream or 0), C.byref(res)))
         return DeviceResult(res, self.device)
 
+    def row_cols(self) -> RowCols:
+        """What an output row prints beyond the batch (aasm_paf_upload_rows), uploaded once from the Paf the batch was made from
+        and freed with the batch."""
+        if getattr(self, "_row_cols", None) is None:
+            if not isinstance(self._keep, Paf):
+                raise AlignasmError(AASM_E_INVAL, "row_cols: the batch was not made from a Paf (names and row columns are the container's)")
+            up, cols = C.c_void_p(), RowCols()
+            _check(LIB.aasm_paf_upload_rows(self._keep._h, C.c_int64(0), C.c_int64(self.n_contigs), int(self.device), C.byref(up), C.byref(cols)))
+            self._row_up, self._row_cols = up, cols
+        return self._row_cols
+
     def close(self):
+        if getattr(self, "_row_up", None):
+            LIB.aasm_upload_free(self._row_up)
+            self._row_up = self._row_cols = None
         if self._up:
             LIB.aasm_upload_free(self._up)
             self._up = None
@@ -379,14 +415,18 @@ class DeviceResult:
         """aasm_result_export as is: returns the C-ABI code (0 = enqueued on `stream`, a hipStream_t handle or 0)."""
         return int(LIB.aasm_result_export(self._h, C.byref(sizes), C.byref(dst), C.c_void_p(stream or 0)))
 
-    def to_torch(self, stream=None, cuts=None):
+    def to_torch(self, stream=None, cuts=None, rows=False):
         """The result in torch tensors on its device, packed there (aasm_result_export): the keys of unpack_out() without
         `stats`; element lists are int64 [n, 5] tensors holding the 40-byte rows (column 4 is ctg_index / is_alt as two int32:
         `.view(torch.int32)`).  Asynchronous on `stream` (default: the device's current torch stream); the tensors outlive the
         next solve on the device.
         cuts: the DeviceBatch the result was solved from (one with cs tags on the device: a Paf read with device_ranges) - the
         dict then also holds `main_cut`, `alt_cut`, `all_cut`, int64 [n, 6] tensors of the elements' 48-byte cut plans
-        (aasm_cut_plans_device; `cuts_to_numpy`), made on the same stream right behind the export."""
+        (aasm_cut_plans_device; `cuts_to_numpy`), made on the same stream right behind the export.
+        rows (with cuts): the dict also holds the three files' text, `main_text`, `alt_text`, `all_text` (uint8), and the rows'
+        offsets in it, `main_row_off`, `alt_row_off`, `all_row_off` (int64, one more entry than rows), formatted on the same
+        stream right behind the plans (one wait for the sizes).  A result with an element that cannot be formatted raises
+        AlignasmError: AASM_E_PARSE, or AASM_E_INVAL for a record or plan fault; the message names list, element and flags."""
         import torch
         _check_one_hip_runtime()
         dev = torch.device("cuda", self.device)
@@ -416,6 +456,10 @@ class DeviceResult:
             dc = DevCuts(ptr(plans["main_cut"]), ptr(plans["alt_cut"]), ptr(plans["all_cut"]))
             _check(cut_plans_raw(cuts.dev_view, csz, dst, dc, self.device, stream.cuda_stream))
             d.update(plans)
+            if rows:
+                d.update(_rows_to_torch(cuts, csz, dst, dc, sz, dev, stream))
+        elif rows:
+            raise AlignasmError(AASM_E_INVAL, "to_torch(rows=True) needs cuts=: the DeviceBatch the result was solved from")
         d["n_contigs"] = c
         return d
 
@@ -442,6 +486,59 @@ class DeviceResult:
 def cut_plans_raw(dev_view: BatchIn, sizes: OutSizes, dev_out: DevOut, dst: DevCuts, device=0, stream=0):
     """aasm_cut_plans_device as is: returns the C-ABI code (0 = enqueued on `stream`, a hipStream_t handle or 0)."""
     return int(LIB.aasm_cut_plans_device(C.byref(dev_view), C.byref(sizes), C.byref(dev_out), C.byref(dst), int(device), C.c_void_p(stream or 0)))
+
+
+def rows_sizes_raw(dev_view: BatchIn, cols: RowCols, sizes: OutSizes, dev_out: DevOut, cuts: DevCuts, row_off: DevRows, info: RowsInfo, flags=0, device=0, stream=0):
+    """aasm_rows_sizes_device as is: returns the C-ABI code; info is filled."""
+    return int(LIB.aasm_rows_sizes_device(C.byref(dev_view), C.byref(cols), C.byref(sizes), C.byref(dev_out), C.byref(cuts), C.byref(row_off), int(flags), int(device),
+                                          C.c_void_p(stream or 0), C.byref(info)))
+
+
+def rows_format_raw(dev_view: BatchIn, cols: RowCols, sizes: OutSizes, dev_out: DevOut, cuts: DevCuts, row_off: DevRows, info: RowsInfo, lst, e0, e1, text_ptr,
+                    flags=0, device=0, stream=0):
+    """aasm_rows_format_device as is: returns the C-ABI code (0 = enqueued on `stream`)."""
+    return int(LIB.aasm_rows_format_device(C.byref(dev_view), C.byref(cols), C.byref(sizes), C.byref(dev_out), C.byref(cuts), C.byref(row_off), C.byref(info), int(lst),
+                                           C.c_int64(int(e0)), C.c_int64(int(e1)), C.c_void_p(text_ptr or 0), int(flags), int(device), C.c_void_p(stream or 0)))
+
+
+ROW_LISTS = ("main", "alt", "all")
+
+
+def rows_flagged_error(info: RowsInfo):
+    """The AlignasmError of a result whose rows cannot all be formatted."""
+    f = int(info.bad_flags)
+    code = AASM_E_PARSE if f & (AASM_CUT_ERRORS & ~AASM_CUT_E_RECORD) else AASM_E_INVAL
+    return AlignasmError(code, "%d output elements cannot be formatted; the first: list %s, element %d, flags 0x%x"
+                         % (int(info.n_flagged), ROW_LISTS[int(info.bad_list)], int(info.bad_elem), f))
+
+
+def _rows_to_torch(db, csz, dst, dc, sz, dev, stream):
+    import torch
+    ptr = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
+    n = {"main": sz["n_main"], "alt": sz["n_alt"], "all": sz["n_all_elems"]}
+    with torch.cuda.device(dev), torch.cuda.stream(stream):
+        off = {k: torch.empty(n[k] + 1, dtype=torch.int64, device=dev) for k in ROW_LISTS}
+    ro = DevRows(*(ptr(off[k]) for k in ROW_LISTS))
+    cols, info = db.row_cols(), RowsInfo()
+    _check(rows_sizes_raw(db.dev_view, cols, csz, dst, dc, ro, info, 0, db.device, stream.cuda_stream))
+    if info.n_flagged:
+        raise rows_flagged_error(info)
+    out = {}
+    for l, k in enumerate(ROW_LISTS):
+        with torch.cuda.device(dev), torch.cuda.stream(stream):
+            text = torch.empty(int(info.bytes[l]), dtype=torch.uint8, device=dev)
+        _check(rows_format_raw(db.dev_view, cols, csz, dst, dc, ro, info, l, 0, n[k], ptr(text), 0, db.device, stream.cuda_stream))
+        out[k + "_text"], out[k + "_row_off"] = text, off[k]
+    return out
+
+
+def _dev_structs(d):
+    """to_torch(cuts=...)'s dict as the C structures over its tensors."""
+    ptr = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
+    sizes = OutSizes(int(d["n_contigs"]), d["main"].shape[0], d["alt"].shape[0], d["all_elem_off"].shape[0] - 1, d["all"].shape[0])
+    dst = DevOut(ptr(d["main_off"]), ptr(d["alt_off"]), ptr(d["all_path_off"]), ptr(d["all_elem_off"]), ptr(d["main"]), ptr(d["alt"]), ptr(d["all"]), ptr(d["status"]))
+    dc = DevCuts(ptr(d["main_cut"]), ptr(d["alt_cut"]), ptr(d["all_cut"]))
+    return sizes, dst, dc
 
 
 def cuts_to_numpy(d):

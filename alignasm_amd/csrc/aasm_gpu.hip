@@ -1,7 +1,7 @@
 // aasm_gpu.hip -- gfx950 backend of the pipeline + the C-ABI entry points that touch the GPU.
 //
 // * one named __global__ per row of the kernel tables (row shapes: aasm_dev.h; tables: aasm_pipeline.h, aasm_sssp.h, aasm_ksw.h,
-//   aasm_cut.h, aasm_read.h), from ONE generator, so rocprofv3 --kernel-trace shows `aasm_k6_rev_sweep` etc., and ONE launch (launch_row);
+//   aasm_cut.h, aasm_read.h, aasm_rows.h), from ONE generator, so rocprofv3 --kernel-trace shows `aasm_k6_rev_sweep` etc., and ONE launch (launch_row);
 // * the generic graph entries (dijkstra, Dial, k shortest walks): bodies, argument checks and host drivers in aasm_sssp.h and
 //   aasm_ksw.h, run here through one backend (GraphGpu);
 // * exclusive scans (count -> offsets): ONE launch each, single pass with decoupled look-back (aasm_scan_chain);
@@ -27,6 +27,7 @@
 #include "aasm_ksw.h"
 #include "aasm_cut.h"
 #include "aasm_read.h"
+#include "aasm_rows.h"
 #include "aasm_paf.hpp"
 
 namespace aasm {
@@ -80,6 +81,10 @@ AASM_CUT_KERNELS(K, KL)
 #define AASM_FAMILY (ReadArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_READ_KERNELS(K, KL)
 #undef AASM_FAMILY
+// output rows on the device (aasm_rows_sizes_device / aasm_rows_format_device; bodies in aasm_rows.h)
+#define AASM_FAMILY (RowsArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_ROWS_KERNELS(K, KL)
+#undef AASM_FAMILY
 #undef K
 #undef KL
 
@@ -93,6 +98,7 @@ static const KernelSym<SsspArgs> sssp_syms[] = {AASM_SSSP_KERNELS(K, K)};
 static const KernelSym<int64_t, KswArgs> ksw_syms[] = {AASM_KSW_KERNELS(K, K)};
 static const KernelSym<CutArgs> cut_syms[] = {AASM_CUT_KERNELS(K, K)};
 static const KernelSym<ReadArgs> read_syms[] = {AASM_READ_KERNELS(K, K)};
+static const KernelSym<RowsArgs> rows_syms[] = {AASM_ROWS_KERNELS(K, K)};
 #undef K
 template <size_t N, class... P> static void launch_row(const KernelSym<P...> (&rows)[N], int id, int64_t nblocks, int nthreads, hipStream_t s, const P &...args) {
     if ((size_t)id >= N) return;
@@ -889,6 +895,17 @@ struct CutGpu {
     }
 };
 }
+// the arrays a cut-plan launch touches (and a rows launch, which reads the plans): device memory of `device`, aligned
+static bool cut_arrays_ok(const aasm_batch_in &in, const aasm_dev_out &o, const aasm_dev_cuts &d, const CutArgs &a, int device) {
+    const int64_t C = a.C, R = a.R;
+    return dev_buffer_ok(in.ctg_rec_off, C + 1, 8, device) && dev_buffer_ok(in.qry_str, R, 8, device) && dev_buffer_ok(in.qry_end, R, 8, device) &&
+           dev_buffer_ok(in.aln_fwd, R, 1, device) && dev_buffer_ok(in.rec_cs_off, R + 1, 8, device) &&
+           dev_buffer_ok(in.cs_text, R > 0 ? 1 : 0, 1, device) &&     // (the text's length is rec_cs_off[R], on the device: only its base is checked)
+           dev_buffer_ok(o.main_off, C + 1, 8, device) && dev_buffer_ok(o.alt_off, C + 1, 8, device) && dev_buffer_ok(o.all_path_off, C + 1, 8, device) &&
+           dev_buffer_ok(o.all_elem_off, a.NP + 1, 8, device) && dev_buffer_ok(o.main_elems, a.n[0], 8, device) &&
+           dev_buffer_ok(o.alt_elems, a.n[1], 8, device) && dev_buffer_ok(o.all_elems, a.n[2], 8, device) &&
+           dev_buffer_ok(d.main, a.n[0], 8, device) && dev_buffer_ok(d.alt, a.n[1], 8, device) && dev_buffer_ok(d.all, a.n[2], 8, device);
+}
 int aasm_cut_plans_device(const aasm_batch_in *dev_in, const aasm_out_sizes *sz, const aasm_dev_out *dev_out, const aasm_dev_cuts *dst,
                           int device, void *stream) {
     if (!dev_in || !sz || !dev_out || !dst) return AASM_E_INVAL;
@@ -898,14 +915,7 @@ int aasm_cut_plans_device(const aasm_batch_in *dev_in, const aasm_out_sizes *sz,
     int rc = ctx_init(device);
     if (rc != AASM_OK) return rc;
     hipSetDevice(device);
-    const int64_t C = a.C, R = a.R;
-    if (!dev_buffer_ok(dev_in->ctg_rec_off, C + 1, 8, device) || !dev_buffer_ok(dev_in->qry_str, R, 8, device) || !dev_buffer_ok(dev_in->qry_end, R, 8, device) ||
-        !dev_buffer_ok(dev_in->aln_fwd, R, 1, device) || !dev_buffer_ok(dev_in->rec_cs_off, R + 1, 8, device) || !dev_buffer_ok(dev_in->cs_text, R > 0 ? 1 : 0, 1, device) ||   // (the text's length is rec_cs_off[R], on the device: only its base is checked)
-       
-        !dev_buffer_ok(dev_out->main_off, C + 1, 8, device) || !dev_buffer_ok(dev_out->alt_off, C + 1, 8, device) || !dev_buffer_ok(dev_out->all_path_off, C + 1, 8, device) ||
-        !dev_buffer_ok(dev_out->all_elem_off, a.NP + 1, 8, device) || !dev_buffer_ok(dev_out->main_elems, a.n[0], 8, device) ||
-        !dev_buffer_ok(dev_out->alt_elems, a.n[1], 8, device) || !dev_buffer_ok(dev_out->all_elems, a.n[2], 8, device) ||
-        !dev_buffer_ok(dst->main, a.n[0], 8, device) || !dev_buffer_ok(dst->alt, a.n[1], 8, device) || !dev_buffer_ok(dst->all, a.n[2], 8, device)) {
+    if (!cut_arrays_ok(*dev_in, *dev_out, *dst, a, device)) {
         set_last_error("an array is NULL, not device memory of the device, or misaligned");
         return AASM_E_INVAL;
     }
@@ -1243,6 +1253,312 @@ int aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf
     ::madvise(m, (size_t)st.st_size, MADV_WILLNEED);
     const int rc = aasm_paf_parse_device((const char *)m, (int64_t)st.st_size, flags, device, paf_out, up_out, dev_view);
     ::munmap(m, (size_t)st.st_size);
+    return rc;
+}
+
+// ---- output rows on the device (aasm_rows.h) ----------------------------------------------------------------------------------
+// aasm_paf_upload_rows: plain hipMalloc memory owned by the handle, as an uploaded batch's
+int aasm_paf_upload_rows(const aasm_paf *paf, int64_t c0, int64_t c1, int device, aasm_upload **up_out, aasm_row_cols *dev_cols) {
+    if (!paf || !up_out || !dev_cols) return AASM_E_INVAL;
+    RowsHostCols h;
+    if (!rows_host_cols(*paf, c0, c1, h)) { set_last_error("aasm_paf_upload_rows: [c0, c1) is no range of the container's contigs"); return AASM_E_INVAL; }
+    int rc = ctx_init(device);
+    if (rc != AASM_OK) return rc;
+    hipSetDevice(device);
+    aasm_upload *up = new aasm_upload();
+    up->device = device;
+    std::memset(&up->view, 0, sizeof up->view);
+    hipError_t e = hipSuccess;
+    auto put = [&](const void *src, size_t bytes) -> void * {
+        void *p = nullptr;
+        if (e != hipSuccess) return nullptr;
+        if ((e = hipMalloc(&p, bytes ? bytes : 8)) != hipSuccess) return nullptr;
+        up->ptrs.push_back(p);
+        if (bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+        return p;
+    };
+    aasm_row_cols v;
+    const size_t R = h.ref_total.size();
+    v.n_chr = (int64_t)h.chr_name_off.size() - 1;
+    v.ref_total = (const int64_t *)put(h.ref_total.data(), R * 8);
+    v.mat_num = (const int32_t *)put(h.mat_num.data(), R * 4); v.aln_len = (const int32_t *)put(h.aln_len.data(), R * 4);
+    v.row_index = (const int32_t *)put(h.row_index.data(), R * 4); v.cord_type = (const uint8_t *)put(h.cord_type.data(), R);
+    v.names = (const char *)put(h.names.data(), h.names.size());
+    v.ctg_name_off = (const int64_t *)put(h.ctg_name_off.data(), h.ctg_name_off.size() * 8);
+    v.chr_name_off = (const int64_t *)put(h.chr_name_off.data(), h.chr_name_off.size() * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void *p : up->ptrs) hipFree(p);
+        delete up;
+        set_last_error(hip_err("aasm_paf_upload_rows", e));
+        return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP;
+    }
+    *dev_cols = v;
+    *up_out = up;
+    return AASM_OK;
+}
+
+namespace {
+struct RowsGpu {
+    hipStream_t stream;
+    hipError_t err = hipSuccess;
+    void launch_rows(int kw, int64_t nblocks, int nthreads, const RowsArgs &a) {
+        if (err != hipSuccess) return;
+        launch_row(rows_syms, kw, nblocks, nthreads, stream, a);
+        err = hipGetLastError();
+    }
+};
+// what the sizes calls on a device returned, by their row_off arrays: aasm_rows_format_device cannot read the device.  Under a lock
+// of its own, so that the format call never waits for a solve that holds the context's.
+struct RowsSized { const int64_t *off[3]; int64_t n[3], bytes[3], n_flagged; };
+std::vector<RowsSized> g_rows_sized[16];
+std::mutex g_rows_mu;
+int64_t *g_rows_words[16];                                           // RowsArgs::words of a device, made once
+}  // namespace
+
+// the checked arguments of a rows entry, or AASM_E_INVAL and its message
+static int rows_entry_args(const aasm_batch_in *dev_in, const aasm_row_cols *cols, const aasm_out_sizes *sz, const aasm_dev_out *dev_out,
+                           const aasm_dev_cuts *cuts, const aasm_dev_rows *ro, int device, RowsArgs &a) {
+    if (!dev_in || !cols || !sz || !dev_out || !cuts || !ro) return AASM_E_INVAL;
+    if (!dev_in->cs_text || !dev_in->rec_cs_off) { set_last_error("the device batch carries no cs text (it was uploaded with match ranges)"); return AASM_E_INVAL; }
+    if (!rows_args(*dev_in, *cols, *sz, *dev_out, *cuts, *ro, a)) { set_last_error("sizes do not fit the batch"); return AASM_E_INVAL; }
+    const int rc = ctx_init(device);
+    if (rc != AASM_OK) return rc;
+    hipSetDevice(device);
+    const int64_t C = a.c.C, R = a.c.R;
+    if (!cut_arrays_ok(*dev_in, *dev_out, *cuts, a.c, device) || !dev_buffer_ok(dev_in->qry_total, R, 8, device) || !dev_buffer_ok(dev_in->ref_chr, R, 4, device) ||
+        !dev_buffer_ok(dev_in->map_qul, R, 1, device) || !dev_buffer_ok(cols->ref_total, R, 8, device) || !dev_buffer_ok(cols->mat_num, R, 4, device) ||
+        !dev_buffer_ok(cols->aln_len, R, 4, device) || !dev_buffer_ok(cols->row_index, R, 4, device) || !dev_buffer_ok(cols->cord_type, R, 1, device) ||
+        !dev_buffer_ok(cols->names, 1, 1, device) || !dev_buffer_ok(cols->ctg_name_off, C + 1, 8, device) || !dev_buffer_ok(cols->chr_name_off, cols->n_chr + 1, 8, device) ||
+        !dev_buffer_ok(ro->main_off, a.c.n[0] + 1, 8, device) || !dev_buffer_ok(ro->alt_off, a.c.n[1] + 1, 8, device) || !dev_buffer_ok(ro->all_off, a.c.n[2] + 1, 8, device)) {
+        set_last_error("an array is NULL, not device memory of the device, or misaligned");
+        return AASM_E_INVAL;
+    }
+    return AASM_OK;
+}
+
+// under cx.mu: the length pass, the three scans (the context's single-pass scan, in place) and one read-back, on stream s
+static int rows_sizes_locked(DevCtx &cx, RowsArgs &a, int flags, int device, hipStream_t s, aasm_rows_info *info) {
+    (void)hipStreamSynchronize(cx.stream);                           // (the scans' scratch words are the context's: nothing of a solve may still use them)
+    if (!g_rows_words[device]) {
+        const hipError_t e = hipMalloc((void **)&g_rows_words[device], RW_WORDS * 8);
+        if (e != hipSuccess) { (void)hipGetLastError(); g_rows_words[device] = nullptr; set_last_error(hip_err("hipMalloc(rows)", e)); return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP; }
+    }
+    a.words = g_rows_words[device];
+    const int64_t init[RW_WORDS] = {0, AASM_ROWS_NO_KEY};
+    hipError_t e = hipMemcpyAsync(a.words, init, sizeof init, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                // (init is this frame's)
+    if (e != hipSuccess) { set_last_error(hip_err("aasm_rows_sizes_device", e)); return AASM_E_HIP; }
+    RowsGpu be{s};
+    rows_launch_len(be, a, flags);
+    if (be.err != hipSuccess) { set_last_error(hip_err("kernel launch", be.err)); return AASM_E_HIP; }
+    GpuBackend sc(cx, s, GpuBackend::Attach{});
+    for (int l = 0; l < 3; l++) sc.scan_t<int64_t>(a.row_off[l] + 1, a.c.n[l], a.row_off[l]);
+    int64_t got[5];
+    sc.read_i64s({a.words + RW_FLAGGED, a.words + RW_FIRST, a.row_off[0] + a.c.n[0], a.row_off[1] + a.c.n[1], a.row_off[2] + a.c.n[2]}, got);
+    if (sc.failed()) {
+        // a scan that did not run to its end leaves its words behind (solve_on_device does the same)
+        (void)hipDeviceSynchronize();
+        if (cx.d_scratch) (void)hipMemset(cx.d_scratch, 0, cx.d_scratch_cap * 8);
+        cx.pinned[SCAN_STALL_SLOT] = 0;
+        (void)hipGetLastError();
+        return AASM_E_HIP;
+    }
+    rows_info_of(got, *info);
+    for (int l = 0; l < 3; l++) info->bytes[l] = got[2 + l];
+    std::lock_guard<std::mutex> rlk(g_rows_mu);
+    std::vector<RowsSized> &reg = g_rows_sized[device];
+    reg.erase(std::remove_if(reg.begin(), reg.end(), [&](const RowsSized &x) { return x.off[0] == a.row_off[0] && x.off[1] == a.row_off[1] && x.off[2] == a.row_off[2]; }), reg.end());
+    if (reg.size() >= 64) reg.erase(reg.begin());
+    RowsSized x;
+    for (int l = 0; l < 3; l++) { x.off[l] = a.row_off[l]; x.n[l] = a.c.n[l]; x.bytes[l] = info->bytes[l]; }
+    x.n_flagged = info->n_flagged;
+    reg.push_back(x);
+    return AASM_OK;
+}
+
+int aasm_rows_sizes_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz, const aasm_dev_out *dev_out,
+                           const aasm_dev_cuts *cuts, const aasm_dev_rows *row_off, int flags, int device, void *stream, aasm_rows_info *info) {
+    if (!info) return AASM_E_INVAL;
+    RowsArgs a;
+    const int rc = rows_entry_args(dev_in, dev_cols, sz, dev_out, cuts, row_off, device, a);
+    if (rc != AASM_OK) return rc;
+    DevCtx &cx = g_ctx[device];
+    std::lock_guard<std::mutex> lk(cx.mu);
+    return rows_sizes_locked(cx, a, flags, device, (hipStream_t)stream, info);
+}
+
+// info against what the sizes call on these row_off arrays returned
+static bool rows_info_known(int device, const RowsArgs &a, const aasm_rows_info &info) {
+    std::lock_guard<std::mutex> rlk(g_rows_mu);
+    for (const RowsSized &x : g_rows_sized[device])
+        if (x.off[0] == a.row_off[0] && x.off[1] == a.row_off[1] && x.off[2] == a.row_off[2])
+            return x.n[0] == a.c.n[0] && x.n[1] == a.c.n[1] && x.n[2] == a.c.n[2] && x.bytes[0] == info.bytes[0] && x.bytes[1] == info.bytes[1] &&
+                   x.bytes[2] == info.bytes[2] && x.n_flagged == info.n_flagged;
+    return false;
+}
+
+int aasm_rows_format_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz, const aasm_dev_out *dev_out,
+                            const aasm_dev_cuts *cuts, const aasm_dev_rows *row_off, const aasm_rows_info *info, int list, int64_t e0, int64_t e1,
+                            char *text, int flags, int device, void *stream) {
+    if (!info) return AASM_E_INVAL;
+    RowsArgs a;
+    const int rc = rows_entry_args(dev_in, dev_cols, sz, dev_out, cuts, row_off, device, a);
+    if (rc != AASM_OK) return rc;
+    if (const char *why = rows_format_refusal(a, *info, list, e0, e1)) { set_last_error(std::string("aasm_rows_format_device: ") + why); return AASM_E_INVAL; }
+    if (!rows_info_known(device, a, *info)) { set_last_error("aasm_rows_format_device: info is not what aasm_rows_sizes_device returned for these row_off arrays"); return AASM_E_INVAL; }
+    if (e1 > e0 && !dev_buffer_ok(text, 1, 1, device)) { set_last_error("aasm_rows_format_device: text is NULL or not device memory of the device"); return AASM_E_INVAL; }
+    RowsGpu be{(hipStream_t)stream};
+    rows_launch_fill(be, a, list, e0, e1, text, flags);
+    if (be.err != hipSuccess) { set_last_error(hip_err("kernel launch", be.err)); return AASM_E_HIP; }
+    return AASM_OK;
+}
+
+// ---- aasm_writer_append_device: the three lists' rows formatted piece by piece, piece k + 1 while piece k comes back and is written ----
+namespace {
+struct RowsPiece { int list; int64_t e0, e1, b0, b1; };
+#define AASM_ROWS_SAMPLE 1024            // piece cut points are looked for among every 1024th row offset first
+// The pieces of one list: runs of rows of at most `limit` bytes (a longer row alone), cut at sampled offsets where that will do and
+// at single rows inside a block of samples that is too large.  false: a copy failed.
+bool rows_cut_pieces(const int64_t *d_off, int64_t n, int64_t total, int list, int64_t limit, std::vector<RowsPiece> &out) {
+    if (n <= 0) return true;
+    const int64_t ns = n / AASM_ROWS_SAMPLE;                         // samples 0, S, 2 S, .. ns S; then n itself
+    std::vector<int64_t> at, off((size_t)ns + 1);
+    if (hipMemcpy2D(off.data(), 8, d_off, (size_t)AASM_ROWS_SAMPLE * 8, 8, (size_t)ns + 1, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (int64_t j = 0; j <= ns; j++) at.push_back(j * AASM_ROWS_SAMPLE);
+    if (at.back() != n) { at.push_back(n); off.push_back(total); }
+    std::vector<int64_t> fine;
+    size_t cur = 0;
+    while (cur + 1 < at.size()) {
+        size_t j = cur + 1;
+        while (j + 1 < at.size() && off[j + 1] - off[cur] <= limit) j++;
+        if (off[j] - off[cur] <= limit || at[j] - at[cur] == 1) { out.push_back({list, at[cur], at[j], off[cur], off[j]}); cur = j; continue; }
+        // one block of samples beyond the limit: its rows' own offsets
+        const int64_t e0 = at[cur], m = at[j] - e0;
+        fine.resize((size_t)m + 1);
+        if (hipMemcpy(fine.data(), d_off + e0, (size_t)(m + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (int64_t x = 0; x < m; ) {
+            int64_t y = x + 1;
+            while (y < m && fine[(size_t)y + 1] - fine[(size_t)x] <= limit) y++;
+            out.push_back({list, e0 + x, e0 + y, fine[(size_t)x], fine[(size_t)y]});
+            x = y;
+        }
+        cur = j;
+    }
+    return true;
+}
+}  // namespace
+
+int aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz,
+                              const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts, int64_t contig0, int64_t piece_bytes, int device) {
+    if (!w || !paf || !sz || piece_bytes < 0) return AASM_E_INVAL;
+    int rc = writer_device_begin(w, paf, contig0, sz->n_contigs);
+    if (rc != AASM_OK) return rc;
+    RowsArgs a;
+    aasm_dev_rows ro = {nullptr, nullptr, nullptr};
+    std::vector<void *> dev_mem;
+    char *pinned_own[2] = {nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool oom = false;
+    auto dalloc = [&](size_t bytes) -> void * {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
+        if (e != hipSuccess) { (void)hipGetLastError(); oom = true; return nullptr; }
+        dev_mem.push_back(p);
+        return p;
+    };
+    auto cleanup = [&]() {
+        for (void *p : dev_mem) hipFree(p);
+        for (char *p : pinned_own) if (p) hipHostFree(p);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    };
+    if ((rc = ctx_init(device)) != AASM_OK) return rc;
+    hipSetDevice(device);
+    ro.main_off = (int64_t *)dalloc((size_t)(sz->n_main + 1) * 8); ro.alt_off = (int64_t *)dalloc((size_t)(sz->n_alt + 1) * 8); ro.all_off = (int64_t *)dalloc((size_t)(sz->n_all_elems + 1) * 8);
+    if (oom) { cleanup(); set_last_error("out of device memory (device writer)"); return AASM_E_NOMEM; }   // (nothing written: the session stays as it was)
+    if ((rc = rows_entry_args(dev_in, dev_cols, sz, dev_out, cuts, &ro, device, a)) != AASM_OK) { cleanup(); return rc; }
+    DevCtx &cx = g_ctx[device];
+    std::lock_guard<std::mutex> lk(cx.mu);
+    aasm_rows_info info;
+    if ((rc = rows_sizes_locked(cx, a, 0, device, cx.stream, &info)) != AASM_OK) { cleanup(); if (rc == AASM_E_NOMEM) return rc; writer_device_end(w, sz->n_contigs, rc); return rc; }
+    const int64_t C = a.c.C;
+    if (info.n_flagged != 0) {
+        // the first element that cannot be formatted, through the planned writer's own check: its code and message are the contract
+        const int l = info.bad_list;
+        const int64_t i = info.bad_elem;
+        aasm_out_elem el;
+        aasm_cut_plan plan;
+        std::vector<int64_t> off((size_t)C + 1), eoff;
+        hipError_t e = hipMemcpy(&el, a.c.el[l] + i, sizeof el, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&plan, a.c.dst[l] + i, sizeof plan, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(off.data(), l == 2 ? a.c.path_off : a.c.off[l], (size_t)(C + 1) * 8, hipMemcpyDeviceToHost);
+        int64_t owner = i;
+        if (e == hipSuccess && l == 2) {
+            eoff.resize((size_t)a.c.NP + 1);
+            e = hipMemcpy(eoff.data(), a.c.off[2], eoff.size() * 8, hipMemcpyDeviceToHost);
+            owner = (std::upper_bound(eoff.begin(), eoff.end(), i) - eoff.begin()) - 1;   // the element's path
+        }
+        cleanup();
+        if (e != hipSuccess) { set_last_error(hip_err("device writer", e)); rc = AASM_E_HIP; }
+        else {
+            const int64_t c = (std::upper_bound(off.begin(), off.end(), owner) - off.begin()) - 1;
+            std::string name = paf->ctg_name[(size_t)(contig0 + c)], err;
+            if (l == 2) name += "." + std::to_string((long long)(owner - off[(size_t)c] + 1));
+            rc = writer_row_verdict(paf, contig0 + c, name, el, plan, err);
+            if (rc == AASM_OK) { rc = AASM_E_INTERNAL; err = "the device refused a row the host writer formats"; }
+            set_last_error(err);
+        }
+        writer_device_end(w, sz->n_contigs, rc);
+        return rc;
+    }
+    // ---- pieces
+    const int64_t limit = piece_bytes > 0 ? piece_bytes : (int64_t)AASM_STAGE_BYTES;
+    std::vector<RowsPiece> pieces;
+    bool ok = true;
+    for (int l = 0; l < 3 && ok; l++)
+        if (writer_device_has(w, l)) ok = rows_cut_pieces(a.row_off[l], a.c.n[l], info.bytes[l], l, limit, pieces);
+    if (!ok) { (void)hipGetLastError(); cleanup(); set_last_error("device writer: reading the row offsets failed"); writer_device_end(w, sz->n_contigs, AASM_E_HIP); return AASM_E_HIP; }
+    int64_t largest = 0;
+    for (const RowsPiece &p : pieces) largest = std::max(largest, p.b1 - p.b0);
+    char *dbuf[2] = {nullptr, nullptr}, *hbuf[2] = {nullptr, nullptr};
+    if (!pieces.empty()) {
+        for (int b = 0; b < 2; b++) dbuf[b] = (char *)dalloc((size_t)largest);
+        for (int b = 0; b < 2 && !oom; b++) {
+            if (largest <= (int64_t)AASM_STAGE_BYTES) {              // the context's staging chunks (made on first use, kept)
+                if (!cx.stage[b] && hipHostMalloc((void **)&cx.stage[b], AASM_STAGE_BYTES) != hipSuccess) { (void)hipGetLastError(); cx.stage[b] = nullptr; oom = true; }
+                hbuf[b] = cx.stage[b];
+            } else {
+                if (hipHostMalloc((void **)&pinned_own[b], (size_t)largest) != hipSuccess) { (void)hipGetLastError(); pinned_own[b] = nullptr; oom = true; }
+                hbuf[b] = pinned_own[b];
+            }
+        }
+        for (int b = 0; b < 4 && !oom; b++) if (hipEventCreateWithFlags(&ev[b], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev[b] = nullptr; oom = true; }
+        if (oom) { cleanup(); set_last_error("out of memory (device writer)"); return AASM_E_NOMEM; }   // (nothing written yet)
+    }
+    hipError_t e = hipSuccess;
+    auto enqueue = [&](size_t k) {                                   // piece k: formatted on the context's stream, copied back on its side stream
+        const RowsPiece &p = pieces[k];
+        const int b = (int)(k & 1);
+        RowsGpu be{cx.stream};
+        rows_launch_fill(be, a, p.list, p.e0, p.e1, dbuf[b], 0);
+        e = be.err;
+        if (e == hipSuccess) e = hipEventRecord(ev[b], cx.stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(cx.side, ev[b], 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(hbuf[b], dbuf[b], (size_t)(p.b1 - p.b0), hipMemcpyDeviceToHost, cx.side);
+        if (e == hipSuccess) e = hipEventRecord(ev[2 + b], cx.side);
+    };
+    rc = AASM_OK;
+    if (!pieces.empty()) enqueue(0);
+    for (size_t k = 0; k < pieces.size() && e == hipSuccess && rc == AASM_OK; k++) {
+        if (k + 1 < pieces.size()) enqueue(k + 1);                   // (its buffers are those of piece k - 1, which is on disk)
+        if (e == hipSuccess) e = hipEventSynchronize(ev[2 + (k & 1)]);
+        if (e == hipSuccess) rc = writer_device_put(w, pieces[k].list, hbuf[k & 1], pieces[k].b1 - pieces[k].b0);
+    }
+    (void)hipStreamSynchronize(cx.stream);
+    (void)hipStreamSynchronize(cx.side);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_last_error(hip_err("device writer", e)); rc = AASM_E_HIP; }
+    cleanup();
+    writer_device_end(w, sz->n_contigs, rc);
     return rc;
 }
 

@@ -1144,6 +1144,33 @@ static int writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_o
     return AASM_OK;
 }
 
+// ---- the device writer's hooks (aasm_paf.hpp) ----
+namespace aasm {
+int writer_device_begin(aasm_writer *w, const aasm_paf *paf, int64_t contig0, int64_t n_contigs) {
+    if (!w || !paf || n_contigs < 0 || contig0 != w->next_contig || contig0 + n_contigs > paf->n_contigs()) return AASM_E_INVAL;
+    if (!paf->has_cs) { set_last_error("PAF was generated without cs strings"); return AASM_E_INVAL; }
+    return w->failed ? AASM_E_IO : AASM_OK;
+}
+bool writer_device_has(const aasm_writer *w, int file) { return file >= 0 && file < 3 && w->fd[file] >= 0; }
+int writer_device_put(aasm_writer *w, int file, const char *bytes, int64_t n) {
+    if (!writer_device_has(w, file)) return AASM_E_INVAL;
+    while (n > 0) {
+        const ssize_t wr = ::pwrite(w->fd[file], bytes, (size_t)std::min<int64_t>(n, 1 << 30), (off_t)w->off[file]);
+        if (wr <= 0) { set_last_error(std::string("write to ") + w->path[file] + " failed"); return AASM_E_IO; }
+        bytes += wr; n -= wr; w->off[file] += wr;
+    }
+    return AASM_OK;
+}
+void writer_device_end(aasm_writer *w, int64_t n_contigs, int rc) {
+    w->next_contig += n_contigs;
+    if (rc != AASM_OK) w->failed = true;
+}
+int writer_row_verdict(const aasm_paf *paf, int64_t contig, const std::string &name, const aasm_out_elem &o, const aasm_cut_plan &plan, std::string &err) {
+    std::string buf;
+    return emit_line(*paf, contig, name, o, &plan, buf, err);
+}
+}  // namespace aasm
+
 extern "C" {
 
 int aasm_writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, int64_t contig0) { return writer_append(w, paf, out, nullptr, contig0); }

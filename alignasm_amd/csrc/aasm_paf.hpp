@@ -63,6 +63,15 @@ int host_threads();                          // aasm_set_host_threads (0 = all h
 // the device reader's slow path (aasm_read.h): one line without its line end through the host's parse_row + record_of; false: no row
 struct ReadRowCols { int64_t qry_str, qry_end, ref_str, ref_end, qry_total, ref_total; int32_t mat_num, aln_len; uint8_t aln_fwd, map_qul; };
 bool read_slow_row(const char *s, const char *e, ReadRowCols &out);
+// The device writer's (aasm_writer_append_device, aasm_gpu.hip) way into a writer session, whose struct stays aasm_paf.cpp's:
+// begin: aasm_writer_append's argument and session checks for contigs [contig0, contig0 + n_contigs), nothing changed;
+// has: file i of the session is open;  put: append these bytes to file i of the session;  end: the range is done with rc (a
+// failure marks the session failed);  row_verdict: emit_line's code and message for one element and its plan (0: it formats).
+int writer_device_begin(aasm_writer *w, const aasm_paf *paf, int64_t contig0, int64_t n_contigs);
+bool writer_device_has(const aasm_writer *w, int file);
+int writer_device_put(aasm_writer *w, int file, const char *bytes, int64_t n);
+void writer_device_end(aasm_writer *w, int64_t n_contigs, int rc);
+int writer_row_verdict(const aasm_paf *paf, int64_t contig, const std::string &name, const aasm_out_elem &o, const aasm_cut_plan &plan, std::string &err);
 // aasm_shard.cpp: per-contig cost estimate and the contiguous cost-balanced partition built on it
 void contig_costs(const aasm_batch_in *in, double *cost);
 void partition_by_cost(const double *cost, int64_t C, int n_shards, int64_t *cuts);

@@ -7,6 +7,7 @@
 // -t sizes the host side (row-parallel PAF reader and writers; default: all hardware threads);
 // the per-contig parallelism the reference drives with it now lives on the GPU.
 // --timing prints the wall time of read / solve / write to stderr.
+// --device-writer formats the output rows on the GPU (export -> cut plans -> aasm_writer_append_device); the files are the same.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,11 +21,13 @@
 #include <iostream>
 #include <string>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../../include/alignasm_amd.h"
 
 static void usage(std::ostream &os) {
     os << "Usage: alignasm [--help] [--version] [--thread THREAD] [--alt PAF_ALT_LOC] [--alt_baseline ALT_BASELINE] "
-          "[--non_skip_linkable] [--max-paths K] [--gpus N] [--device D] [--timing] [--host-ranges] [--device-reader] PAF_LOC\n\n"
+          "[--non_skip_linkable] [--max-paths K] [--gpus N] [--device D] [--timing] [--host-ranges] [--device-reader] [--device-writer] PAF_LOC\n\n"
           "Positional arguments:\n  PAF_LOC              Location of PAF file [required]\n\n"
           "Optional arguments:\n  -h, --help           shows help message and exits\n  -v, --version        prints version information and exits\n"
           "  -t, --thread THREAD  Number of host threads for reading / writing PAF [default: all]\n"
@@ -36,7 +39,8 @@ static void usage(std::ostream &os) {
           "  --device D           first HIP device ordinal [default: 0]\n"
           "  --timing             print read / solve / write wall time to stderr\n"
           "  --host-ranges        build the cs match ranges in the reader instead of on the GPU\n"
-          "  --device-reader      frame and parse the PAF rows on the GPU (not with --host-ranges)\n";
+          "  --device-reader      frame and parse the PAF rows on the GPU (not with --host-ranges)\n"
+          "  --device-writer      format the output rows on the GPU (not with --host-ranges, not with --gpus above 1)\n";
 }
 
 int main(int argc, char **argv) {
@@ -46,7 +50,7 @@ int main(int argc, char **argv) {
     opts.max_paths = 10000;
     int gpus = 1;
     double alt_baseline = 0.5;
-    bool bad = false, use_alt = false, timing = false, host_ranges = false, device_reader = false;
+    bool bad = false, use_alt = false, timing = false, host_ranges = false, device_reader = false, device_writer = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *what) -> const char * {
@@ -59,6 +63,7 @@ int main(int argc, char **argv) {
         else if (a == "--timing") timing = true;
         else if (a == "--host-ranges") host_ranges = true;
         else if (a == "--device-reader") device_reader = true;
+        else if (a == "--device-writer") device_writer = true;
         else if (a == "-a" || a == "--alt") alt_loc = need("--alt");
         else if (a == "-b" || a == "--alt_baseline") alt_baseline = std::atof(need("--alt_baseline"));
         else if (a == "--non_skip_linkable") opts.non_skip_linkable = 1;
@@ -70,6 +75,8 @@ int main(int argc, char **argv) {
         else { std::cerr << "Maximum number of positional arguments exceeded\n"; bad = true; }
     }
     if (host_ranges && device_reader) { std::cerr << "--device-reader: not with --host-ranges\n"; bad = true; }
+    if (host_ranges && device_writer) { std::cerr << "--device-writer: not with --host-ranges\n"; bad = true; }
+    if (gpus > 1 && device_writer) { std::cerr << "--device-writer: not with --gpus above 1\n"; bad = true; }
     if (bad || paf_loc.empty()) { usage(std::cerr); return 1; }                 // alignasm.cpp:59-65
     std::filesystem::path p{paf_loc};
     if (p.extension() != ".paf") {                                              // :67-72
@@ -129,6 +136,80 @@ int main(int argc, char **argv) {
     int64_t n_internal = 0;
     clk::time_point t2 = t1;
     bool done = false;
+    if (device_writer) {
+        // ---- the batch is solved in one piece on the device - resident from --device-reader, else uploaded in its cs form from the
+        //      container (after --alt: the merged one) - and the rows are formatted there: export -> cut plans -> device writer.  Out of
+        //      device memory anywhere on the way, or a tag the device rejects: on with the paths below from the container, with their
+        //      messages and exit codes.
+        if (!up) {
+            aasm_batch_in cs_view = view;
+            cs_view.rng_qry_l = cs_view.rng_qry_r = cs_view.rng_ref_l = nullptr;
+            if (aasm_upload_batch(&cs_view, opts.device, &up, &dev_view) != AASM_OK) up = nullptr;
+        }
+        aasm_upload *up_rows = nullptr;
+        aasm_row_cols cols;
+        aasm_result *res = nullptr;
+        aasm_out_sizes sz;
+        aasm_dev_out d_out;
+        aasm_dev_cuts d_cuts;
+        std::memset(&d_out, 0, sizeof d_out); std::memset(&d_cuts, 0, sizeof d_cuts);
+        std::vector<void *> mem;
+        bool oom = false;
+        auto dalloc = [&](int64_t bytes) -> void * {
+            void *q = nullptr;
+            if (oom || hipMalloc(&q, (size_t)(bytes > 0 ? bytes : 8)) != hipSuccess) { (void)hipGetLastError(); oom = true; return nullptr; }
+            mem.push_back(q);
+            return q;
+        };
+        rc = up ? aasm_paf_upload_rows(paf, 0, view.n_contigs, opts.device, &up_rows, &cols) : AASM_E_NOMEM;
+        const auto tu = clk::now();
+        if (rc == AASM_OK) rc = aasm_solve_device(&dev_view, &opts, nullptr, &res);
+        const auto ts = clk::now();
+        if (rc == AASM_OK) rc = aasm_result_sizes(res, &sz);
+        if (rc == AASM_OK) {
+            (void)hipSetDevice(opts.device);
+            const int64_t C = sz.n_contigs;
+            d_out.main_off = (int64_t *)dalloc((C + 1) * 8); d_out.alt_off = (int64_t *)dalloc((C + 1) * 8); d_out.all_path_off = (int64_t *)dalloc((C + 1) * 8);
+            d_out.all_elem_off = (int64_t *)dalloc((sz.n_all_paths + 1) * 8); d_out.ctg_status = (int32_t *)dalloc(C * 4);
+            d_out.main_elems = (aasm_out_elem *)dalloc(sz.n_main * 40); d_out.alt_elems = (aasm_out_elem *)dalloc(sz.n_alt * 40); d_out.all_elems = (aasm_out_elem *)dalloc(sz.n_all_elems * 40);
+            d_cuts.main = (aasm_cut_plan *)dalloc(sz.n_main * 48); d_cuts.alt = (aasm_cut_plan *)dalloc(sz.n_alt * 48); d_cuts.all = (aasm_cut_plan *)dalloc(sz.n_all_elems * 48);
+            if (oom) rc = AASM_E_NOMEM;
+        }
+        if (rc == AASM_OK) rc = aasm_result_export(res, &sz, &d_out, nullptr);
+        if (rc == AASM_OK) rc = aasm_cut_plans_device(&dev_view, &sz, &d_out, &d_cuts, opts.device, nullptr);
+        aasm_stats st;
+        std::memset(&st, 0, sizeof st);
+        if (rc == AASM_OK) (void)aasm_result_stats(res, &st);
+        aasm_writer *wr = nullptr;
+        bool began = false;
+        if (rc == AASM_OK) {
+            (void)hipDeviceSynchronize();
+            t2 = clk::now();
+            upload_s = secs(t1, tu); device_s = secs(tu, ts); fetch_s = secs(ts, t2); solve_busy_s = secs(t1, t2);   // (fetch: sizes, export and plans)
+            rc = aasm_writer_open(f_main.c_str(), f_alt.c_str(), f_all.c_str(), &wr);
+            if (rc != AASM_OK) { std::cerr << "alignasm: writing outputs failed: " << aasm_last_error() << "\n"; aasm_paf_free(paf); return 3; }
+            rc = aasm_writer_append_device(wr, paf, &dev_view, &cols, &sz, &d_out, &d_cuts, 0, 0, opts.device);
+            began = rc != AASM_E_NOMEM;                                          // (out of memory: nothing was written, the session is as it was)
+            if (began) {
+                if (st.n_internal_errors) std::cerr << "alignasm: " << st.n_internal_errors << " contig(s) hit an internal error state\n";
+                std::cout << "Write output PAF file" << std::endl;                   // :487
+                const std::string msg = rc != AASM_OK ? aasm_last_error() : "";
+                const int crc = aasm_writer_close(wr, rc == AASM_OK ? 1 : 0);
+                if (rc != AASM_OK) std::cerr << "alignasm: writing outputs failed: " << msg << "\n";
+                else if ((rc = crc) != AASM_OK) std::cerr << "alignasm: writing outputs failed: " << aasm_last_error() << "\n";
+                write_busy_s = secs(t2, clk::now());
+                done = true;
+            } else (void)aasm_writer_close(wr, 0);
+        }
+        aasm_result_free(res);
+        for (void *q : mem) (void)hipFree(q);
+        aasm_upload_free(up_rows);
+        aasm_upload_free(up);
+        up = nullptr;
+        if (!done && rc != AASM_E_NOMEM && rc != AASM_E_PARSE) {
+            std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; aasm_paf_free(paf); return 2;
+        }
+    }
     if (up) {
         // ---- the resident batch is solved in place and fetched.  Out of device memory, or a tag the device rejects (a bad file is no
         //      hot path): the batch is freed and the range path below runs from the container, with its messages and exit codes.

@@ -442,6 +442,65 @@ int  aasm_writer_close(aasm_writer *w, int commit);
  * the record's tag give AASM_E_INVAL.                                                                                          */
 typedef struct aasm_cuts { int64_t n_main, n_alt, n_all; aasm_cut_plan *main, *alt, *all; } aasm_cuts;   /* HOST arrays, parallel to aasm_batch_out's element lists */
 int  aasm_writer_append_cuts(aasm_writer *w, const aasm_paf *paf, const aasm_batch_out *out, const aasm_cuts *cuts, int64_t contig0);
+/* ---- output rows on the device: from an exported result and its cut plans to the bytes of the three files --------------------------
+ * A row is what emit_line (aasm_paf.cpp) writes, byte for byte: for element o of contig c, record r = ctg_rec_off[c] + o.ctg_index,
+ *   name \t qry_total[r] \t o.qs \t o.qe+1 \t (+|-) \t chr_name[ref_chr[r]] \t ref_total[r] \t A \t B+1 \t mat \t aln \t map_qul[r]
+ *   \t tp:A:(S|P) \t xi:Z:(P_|A_)row_index[r] \t TAG \n
+ * (A, B) = (o.rs, o.re) on '+', (o.re, o.rs) on '-'; name = ctg_name[c], in .all ctg_name[c] "." (path's number in c, from 1);
+ * an element that spans its record (plan flags 0) takes the record's whole tag and its mat_num / aln_len, a cut one takes
+ * "cs:Z:" [":" head_keep] tag[keep_lo, keep_hi) [":" tail_keep] and the plan's counts; a plan with AASM_CUT_IRREGULAR is rendered
+ * on the device by the walk (every surviving ':' run as ":" + its kept bases, every other surviving operation as it stands).
+ * Use: aasm_paf_upload_rows (once per container) -> aasm_rows_sizes_device -> aasm_rows_format_device per list and range.        */
+/* DEVICE arrays: what an output row prints beyond aasm_batch_in.  names: contig names, then reference names, back to back. */
+typedef struct aasm_row_cols {
+    int64_t n_chr;
+    const int64_t *ref_total;                       /* [n_records] */
+    const int32_t *mat_num, *aln_len, *row_index;   /* [n_records] */
+    const uint8_t *cord_type;                       /* [n_records] 0 = P_, 1 = A_ */
+    const char    *names;
+    const int64_t *ctg_name_off;                    /* [n_contigs+1] into names */
+    const int64_t *chr_name_off;                    /* [n_chr+1]     into names */
+} aasm_row_cols;
+/* the row columns of contigs [c0, c1) of a container (after a --alt merge too), uploaded once; release with aasm_upload_free */
+int  aasm_paf_upload_rows(const aasm_paf *paf, int64_t c0, int64_t c1, int device, aasm_upload **up, aasm_row_cols *dev_cols);
+
+typedef struct aasm_dev_rows { int64_t *main_off, *alt_off, *all_off; } aasm_dev_rows;  /* DEVICE, caller-owned: [n_main+1], [n_alt+1], [n_all_elems+1] */
+typedef struct aasm_rows_info {
+    int64_t bytes[3];          /* text bytes of main / alt / all */
+    int64_t n_flagged;         /* elements that cannot be formatted */
+    int64_t bad_elem; int32_t bad_list, bad_flags;   /* the first of them in file order; -1 / 0 / 0 when none */
+} aasm_rows_info;
+/* bad_flags: the plan's AASM_CUT_E_* flags (AASM_CUT_E_RECORD also for a ctg_index outside the element's contig), or one of */
+#define AASM_ROWS_E_PLAN     0x100  /* the plan disagrees with its element about being cut ("cut plan does not belong to its output element") */
+#define AASM_ROWS_E_STRETCH  0x200  /* the stretch lies outside the record's tag, or a negative head / tail ("cut plan reaches outside the record's cs tag") */
+#define AASM_ROWS_H_FEW_BLOCKS 0x200  /* flags, test hook, 0 in production: every rows grid is capped at 3 blocks (grid-stride loops) */
+/* The byte length of every row and their prefix sums: row_off[l][i] = file offset of row i of list l, row_off[l][n] = bytes[l].
+ * As aasm_result_sizes NOT asynchronous: ordered behind what is already enqueued on `stream`, one small read-back and a wait.
+ * An element whose plan carries an AASM_CUT_E_* flag, whose plan disagrees with it about being cut, or whose stretch is outside
+ * its record's tag has length 0 and is counted in n_flagged; the first one in file order (main, alt, all; lowest index) is named.
+ * AASM_E_INVAL as aasm_cut_plans_device.                                                                                       */
+int  aasm_rows_sizes_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz,
+                            const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts, const aasm_dev_rows *row_off,
+                            int flags, int device, void *stream, aasm_rows_info *info);
+/* The rows [e0, e1) of list `list` (0 main, 1 alt, 2 all) into text, whose byte 0 is file offset row_off[list][e0]; it must hold
+ * row_off[list][e1] - row_off[list][e0] bytes, and no byte outside them is touched: ranges concatenate to the file.  As
+ * aasm_cut_plans_device asynchronous on `stream`: no host wait, no read-back, no allocation.  AASM_E_INVAL (nothing enqueued)
+ * when info->n_flagged != 0, when e0 > e1 or e1 > the list's elements, when info is not what aasm_rows_sizes_device returned for
+ * these row_off arrays, or when an array that is not empty is NULL, host memory, memory of another device or misaligned.    */
+int  aasm_rows_format_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz,
+                             const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts, const aasm_dev_rows *row_off,
+                             const aasm_rows_info *info, int list, int64_t e0, int64_t e1, char *text,
+                             int flags, int device, void *stream);
+
+/* aasm_writer_append with the rows formatted on the device: the three lists' text is made in pieces of at most piece_bytes
+ * (0 = default; a row longer than a piece gets a piece of its own), brought back through pinned staging and written in order,
+ * piece k + 1 being formatted while piece k is copied back and written.  dev_in .. cuts: the resident batch, the row columns of the
+ * same contigs, the exported result and its plans, all on `device`; the files are byte for byte those of aasm_writer_append for
+ * the same result, and the session rules are its own.  A result with an element that cannot be formatted writes nothing and fails
+ * the append with the code and message of aasm_writer_append_cuts on the same inputs.                                        */
+int  aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols,
+                               const aasm_out_sizes *sz, const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts,
+                               int64_t contig0, int64_t piece_bytes, int device);
 /* get_overlap_range (paf_data.cpp:90): returns #ranges or <0; arrays may be NULL      */
 int64_t aasm_cs_match_ranges(const char *cs, int64_t cs_len, int aln_fwd,
                              int64_t qry_str, int64_t qry_end, int64_t ref_str, int64_t ref_end,

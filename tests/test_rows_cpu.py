@@ -1,0 +1,295 @@
+"""CPU tier of the device rows (alignasm_amd/csrc/aasm_rows.h) on the 1-lane emulation (tests/host_emul/rows_emul.cpp): row lengths,
+offsets, digits, the irregular walk, ranges and the error contract.  One lane cannot see a fault between the lanes of the fill's
+cooperative copy; tests/test_gpu_rows.py runs the same cases on the card.  Expected bytes come from the oracle's files, the
+committed golden files, or the row layout restated in tests/rows_testlib.py - never from the code under test."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import cuts_testlib as X
+import rows_testlib as W
+import text_fuzz as F
+from alignasm_amd import _abi
+from alignasm_amd._abi import AASM_CUT_IS_CUT, CUT_DT
+
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def emw(tmp_path_factory):
+    return W.build_emul(tmp_path_factory.mktemp("emul_rows"))
+
+
+@pytest.fixture(scope="module")
+def emc(tmp_path_factory):
+    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_rows"))[0]
+
+
+def _variants():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(G, "make_golden.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m.FILE_VARIANTS
+
+
+def golden_case(T, emw, emc, variant):
+    """A golden file variant as a case: oracle solve on the host container, emulated plans on the cs-form container -> (case, files)."""
+    sub, inp, alt, _flags, K, nsl, base = variant
+    api = T.api()
+    text = open(os.path.join(G, "files", inp), "rb").read()
+    alt_text = open(os.path.join(G, "files", alt), "rb").read() if alt else None
+    want = [open(os.path.join(G, "files", sub, inp[:-4] + s), "rb").read() for s in (".aln.paf", ".aln.alt.paf", ".aln.all.paf")]
+    host, dev = api.Paf.parse(text), api.Paf.parse(text, device_ranges=True)
+    if alt_text:
+        host.merge_alt(alt_text, base); dev.merge_alt(alt_text, base)
+    view, out = host.view(), _abi.BatchOut()
+    assert T.oracle().oracle_solve_batch(C.byref(view), C.byref(_abi.Opts(K, 1 if nsl else 0, 0, 0, 0)), 1, C.byref(out)) == 0
+    sol = _abi.unpack_out(out)
+    T.oracle().oracle_free_out(C.byref(out))
+    return W.paf_case(emw[0], dev, sol, X.emul_plans(emc, dev.view(), sol)), want
+
+
+@pytest.mark.parametrize("variant", _variants(), ids=lambda v: v[0] or "default")
+def test_golden_files(T, emw, emc, variant):
+    """tiny, dense (default K, K = 4, non_skip_linkable) and the two -a cases (A_ rows, merged row_index): oracle solve -> emulated
+    plans -> emulated rows equal the committed files byte for byte, all three lists."""
+    case, want = golden_case(T, emw, emc, variant)
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == want
+    W.check_offsets(off, texts)
+    if variant[2]:
+        assert b"xi:Z:A_" in texts[0] + texts[1] + texts[2]
+
+
+def fuzz_case(T, emw, emc, text, K, nsl):
+    exp = F.expected(T, text, K, nsl)
+    dev = T.api().Paf.parse(text, device_ranges=True)
+    return exp, W.paf_case(emw[0], dev, exp.sol, X.emul_plans(emc, dev.view(), exp.sol))
+
+
+def test_text_fuzz_accepted(T, emw, emc):
+    """Shaped texts 0 - 29, both runs of each: the three files equal the oracle's, irregular plans included."""
+    irregular = 0
+    for i in range(30):
+        for K, nsl in F.RUNS:
+            exp, case = fuzz_case(T, emw, emc, F.shaped_text(i), K, nsl)
+            assert exp.kind == "ok"
+            info, off, texts = W.emul_texts(emw[0], case, max_blocks=(3 if i % 5 == 0 else 0))
+            assert texts == list(exp.files), (i, K)
+            W.check_offsets(off, texts)
+            irregular += sum(int(((case.plans[k]["flags"] & _abi.AASM_CUT_IRREGULAR) != 0).sum()) for k in W.LISTS)
+    assert irregular >= 1, "no irregular row was rendered"
+
+
+def test_text_fuzz_rejected(T, emw, emc):
+    """Unshaped texts 0 - 23: a run the oracle rejects has flagged elements, the first of them the first non-zero entry of the
+    oracle's verdict in file order, and the format call refuses; a run it accepts equals its files.  At least a quarter of the
+    runs are of either kind (counted on the oracle alone)."""
+    n = {"ok": 0, "err": 0}
+    for i in range(24):
+        for K, nsl in F.RUNS:
+            exp, case = fuzz_case(T, emw, emc, F.unshaped_text(i), K, nsl)
+            n[exp.kind] += 1
+            if exp.kind == "ok":
+                assert W.emul_texts(emw[0], case)[2] == list(exp.files), (i, K)
+                continue
+            rc, info, off = W.emul_sizes(emw[0], case)
+            first = next((l, j, v) for l, k in enumerate(W.LISTS) for j, v in enumerate(exp.verdict[k]) if v)
+            assert rc == 0 and info.n_flagged == sum(1 for k in W.LISTS for v in exp.verdict[k] if v) > 0
+            assert (info.bad_list, info.bad_elem, info.bad_flags) == first, (i, K)
+            for l, k in enumerate(W.LISTS):
+                assert W.emul_format(emw[0], case, info, off, l, 0, case.n[k])[0] == _abi.AASM_E_INVAL
+    assert n["ok"] >= 12 and n["err"] >= 12, n
+
+
+I64_EDGES = [0] + [v for k in range(1, 19) for v in (10 ** k - 1, 10 ** k)] + [1 << 40, -1, -10, -(1 << 40)]
+I32_EDGES = [0, 1, -1, 999999999, -999999999, 1000000000, -1000000000, 2 ** 31 - 1, -2 ** 31]
+
+
+def test_digit_edges(emw):
+    """Every printed int64 field through 0, 9, 10, ... 10^18, 2^40 and negatives; the int32 fields through their edges from the
+    record (uncut) and from the plan (cut); map_qul, row_index, both strands, both tp and both xi kinds."""
+    contigs, per, plans = [], [], []
+    mqs, n64, n32 = (0, 9, 10, 99, 100, 255), len(I64_EDGES), len(I32_EDGES)
+    for i in range(n64):
+        v = lambda k: I64_EDGES[(i + k) % n64]   # noqa: E731
+        w = lambda k: I32_EDGES[(i + k) % n32]   # noqa: E731
+        qe = v(2) if v(2) != v(1) else v(2) + 5                     # (qe + 1 is printed: 10^k - 1 prints 10^k)
+        rec = {"cs": W.TAG, "fwd": i % 2 == 0, "qs": v(1), "qe": qe, "qtot": v(0), "rtot": v(3), "chr": i % 2, "mat": w(0), "aln": w(1), "mq": mqs[i % 6],
+               "row_index": (0, 2 ** 31 - 1)[i % 2], "cord": (i // 2) % 2}
+        contigs.append(("d%d" % i, [rec]))
+        # main: the uncut element (the record's own mat / aln); alt: a cut one with the plan's counts, head and tail
+        per.append({"main": [(v(1), qe, v(4), v(5), 0)], "alt": [(v(1) + 1, qe, v(5), v(4), 0)]})
+        plans.append(W.cut_plan(7, 15, abs(v(6)), abs(v(7)), w(2), w(3)))
+    case = W.hand_case(contigs, ["chrA", "b"], per, {"main": np.zeros(n64, CUT_DT), "alt": np.array(plans, CUT_DT), "all": np.zeros(0, CUT_DT)})
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == W.joined_py(case)
+    W.check_offsets(off, texts)
+    both = texts[0] + texts[1]
+    for needle in (b"\t+\t", b"\t-\t", b"tp:A:P", b"tp:A:S", b"xi:Z:P_0\t", b"xi:Z:A_2147483647\t", b"\t-2147483648\t", b"\t1000000000000000000\t", b"\t-1099511627776\t", b"\t255\t"):
+        assert needle in both, needle
+
+
+def test_all_numbering(emw):
+    """.all names: a contig with 101 paths (.1 .9 .10 .99 .100 .101), contigs without paths between contigs with paths, an empty path."""
+    rec = {"cs": W.TAG, "fwd": True, "qs": 100, "qe": 134}
+    contigs = [("first", [rec]), ("none", [rec]), ("many", [rec, dict(rec, fwd=False)]), ("none2", [rec]), ("last", [rec])]
+    el = (100, 134, 7, 41, 0)
+    per = [{"all": [[el], [], [el, el]]}, {}, {"all": [[(100, 134, 7, 41, p % 2)] * (1 + p % 3) for p in range(101)]}, {}, {"all": [[], [el]]}]
+    case = W.hand_case(contigs, ["chrA"], per)
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == W.joined_py(case)
+    for suffix in (1, 9, 10, 99, 100, 101):
+        assert b"many.%d\t" % suffix in texts[2]
+    assert b"first.3\t" in texts[2] and b"first.2\t" not in texts[2] and b"last.2\t" in texts[2] and b"last.1\t" not in texts[2]
+
+
+def test_alignment(emw):
+    case = W.alignment_case()
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == W.joined_py(case)
+    assert set(int(o) % 16 for o in off["main"][:-1]) == set(range(16))
+
+
+def test_long_rows(emw):
+    case = W.long_case()
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == W.joined_py(case)
+    assert info.bytes[0] > (1 << 20) + (1 << 19)
+
+
+@pytest.mark.parametrize("n", (1, W.CHUNK - 1, W.CHUNK, W.CHUNK + 1, 2 * W.CHUNK + 1))
+def test_list_sizes(emw, n):
+    """Lists of 1, chunk - 1, chunk, chunk + 1 and 2 chunk + 1 rows, an empty alt list, contigs without elements at chunk edges;
+    the largest also with every grid capped at 3 blocks and with all three lists long."""
+    case = W.sized_case(n, 0, (n + 7) % (2 * W.CHUNK + 2))
+    want = W.joined_py(case)
+    assert W.emul_texts(emw[0], case)[2] == want and want[1] == b""
+    if n == 2 * W.CHUNK + 1:
+        big = W.sized_case(4 * W.CHUNK + 5, 3 * W.CHUNK + 1, 5 * W.CHUNK + 3)
+        assert W.emul_texts(emw[0], big, max_blocks=3)[2] == W.joined_py(big)
+
+
+def test_ranges(emw):
+    """A 40-row list at every split point: format[0, e) + format[e, n) is the whole; the empty range writes nothing."""
+    case = W.sized_case(40, 40, 40)
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == W.joined_py(case)
+    for l in range(3):
+        for e in range(41):
+            a, b = W.emul_format(emw[0], case, info, off, l, 0, e), W.emul_format(emw[0], case, info, off, l, e, 40)
+            assert a[0] == 0 and b[0] == 0 and a[1] + b[1] == texts[l], (l, e)
+        assert W.emul_format(emw[0], case, info, off, l, 17, 17) == (0, b"")
+        for e0, e1 in ((3, 2), (0, 41), (-1, 4)):
+            assert W.emul_format(emw[0], case, info, off, l, e0, e1)[0] == _abi.AASM_E_INVAL
+    assert W.emul_format(emw[0], case, info, off, 3, 0, 1)[0] == _abi.AASM_E_INVAL
+    other = _abi.RowsInfo.from_buffer_copy(info)
+    other.bytes[0] += 1                                              # not what the sizes call returned
+    assert W.emul_format(emw[0], case, other, off, 0, 0, 40)[0] == _abi.AASM_E_INVAL
+
+
+def test_offsets_above_2_31(emw):
+    """2 100 uncut elements that all name the one 1 MiB-tag record: bytes[0] > 2^31 and row_off are the prefix sums, without the
+    memory - only the last two rows are formatted, into a buffer of their 2 MiB."""
+    import read_cases as RC
+    big = "cs:Z:" + RC.long_tag(1 << 20).decode()
+    case = W.hand_case([("huge", [{"cs": big, "fwd": True, "qs": 0, "qe": 10 ** 7}])], ["chrL"], [{"main": [(0, 10 ** 7, 1, 2, 0)] * 2100}])
+    rc, info, off = W.emul_sizes(emw[0], case)
+    row = W.py_row("huge", 1000, 0, 10 ** 7, True, "chrL", 5000, 1, 2, 7, 9, 60, False, 0, 0, big)
+    assert rc == 0 and info.n_flagged == 0 and info.bytes[0] == 2100 * len(row) > 2 ** 31
+    assert np.array_equal(off["main"], np.arange(2101, dtype=np.int64) * len(row))
+    assert 2 * len(row) < (2 << 20) + 512                            # (the buffer: two rows, 2 MiB and the rows' few columns)
+    assert W.emul_format(emw[0], case, info, off, 0, 2098, 2100) == (0, row + row)
+
+
+def fault_cases():
+    """(name, flags, mutate(case, list, i)): record and plan faults an element can carry."""
+    def plan(**f):
+        def m(case, k, i):
+            for name, v in f.items():
+                case.plans[k][name][i] = v
+        return m
+
+    def ctg_index(v):
+        def m(case, k, i):
+            case.out[k]["ctg_index"][i] = v
+        return m
+    return [("ctg_index_neg", 0x80, ctg_index(-1)), ("ctg_index_count", 0x80, ctg_index(3)),
+            ("cut_on_uncut", 0x100, "uncut_says_cut"), ("uncut_on_cut", 0x100, "cut_says_uncut"),
+            ("keep_hi_beyond", 0x200, plan(keep_hi=len(W.TAG) + 1)), ("keep_lo_4", 0x200, plan(keep_lo=4)), ("negative_head", 0x200, plan(head_keep=-1)),
+            ("plan_edit_error", 0x40, plan(flags=AASM_CUT_IS_CUT | 0x40))]
+
+
+@pytest.mark.parametrize("name,flag,mutate", fault_cases(), ids=[f[0] for f in fault_cases()])
+def test_record_and_plan_faults(emw, name, flag, mutate):
+    """Each fault as the first and as the last element of a chunk (of the fill's and of the length pass's): flagged, named as the
+    first one in file order, its neighbours' lengths untouched, and never formatted."""
+    n = W.LEN_CHUNK + W.CHUNK + 1
+    good = W.sized_case(n, n, n)
+    rc, info0, off0 = W.emul_sizes(emw[0], good)
+    assert rc == 0 and info0.n_flagged == 0
+    len0 = {k: np.diff(off0[k]) for k in W.LISTS}
+    for where in (0, W.CHUNK - 1, W.CHUNK, W.LEN_CHUNK - 1, W.LEN_CHUNK, n - 1):
+        for l, k in enumerate(W.LISTS):
+            case = W.sized_case(n, n, n)
+            cut = (case.plans[k]["flags"] & AASM_CUT_IS_CUT) != 0
+            i = where
+            if mutate == "uncut_says_cut":
+                i = where if not cut[where] else (where + 1 if where + 1 < n else where - 1)
+                case.plans[k]["flags"][i] = AASM_CUT_IS_CUT
+            elif mutate == "cut_says_uncut":
+                i = int(np.flatnonzero(cut)[np.abs(np.flatnonzero(cut) - where).argmin()])
+                case.plans[k][i] = np.zeros(1, CUT_DT)[0]
+            elif flag in (0x200, 0x40):                             # (a stretch fault needs a cut, regular plan)
+                i = int(np.flatnonzero(cut)[np.abs(np.flatnonzero(cut) - where).argmin()])
+                mutate(case, k, i)
+            else:
+                mutate(case, k, i)
+            rc, info, off = W.emul_sizes(emw[0], case)
+            assert rc == 0 and info.n_flagged == 1 and (info.bad_list, info.bad_elem, info.bad_flags) == (l, i, flag), (name, k, where, info.bad_list, info.bad_elem, hex(info.bad_flags))
+            want = {kk: len0[kk].copy() for kk in W.LISTS}
+            want[k][i] = 0
+            assert all(np.array_equal(np.diff(off[kk]), want[kk]) for kk in W.LISTS)
+            assert W.emul_format(emw[0], case, info, off, l, 0, n)[0] == _abi.AASM_E_INVAL
+            clean = _abi.RowsInfo.from_buffer_copy(info)             # a caller that hides the count: the chunk with the fault is not written
+            clean.n_flagged = 0
+            rc, t = W.emul_format(emw[0], case, clean, off, l, 0, n)
+            lo, hi = int(off[k][i - i % W.CHUNK]), int(off[k][min(n, i - i % W.CHUNK + W.CHUNK)])
+            assert rc == 0 and t[lo:hi] == b"\xee" * (hi - lo)
+
+
+def test_sanitizer_program(T, emw, emc, tmp_path):
+    """rows_emul_san (host address + undefined sanitizers; every tag in a block that ends with it, every list's text in a block of
+    exactly its bytes) on the shaped corpus, the alignment case and the long rows: exit 0 and the expected bytes."""
+    lib, san = emw
+    for i in range(0, 30, 3):
+        K, nsl = F.RUNS[i % 2]
+        exp, case = fuzz_case(T, emw, emc, F.shaped_text(i), K, nsl)
+        assert W.run_san(san, case, tmp_path, "shaped%d" % i) == b"".join(exp.files), i
+    for name, case in (("align", W.alignment_case()), ("long", W.long_case()), ("sized", W.sized_case(2 * W.CHUNK + 1, 5, W.CHUNK + 3))):
+        assert W.run_san(san, case, tmp_path, name) == b"".join(W.joined_py(case)), name
+
+
+def test_cli_refuses_device_writer_with_host_ranges_or_several_gpus(T, tmp_path):
+    """--device-writer needs the tags on one device: a usage error (exit 1, nothing read) with --host-ranges and with --gpus 2."""
+    import subprocess
+    exe = os.path.join(T.ROOT, "alignasm_amd", "alignasm")
+    for extra, text in ((["--host-ranges"], "--device-writer: not with --host-ranges"), (["--gpus", "2"], "--device-writer: not with --gpus above 1")):
+        r = subprocess.run([exe, str(tmp_path / "none.paf"), "--device-writer"] + extra, capture_output=True, text=True)
+        assert r.returncode == 1 and text in r.stderr and "Usage: alignasm" in r.stderr, (extra, r.stderr)
+    assert "--device-writer" in subprocess.run([exe, "--help"], capture_output=True, text=True).stdout
+
+
+def test_the_entries_exist_and_the_structs_have_the_header_layout(T):
+    """What fails first without the feature: the C-ABI entries, the emulation sources and the ctypes layouts."""
+    api = T.api()
+    for name in ("aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device"):
+        assert hasattr(api.LIB, name) and name in api.EXPORTED
+    assert C.sizeof(_abi.RowCols) == 72 and C.sizeof(_abi.DevRows) == 24 and C.sizeof(_abi.RowsInfo) == 48
+    assert api.LIB.aasm_abi_version() == 3
+    null = C.c_void_p()
+    assert api.LIB.aasm_rows_sizes_device(null, null, null, null, null, null, 0, 0, null, null) == _abi.AASM_E_INVAL
+    assert api.LIB.aasm_writer_append_device(null, null, null, null, null, null, null, C.c_int64(0), C.c_int64(0), 0) == _abi.AASM_E_INVAL

@@ -11,6 +11,7 @@ ap.add_argument("--k", type=int, default=4); ap.add_argument("--seed", type=int,
 ap.add_argument("--dir", default="/tmp/aasm_e2e"); ap.add_argument("--threads", default="0", help="host threads (-t); a comma list runs the command once per value")
 ap.add_argument("--quiet", type=int, default=0, help="1: only the timing line of each run")
 ap.add_argument("--device-reader", action="store_true", help="pass --device-reader: the rows are framed and parsed on the GPU (its stages: AASM_READ_TIMING)")
+ap.add_argument("--device-writer", action="store_true", help="pass --device-writer: the output rows are formatted on the GPU")
 a = ap.parse_args()
 os.makedirs(a.dir, exist_ok=True)
 path = os.path.join(a.dir, "synth.paf")
@@ -26,6 +27,8 @@ for thr in [int(x) for x in str(a.threads).split(",")]:
         cmd += ["-t", str(thr)]
     if a.device_reader:
         cmd += ["--device-reader"]
+    if a.device_writer:
+        cmd += ["--device-writer"]
     for rep in range(2):                   # second run: file in the page cache, GPU context warm-up is per process
         for o in outs:                     # to NEW files (replacing a 3 GB file frees its page cache inside rename())
             if os.path.exists(o): os.remove(o)
