@@ -1416,37 +1416,14 @@ int aasm_rows_format_device(const aasm_batch_in *dev_in, const aasm_row_cols *de
 
 // ---- aasm_writer_append_device: the three lists' rows formatted piece by piece, piece k + 1 while piece k comes back and is written ----
 namespace {
-struct RowsPiece { int list; int64_t e0, e1, b0, b1; };
-#define AASM_ROWS_SAMPLE 1024            // piece cut points are looked for among every 1024th row offset first
-// The pieces of one list: runs of rows of at most `limit` bytes (a longer row alone), cut at sampled offsets where that will do and
-// at single rows inside a block of samples that is too large.  false: a copy failed.
-bool rows_cut_pieces(const int64_t *d_off, int64_t n, int64_t total, int list, int64_t limit, std::vector<RowsPiece> &out) {
-    if (n <= 0) return true;
-    const int64_t ns = n / AASM_ROWS_SAMPLE;                         // samples 0, S, 2 S, .. ns S; then n itself
-    std::vector<int64_t> at, off((size_t)ns + 1);
-    if (hipMemcpy2D(off.data(), 8, d_off, (size_t)AASM_ROWS_SAMPLE * 8, 8, (size_t)ns + 1, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    for (int64_t j = 0; j <= ns; j++) at.push_back(j * AASM_ROWS_SAMPLE);
-    if (at.back() != n) { at.push_back(n); off.push_back(total); }
-    std::vector<int64_t> fine;
-    size_t cur = 0;
-    while (cur + 1 < at.size()) {
-        size_t j = cur + 1;
-        while (j + 1 < at.size() && off[j + 1] - off[cur] <= limit) j++;
-        if (off[j] - off[cur] <= limit || at[j] - at[cur] == 1) { out.push_back({list, at[cur], at[j], off[cur], off[j]}); cur = j; continue; }
-        // one block of samples beyond the limit: its rows' own offsets
-        const int64_t e0 = at[cur], m = at[j] - e0;
-        fine.resize((size_t)m + 1);
-        if (hipMemcpy(fine.data(), d_off + e0, (size_t)(m + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return false;
-        for (int64_t x = 0; x < m; ) {
-            int64_t y = x + 1;
-            while (y < m && fine[(size_t)y + 1] - fine[(size_t)x] <= limit) y++;
-            out.push_back({list, e0 + x, e0 + y, fine[(size_t)x], fine[(size_t)y]});
-            x = y;
-        }
-        cur = j;
+// rows_cut_pieces' fetch (aasm_rows.h) over a device array: the sampled offsets by one strided copy, a block's own by a plain one
+struct RowsOffFetch {
+    const int64_t *d_off;
+    bool operator()(int64_t first, int64_t stride, int64_t count, int64_t *dst) const {
+        if (stride == 1) return hipMemcpy(dst, d_off + first, (size_t)count * 8, hipMemcpyDeviceToHost) == hipSuccess;
+        return hipMemcpy2D(dst, 8, d_off + first, (size_t)stride * 8, 8, (size_t)count, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    return true;
-}
+};
 }  // namespace
 
 int aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz,
@@ -1516,7 +1493,7 @@ int aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_ba
     std::vector<RowsPiece> pieces;
     bool ok = true;
     for (int l = 0; l < 3 && ok; l++)
-        if (writer_device_has(w, l)) ok = rows_cut_pieces(a.row_off[l], a.c.n[l], info.bytes[l], l, limit, pieces);
+        if (writer_device_has(w, l)) ok = rows_cut_pieces(RowsOffFetch{a.row_off[l]}, a.c.n[l], info.bytes[l], l, limit, pieces);
     if (!ok) { (void)hipGetLastError(); cleanup(); set_last_error("device writer: reading the row offsets failed"); writer_device_end(w, sz->n_contigs, AASM_E_HIP); return AASM_E_HIP; }
     int64_t largest = 0;
     for (const RowsPiece &p : pieces) largest = std::max(largest, p.b1 - p.b0);

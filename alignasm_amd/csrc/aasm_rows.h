@@ -413,6 +413,40 @@ static inline const char *rows_format_refusal(const RowsArgs &a, const aasm_rows
     return nullptr;
 }
 
+// ---- aasm_writer_append_device's pieces ------------------------------------------------------------------------------------------
+struct RowsPiece { int list; int64_t e0, e1, b0, b1; };              // rows [e0, e1) of a list, bytes [b0, b1) of its text
+#define AASM_ROWS_SAMPLE 1024            // piece cut points are looked for among every 1024th row offset first
+// The pieces of one list of n rows and `total` bytes: runs of rows of at most `limit` bytes (a longer row alone), cut at sampled
+// offsets where that will do and at single rows inside a block of samples that is too large.  fetch(first, stride, count, dst)
+// reads row_off[first + k * stride], k < count, into dst (the product: copies from the device); false: a fetch failed.
+template <class F> bool rows_cut_pieces(F &&fetch, int64_t n, int64_t total, int list, int64_t limit, std::vector<RowsPiece> &out) {
+    if (n <= 0) return true;
+    const int64_t ns = n / AASM_ROWS_SAMPLE;                         // samples 0, S, 2 S, .. ns S; then n itself
+    std::vector<int64_t> at, off((size_t)ns + 1);
+    if (!fetch((int64_t)0, (int64_t)AASM_ROWS_SAMPLE, ns + 1, off.data())) return false;
+    for (int64_t j = 0; j <= ns; j++) at.push_back(j * AASM_ROWS_SAMPLE);
+    if (at.back() != n) { at.push_back(n); off.push_back(total); }
+    std::vector<int64_t> fine;
+    size_t cur = 0;
+    while (cur + 1 < at.size()) {
+        size_t j = cur + 1;
+        while (j + 1 < at.size() && off[j + 1] - off[cur] <= limit) j++;
+        if (off[j] - off[cur] <= limit || at[j] - at[cur] == 1) { out.push_back({list, at[cur], at[j], off[cur], off[j]}); cur = j; continue; }
+        // one block of samples beyond the limit: its rows' own offsets
+        const int64_t e0 = at[cur], m = at[j] - e0;
+        fine.resize((size_t)m + 1);
+        if (!fetch(e0, (int64_t)1, m + 1, fine.data())) return false;
+        for (int64_t x = 0; x < m; ) {
+            int64_t y = x + 1;
+            while (y < m && fine[(size_t)y + 1] - fine[(size_t)x] <= limit) y++;
+            out.push_back({list, e0 + x, e0 + y, fine[(size_t)x], fine[(size_t)y]});
+            x = y;
+        }
+        cur = j;
+    }
+    return true;
+}
+
 // What an output row prints beyond aasm_batch_in, for contigs [c0, c1) of a container, as host arrays in aasm_row_cols' layout
 struct RowsHostCols {
     std::vector<int64_t> ref_total, ctg_name_off, chr_name_off;

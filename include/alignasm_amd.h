@@ -486,7 +486,12 @@ int  aasm_rows_sizes_device(const aasm_batch_in *dev_in, const aasm_row_cols *de
  * row_off[list][e1] - row_off[list][e0] bytes, and no byte outside them is touched: ranges concatenate to the file.  As
  * aasm_cut_plans_device asynchronous on `stream`: no host wait, no read-back, no allocation.  AASM_E_INVAL (nothing enqueued)
  * when info->n_flagged != 0, when e0 > e1 or e1 > the list's elements, when info is not what aasm_rows_sizes_device returned for
- * these row_off arrays, or when an array that is not empty is NULL, host memory, memory of another device or misaligned.    */
+ * these row_off arrays, or when an array that is not empty is NULL, host memory, memory of another device or misaligned.
+ * The library remembers the 64 most recent sizes calls per device, by their three row_off arrays: a later sizes call on the same
+ * three arrays replaces the earlier one (whose info is refused from then on), and the info of a call that 64 calls on other
+ * arrays have followed is refused too ("info is not what aasm_rows_sizes_device returned for these row_off arrays"); calling
+ * aasm_rows_sizes_device again makes it valid.  A caller that keeps more than 64 sized results per device re-sizes before it
+ * formats.                                                                                                                     */
 int  aasm_rows_format_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz,
                              const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts, const aasm_dev_rows *row_off,
                              const aasm_rows_info *info, int list, int64_t e0, int64_t e1, char *text,

@@ -5,7 +5,8 @@
 // the error contract against the oracle's files and the host writers.  One lane cannot see a fault between the lanes of the
 // cooperative copy: that is the GPU tier's.
 //  * libaasm_emul_rows.so: emw_rows_sizes() / emw_rows_format(), the entries' argument order with host arrays, and
-//    emw_row_cols(): the row columns of a container as host arrays.
+//    emw_row_cols(): the row columns of a container as host arrays; emw_cut_pieces(): the device writer's piece cutter
+//    (rows_cut_pieces) over a host array, with a record of what it fetched.
 //  * rows_emul_san: the same bodies in a program built with the host address sanitizer, which formats every list into a heap
 //    block of exactly its bytes and reads every record's tag from a private block that ends where the tag ends.
 #define AASM_HOST_EMUL 1
@@ -87,6 +88,32 @@ int emw_row_cols(const aasm_paf *paf, int64_t c0, int64_t c1, emw_cols **keep, a
     return AASM_OK;
 }
 void emw_row_cols_free(emw_cols *k) { delete k; }
+// rows_cut_pieces (aasm_writer_append_device's pieces) over a host array of n + 1 offsets: the pieces as {list, e0, e1, b0, b1}
+// into out[5 * cap] -> their number, -1: more than cap.  The fetches of the last call stay behind for emw_cut_fetches.
+static std::vector<int64_t> g_fetches;                               // {first, stride, count} per fetch
+int64_t emw_cut_pieces(const int64_t *off, int64_t n, int64_t total, int list, int64_t limit, int64_t *out, int64_t cap) {
+    g_fetches.clear();
+    std::vector<RowsPiece> pieces;
+    auto fetch = [&](int64_t first, int64_t stride, int64_t count, int64_t *dst) {
+        g_fetches.insert(g_fetches.end(), {first, stride, count});
+        for (int64_t k = 0; k < count; k++) dst[k] = off[first + k * stride];
+        return true;
+    };
+    if (!rows_cut_pieces(fetch, n, total, list, limit, pieces)) return -2;
+    if ((int64_t)pieces.size() > cap) return -1;
+    for (size_t k = 0; k < pieces.size(); k++) {
+        const RowsPiece &p = pieces[k];
+        const int64_t v[5] = {p.list, p.e0, p.e1, p.b0, p.b1};
+        std::memcpy(out + 5 * k, v, sizeof v);
+    }
+    return (int64_t)pieces.size();
+}
+int64_t emw_cut_fetches(int64_t *out, int64_t cap) {                 // -> the fetches of the last emw_cut_pieces call, 3 words each
+    const int64_t m = (int64_t)g_fetches.size() / 3;
+    for (int64_t k = 0; k < m && k < cap; k++) std::memcpy(out + 3 * k, g_fetches.data() + 3 * k, 24);
+    return m;
+}
+int64_t emw_sample(void) { return AASM_ROWS_SAMPLE; }
 }
 
 #if defined(AASM_ROWS_SAN_MAIN)

@@ -2,10 +2,13 @@
 the row layout restated in Python, and the same case on host arrays (emulation) or device tensors (the product's entries).
 
 A case is a Case: the batch's arrays and the row columns as numpy arrays, a result in unpack_out()'s form and its cut plans.
-Expected bytes never come from the code under test: the oracle's files, the host writers, or py_row() below."""
+Expected bytes never come from the code under test: the oracle's files, the host writers, or py_row() below with - for a tag
+that is not a stretch of the record's own (AASM_CUT_IRREGULAR) - the I/O oracle's re-cut tag (oracle/paf_io_oracle.py)."""
 import ctypes as C
 import os
+import re
 import subprocess
+import types
 
 import numpy as np
 
@@ -18,6 +21,7 @@ LISTS = X.LISTS
 EMUL_DIR = aasm_testlib.EMUL_DIR
 CHUNK = 128                                                          # AASM_ROWS_CHUNK (the emulation library reports it: emw_chunk)
 LEN_CHUNK = 2048                                                     # the length pass's chunk (emw_len_chunk)
+SAMPLE = 1024                                                        # AASM_ROWS_SAMPLE: the device writer's sampled row offsets (emw_sample)
 IN_KEYS = (("ctg_rec_off", np.int64), ("qry_str", np.int64), ("qry_end", np.int64), ("qry_total", np.int64), ("ref_chr", np.int32), ("aln_fwd", np.uint8),
            ("map_qul", np.uint8), ("rec_cs_off", np.int64), ("cs_text", np.uint8))
 COL_KEYS = (("ref_total", np.int64), ("mat_num", np.int32), ("aln_len", np.int32), ("row_index", np.int32), ("cord_type", np.uint8), ("names", np.uint8),
@@ -30,7 +34,8 @@ def build_emul(out_dir, san=True):
     subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "rows.mk", f"OUT={out_dir}"] + targets, check=True)
     lib = C.CDLL(targets[0])
     lib.emw_chunk.restype = lib.emw_len_chunk.restype = C.c_int64
-    assert lib.emw_chunk() == CHUNK and lib.emw_len_chunk() == LEN_CHUNK
+    lib.emw_cut_pieces.restype = lib.emw_cut_fetches.restype = lib.emw_sample.restype = C.c_int64
+    assert lib.emw_chunk() == CHUNK and lib.emw_len_chunk() == LEN_CHUNK and lib.emw_sample() == SAMPLE
     return lib, (targets[1] if san else None)
 
 
@@ -52,6 +57,7 @@ class Case:
             self.va["cs_text"] = np.zeros(8, np.uint8)
         if self.ca["names"].size == 0:
             self.ca["names"] = np.zeros(8, np.uint8)
+        self.consistent, self.irregular, self._oracle = False, None, {}   # (consistent_case)
 
     n_chr = property(lambda self: len(self.ca["chr_name_off"]) - 1)
     n = property(lambda self: {k: len(self.out[k]) for k in LISTS})
@@ -80,7 +86,7 @@ class Case:
     def tag_of(self, r):
         return self.va["cs_text"][int(self.va["rec_cs_off"][r]):int(self.va["rec_cs_off"][r + 1])].tobytes().decode("latin-1")
 
-    def owners(self):
+    def _owners_of(self):
         """{list: per element (contig, name)}: the .all names carry the path's number inside its contig."""
         o, C_ = self.out, int(self.out["n_contigs"])
         own = {}
@@ -90,8 +96,28 @@ class Case:
                       for p in range(int(o["all_path_off"][c]), int(o["all_path_off"][c + 1])) for _ in range(int(o["all_elem_off"][p]), int(o["all_elem_off"][p + 1]))]
         return own
 
+    def oracle_cut(self, k, i):
+        """(tag, mat_num, aln_len) of cut element i of list k from the I/O oracle's get_edited_paf_data, the counts wrapped to
+        int32 as the product's counters wrap (aasm_cut.h); the oracle raises where tag and coordinates do not agree."""
+        if (k, i) not in self._oracle:
+            va, e, (c, _) = self.va, self.out[k][i], self.owners()[k][i]
+            r = int(va["ctg_rec_off"][c]) + int(e["ctg_index"])
+            row = types.SimpleNamespace(qry_str=int(va["qry_str"][r]), qry_end=int(va["qry_end"][r]), aln_fwd=bool(va["aln_fwd"][r]), cs_string=self.tag_of(r),
+                                        mat_num=int(self.ca["mat_num"][r]), aln_len=int(self.ca["aln_len"][r]))
+            tag, mat, aln, cut = aasm_testlib.io_oracle().get_edited_paf_data(int(e["qs"]), int(e["qe"]), int(e["rs"]), int(e["re"]), row)
+            assert cut
+            self._oracle[(k, i)] = (tag, wrap32(mat), wrap32(aln))
+        return self._oracle[(k, i)]
+
+    def owners(self):
+        if getattr(self, "_owners", None) is None:
+            self._owners = self._owners_of()
+        return self._owners
+
     def py_rows(self, which=None):
-        """{list: [row bytes]} by py_row; plans without AASM_CUT_IRREGULAR.  which: {list: indices} (default: all)."""
+        """{list: [row bytes]} by py_row.  The tag of a cut element: render_cut on a regular plan, the I/O oracle's on an irregular
+        one; in a consistent case (consistent_case) tag, mat_num and aln_len of every cut element are the oracle's, whatever the
+        plan says.  which: {list: indices} (default: all)."""
         va, ca, own, rows = self.va, self.ca, self.owners(), {}
         for k in LISTS:
             rows[k] = {}
@@ -99,12 +125,20 @@ class Case:
                 e, p, (c, name) = self.out[k][i], self.plans[k][i], own[k][i]
                 r = int(va["ctg_rec_off"][c]) + int(e["ctg_index"])
                 cut = bool(int(p["flags"]) & AASM_CUT_IS_CUT)
-                assert not int(p["flags"]) & AASM_CUT_IRREGULAR
                 mat, aln = (int(p["mat_num"]), int(p["aln_len"])) if cut else (int(ca["mat_num"][r]), int(ca["aln_len"][r]))
+                if cut and self.consistent:
+                    tag, mat, aln = self.oracle_cut(k, i)
+                elif cut and int(p["flags"]) & AASM_CUT_IRREGULAR:
+                    tag = self.oracle_cut(k, i)[0]
+                else:
+                    tag = render_cut(p, self.tag_of(r))
                 rows[k][i] = py_row(name, int(va["qry_total"][r]), int(e["qs"]), int(e["qe"]), bool(va["aln_fwd"][r]), self.chr_of(int(va["ref_chr"][r])), int(ca["ref_total"][r]),
-                                    int(e["rs"]), int(e["re"]), mat, aln, int(va["map_qul"][r]), bool(e["is_alt"]), int(ca["cord_type"][r]), int(ca["row_index"][r]),
-                                    render_cut(p, self.tag_of(r)))
+                                    int(e["rs"]), int(e["re"]), mat, aln, int(va["map_qul"][r]), bool(e["is_alt"]), int(ca["cord_type"][r]), int(ca["row_index"][r]), tag)
         return rows
+
+
+def wrap32(v):
+    return (int(v) + 2 ** 31) % 2 ** 32 - 2 ** 31
 
 
 def hand_case(contigs, chr_names, per_contig, plans=None):
@@ -192,6 +226,47 @@ def check_offsets(off, texts):
         assert off[k][0] == 0 and np.array_equal(off[k][1:], ends), k
 
 
+def emul_cut_pieces(lib, off, limit, lst=1):
+    """rows_cut_pieces on the offsets `off` (n + 1 of them) -> (pieces as an [m, 5] array of list, e0, e1, b0, b1, its fetches as
+    an [f, 3] array of first, stride, count)."""
+    off = np.ascontiguousarray(off, np.int64)
+    n = len(off) - 1
+    out = np.full((n + 1, 5), -7, np.int64)
+    m = lib.emw_cut_pieces(C.c_void_p(off.ctypes.data), C.c_int64(n), C.c_int64(int(off[-1])), int(lst), C.c_int64(int(limit)), C.c_void_p(out.ctypes.data), C.c_int64(n + 1))
+    assert 0 <= m <= n, m
+    calls = np.zeros((n // SAMPLE + 3, 3), np.int64)
+    f = lib.emw_cut_fetches(C.c_void_p(calls.ctypes.data), C.c_int64(len(calls)))
+    assert 0 <= f <= len(calls), f
+    return out[:m], calls[:f]
+
+
+def check_pieces(off, limit, pieces, calls, lst=1):
+    """The piece cutter's contract on offsets `off` (numpy, n + 1 of them) -> (pieces made of whole sample blocks, pieces inside
+    a block whose rows were fetched)."""
+    n, total = len(off) - 1, int(off[-1])
+    if n == 0:
+        assert len(pieces) == 0 and len(calls) == 0
+        return 0, 0
+    starts = list(range(0, n, SAMPLE))
+    block_bytes = {s: int(off[min(n, s + SAMPLE)] - off[s]) for s in starts}
+    assert len(pieces) >= 1 and pieces[0][1] == 0 and pieces[-1][2] == n
+    for a, b in zip(pieces[:-1], pieces[1:]):
+        assert a[2] == b[1], "gap or overlap"
+    for l, e0, e1, b0, b1 in pieces.tolist():
+        assert l == lst and 0 <= e0 < e1 <= n and b0 == off[e0] and b1 == off[e1]
+        assert b1 - b0 <= limit or e1 - e0 == 1, (e0, e1, b1 - b0, limit)
+    if limit >= total:
+        assert len(pieces) == 1
+    if all(v <= limit for v in block_bytes.values()):
+        assert all(int(p[1]) % SAMPLE == 0 for p in pieces)
+    # the fetches: the samples once, then the rows of every block that does not fit (and holds more than one row), once each
+    assert calls[0].tolist() == [0, SAMPLE, n // SAMPLE + 1]
+    fine = [s for s in starts if block_bytes[s] > limit and min(n, s + SAMPLE) - s > 1]
+    assert calls[1:].tolist() == [[s, 1, min(n, s + SAMPLE) - s + 1] for s in fine], (calls[1:].tolist(), fine)
+    inside = sum(1 for p in pieces.tolist() if any(s <= p[1] and p[2] <= min(n, s + SAMPLE) for s in fine))
+    return len(pieces) - inside, inside
+
+
 # ---- the sanitizer program --------------------------------------------------------------------------------------------------------------
 def san_input(case):
     """rows_emul_san's input file (tests/host_emul/rows_emul.cpp)."""
@@ -246,17 +321,27 @@ class DeviceCase:
     def sizes(self, api, flags=0, stream=0):
         return api.rows_sizes_raw(self.view, self.cols, self.sz, self.dev_out, self.cuts, self.ro, self.info, flags, self.device, stream)
 
-    def format(self, api, lst, e0, e1, flags=0, pad=64, stream=0):
-        """-> (rc, bytes): rows [e0, e1) of list lst; pad guard bytes on both sides must come back untouched."""
+    def format(self, api, lst, e0, e1, flags=0, pad=64, stream=0, on=None):
+        """-> (rc, bytes): rows [e0, e1) of list lst; pad guard bytes on both sides must come back untouched.
+        on: a torch stream - the buffer's 0xEE fill is enqueued on it right before the format call on the same stream, with no
+        synchronize in between (a fill that overtakes the kernel shows as 0xEE bytes in the text)."""
         import torch
         o = self.off[LISTS[lst]] if 0 <= lst < 3 else None
         ok = o is not None and 0 <= e0 <= e1 < o.numel()
         nb = int((o[e1] - o[e0]).item()) if ok else 0
-        buf = torch.full((nb + 2 * pad,), 0xEE, dtype=torch.uint8, device=torch.device("cuda", self.device))
-        torch.cuda.synchronize(self.device)
-        rc = api.rows_format_raw(self.view, self.cols, self.sz, self.dev_out, self.cuts, self.ro, self.info, lst, e0, e1, buf.data_ptr() + pad, flags, self.device, stream)
-        torch.cuda.synchronize(self.device)
-        h = buf.cpu().numpy()
+        dev = torch.device("cuda", self.device)
+        if on is not None:
+            with torch.cuda.stream(on):
+                buf = torch.full((nb + 2 * pad,), 0xEE, dtype=torch.uint8, device=dev)
+            rc = api.rows_format_raw(self.view, self.cols, self.sz, self.dev_out, self.cuts, self.ro, self.info, lst, e0, e1, buf.data_ptr() + pad, flags, self.device, on.cuda_stream)
+            with torch.cuda.stream(on):
+                h = buf.cpu().numpy()
+        else:
+            buf = torch.full((nb + 2 * pad,), 0xEE, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(self.device)
+            rc = api.rows_format_raw(self.view, self.cols, self.sz, self.dev_out, self.cuts, self.ro, self.info, lst, e0, e1, buf.data_ptr() + pad, flags, self.device, stream)
+            torch.cuda.synchronize(self.device)
+            h = buf.cpu().numpy()
         assert (h[:pad] == 0xEE).all() and (h[pad + nb:] == 0xEE).all(), "bytes outside the range's text were written"
         return rc, h[pad:pad + nb].tobytes()
 
@@ -341,6 +426,224 @@ def sized_case(n_main, n_alt=0, n_all=0):
     return hand_case(contigs, ["chrA", "chromosome_B"], per, {k: np.array(v, CUT_DT) if v else np.zeros(0, CUT_DT) for k, v in plans.items()})
 
 
+# ---- consistent hand cases: tags, coordinates and cuts that the I/O oracle accepts ------------------------------------------------------
+def cs_ops(tag):
+    return re.findall(r":[0-9]+|\*[a-z][a-z]|[+-][a-z]+", tag[5:])
+
+
+def cs_spans(ops):
+    """(query bases, reference bases) a tag's operations consume."""
+    q = r = 0
+    for op in ops:
+        n = int(op[1:]) if op[0] == ":" else 1 if op[0] == "*" else len(op) - 1
+        q += n if op[0] != "-" else 0
+        r += n if op[0] != "+" else 0
+    return q, r
+
+
+def consistent_case(contigs, chr_names, per_contig):
+    """hand_case for records whose tag consumes exactly [qs, qe] (qe follows from the tag; `rs`: the reference start, default 1000)
+    and elements (ctg_index, a, b): the record without its first a and its last b query bases, both ends inside the ':' runs at
+    the tag's ends, so the reference coordinates follow from the query cut.  The case's expectation is the I/O oracle's on every
+    cut element (Case.py_rows); case.irregular[list][i]: whether the plan must be AASM_CUT_IRREGULAR, from the tag alone - a ':'
+    run that is kept whole is written with a leading zero.  The plans are the zero plans until consistent_plans() sets them."""
+    contigs = [(name, [dict(r) for r in recs]) for name, recs in contigs]
+    info = []
+    for _, recs in contigs:
+        for r in recs:
+            ops = cs_ops(r["cs"])
+            assert "cs:Z:" + "".join(ops) == r["cs"] and ops[0][0] == ":" and ops[-1][0] == ":"
+            q, rb = cs_spans(ops)
+            r["qe"] = r["qs"] + q - 1
+            info.append((ops, rb))
+    first = np.concatenate([[0], np.cumsum([len(recs) for _, recs in contigs])])
+    irregular = {k: [] for k in LISTS}
+
+    def element(c, k, el):
+        ci, a, b = el
+        rec = contigs[c][1][ci]
+        ops, rb = info[int(first[c]) + ci]
+        rs0 = rec.get("rs", 1000)
+        lo, hi = (a, b) if rec["fwd"] else (b, a)                  # bases taken from the tag's first / last run
+        n_lo, n_hi = int(ops[0][1:]), int(ops[-1][1:])
+        assert 0 <= lo and 0 <= hi and (lo < n_lo and hi < n_hi if len(ops) > 1 else lo + hi < n_lo), (c, el)
+        whole = ops[(1 if lo else 0):len(ops) - (1 if hi else 0)] if len(ops) > 1 else ([] if lo or hi else ops)
+        irregular[k].append(bool(a or b) and any(op[0] == ":" and op[1] == "0" for op in whole))
+        ers, ere = (rs0 + a, rs0 + rb - 1 - b) if rec["fwd"] else (rs0 + rb - 1 - a, rs0 + b)
+        return (rec["qs"] + a, rec["qe"] - b, ers, ere, ci)
+    per = []
+    for c, lists in enumerate(per_contig):
+        per.append({k: [element(c, k, el) for el in lists.get(k, ())] for k in ("main", "alt")})
+    for c, lists in enumerate(per_contig):                           # (.all after main and alt: the order of X.elements()' lists)
+        per[c]["all"] = [[element(c, "all", el) for el in path] for path in lists.get("all", ())]
+    case = hand_case(contigs, chr_names, per)
+    case.consistent, case.irregular = True, {k: np.array(v, bool) for k, v in irregular.items()}
+    return case
+
+
+def check_consistent_plans(case, plans):
+    """Plans of a consistent case (from the cut-plan kernel) against the oracle and the builder: an uncut element has the zero
+    plan; a cut one the flags IS_CUT [| IRREGULAR] exactly, and the oracle's counts."""
+    for k in LISTS:
+        assert len(plans[k]) == len(case.out[k]) == len(case.irregular[k]), k
+        va, own = case.va, case.owners()[k]
+        for i, (e, p) in enumerate(zip(case.out[k], plans[k])):
+            r = int(va["ctg_rec_off"][own[i][0]]) + int(e["ctg_index"])
+            if int(e["qs"]) == int(va["qry_str"][r]) and int(e["qe"]) == int(va["qry_end"][r]):
+                assert p.tobytes() == b"\0" * 48 and not case.irregular[k][i], (k, i)
+                continue
+            _, mat, aln = case.oracle_cut(k, i)
+            want = AASM_CUT_IS_CUT | (AASM_CUT_IRREGULAR if case.irregular[k][i] else 0)
+            assert (int(p["flags"]), int(p["mat_num"]), int(p["aln_len"])) == (want, mat, aln), (k, i, p, want, mat, aln)
+
+
+def consistent_plans(emc, case):
+    """The emulated cut-plan kernel's plans of a consistent case, checked (check_consistent_plans) and set as the case's."""
+    plans = X.emul_plans(emc, case.host_structs()[0], case.out)
+    check_consistent_plans(case, plans)
+    case.plans, case._joined = {k: np.ascontiguousarray(plans[k], CUT_DT) for k in LISTS}, None
+    return case
+
+
+def irregular_tag(i):
+    """":20" mid ":00" 10^(i % 19) "*ct:30": mid holds i % 9 runs with a leading zero, each before a substitution, an insertion or
+    a deletion; the long run prints with 1 .. 19 digits (above 2^31 the counters wrap: wrap32)."""
+    mid = "".join(":0%d" % (1 + (i + j) % 12) + ("*ac", "+gt", "-a")[j % 3] for j in range(i % 9))
+    return "cs:Z::20" + mid + ":00" + str(10 ** (i % 19)) + "*ct:30"
+
+
+def irregular_alignment_case(n=3 * CHUNK + 1):
+    """One list of n rows, every one irregular: both strands alternating, contig names of 1 .. 17 bytes, irregular_tag(i) cut by
+    1 + i % 19 bases at one end and 2 + i % 17 at the other.  mat_num and aln_len are the oracle's Python ints wrapped to int32."""
+    contigs = [("n" * (1 + i % 17), [{"cs": irregular_tag(i), "fwd": i % 2 == 0, "qs": 5 + i, "mq": i % 256, "row_index": i}]) for i in range(n)]
+    case = consistent_case(contigs, ["chrA"], [{"main": [(0, 1 + i % 19, 2 + i % 17)]} for i in range(n)])
+    assert case.irregular["main"].all()
+    return case
+
+
+def irregular_stats(rows):
+    """Of expected rows (bytes, in list order) with a re-cut tag: the text offsets mod 8 at which the tags' bodies start, the
+    bodies' lengths mod 8, and the digit counts of their runs."""
+    at, lens, digits, o = set(), set(), set(), 0
+    for row in rows:
+        j = row.index(b"\tcs:Z:") + 6
+        at.add((o + j) % 8); lens.add((len(row) - 1 - j) % 8)
+        digits.update(len(m) for m in re.findall(rb":([0-9]+)", row[j:]))
+        o += len(row)
+    return at, lens, digits
+
+
+REG_TAG, IRR_TAG = "cs:Z::20*ag:4+tt:3-c:12*ct:30", "cs:Z::20*ag:04+tt:3-c:012*ct:30"
+
+
+def kinds_case(kinds, all_paths=None):
+    """A consistent case from {list: "UIR.." per row}: U an uncut element, R a cut with a regular plan (REG_TAG), I a cut with an
+    irregular one (IRR_TAG, both strands).  Every contig has the same three records; main and alt rows are dealt over the contigs
+    by sized_case's pattern, .all rows over all_paths: per contig the sizes of its paths (default: two paths per contig)."""
+    pat = (1, 0, CHUNK - 2, 1, 0, 0, 1, CHUNK - 1, 0, 1)
+    split = {k: X._split(len(kinds.get(k, "")), pat) for k in ("main", "alt")}
+    if all_paths is None:
+        sizes = X._split(len(kinds.get("all", "")), (0, 1, 100, CHUNK - 101, 0, 0, 1, 90, CHUNK - 91, 0, 1))
+        all_paths = [sizes[p:p + 2] for p in range(0, len(sizes), 2)]
+    assert sum(sum(p) for p in all_paths) == len(kinds.get("all", ""))
+    nc = max(3, len(split["main"]) + 1, len(split["alt"]) + 2, len(all_paths) + 1)
+    contigs = [("k%d" % c, [{"cs": REG_TAG, "fwd": c % 2 == 0, "qs": 100 + c, "chr": c % 2, "row_index": 3 * c}, {"cs": IRR_TAG, "fwd": True, "qs": 7, "row_index": 3 * c + 1, "cord": 1},
+                            {"cs": IRR_TAG, "fwd": False, "qs": 10 ** 12, "rs": 5, "row_index": 3 * c + 2}]) for c in range(nc)]
+
+    def element(kind, i):
+        return {"U": (i % 3, 0, 0), "R": (0, i % 4, 1 + i % 5), "I": (1 + i % 2, 1 + i % 6, i % 5)}[kind]
+    per = [{"main": [], "alt": [], "all": []} for _ in range(nc)]
+    for k in ("main", "alt"):
+        i = 0
+        for c, m in enumerate(split[k]):
+            per[c + (1 if k == "alt" else 0)][k] = [element(kinds[k][i + j], i + j) for j in range(m)]
+            i += m
+    i = 0
+    for c, paths in enumerate(all_paths):
+        for m in paths:
+            per[c]["all"].append([element(kinds["all"][i + j], i + j) for j in range(m)])
+            i += m
+    case = consistent_case(contigs, ["chrA", "chromosome_B"], per)
+    for k in LISTS:
+        assert "".join("I" if x else "-" for x in case.irregular[k]) == "".join(x if x == "I" else "-" for x in kinds.get(k, "")), k
+    return case
+
+
+MIXED_N = 3 * CHUNK + 5
+MIXED_PATHS = [[1 + (p + 1) % 3 for p in range(101)]]                   # contig 0: 101 paths (.1, .10 and .100 hold two elements each)
+
+
+def mixed_kinds():
+    """{list: kinds} of irregular_mixed_case: MIXED_N rows per list.  Irregular: the first and the last row of the list, rows
+    CHUNK - 1, CHUNK and 2 CHUNK - 1, in .all both rows of the paths .1, .10 and .100, and every seventh row elsewhere - except in
+    chunk 2, which holds none.  The rows beside those edges are uncut, regular and irregular ones."""
+    out = {}
+    for k in LISTS:
+        kind = ["UR"[i % 2] if i // CHUNK == 2 else "URUIRUR"[i % 7] for i in range(MIXED_N)]
+        for i, x in ((0, "I"), (1, "U"), (CHUNK - 2, "R"), (CHUNK - 1, "I"), (CHUNK, "I"), (CHUNK + 1, "I"), (2 * CHUNK - 2, "U"), (2 * CHUNK - 1, "I"),
+                     (2 * CHUNK, "R"), (MIXED_N - 2, "I"), (MIXED_N - 1, "I")):
+            kind[i] = x
+        if k == "all":
+            ends = np.concatenate([[0], np.cumsum(MIXED_PATHS[0])])
+            for p in (0, 9, 99):
+                assert ends[p + 1] - ends[p] == 2 and ends[p + 1] < 2 * CHUNK
+                kind[int(ends[p])] = kind[int(ends[p]) + 1] = "I"
+        out[k] = "".join(kind)
+    return out
+
+
+def irregular_mixed_case():
+    kinds = mixed_kinds()
+    rest = X._split(MIXED_N - sum(MIXED_PATHS[0]), (0, 60, CHUNK - 3, 1, 0, 70))
+    return kinds_case(kinds, MIXED_PATHS + [[]] + [rest[p:p + 2] for p in range(0, len(rest), 2)])
+
+
+LONG_UNIT = ":01*ac"
+
+
+def long_irregular_case():
+    """"cs:Z::5" + ":01*ac" * 70 000 + ":5" cut on both strands, and a tag of about 1 MiB built the same way: every ":01" comes out
+    as ":1", so a rendered tag is shorter than its source by the number of its units.  Each long row has short rows (uncut, regular)
+    before and behind it in its chunk."""
+    many, mib = "cs:Z::5" + LONG_UNIT * 70000 + ":5", "cs:Z::5" + LONG_UNIT * ((1 << 20) // len(LONG_UNIT)) + ":5"
+    contigs = [("s", [{"cs": REG_TAG, "fwd": True, "qs": 100}]), ("many", [{"cs": many, "fwd": True, "qs": 0}, {"cs": many, "fwd": False, "qs": 7}]),
+               ("t", [{"cs": REG_TAG, "fwd": False, "qs": 50}]), ("mib", [{"cs": mib, "fwd": False, "qs": 3}]), ("u", [{"cs": REG_TAG, "fwd": True, "qs": 9}])]
+    per = [{"main": [(0, 0, 0), (0, 3, 1)], "alt": [(0, 2, 2)]}, {"main": [(0, 2, 2)], "alt": [(1, 3, 1)], "all": [[(1, 4, 4)]]}, {"main": [(0, 1, 0)], "alt": [(0, 0, 0)], "all": [[(0, 0, 5)]]},
+           {"main": [(0, 1, 3)]}, {"main": [(0, 0, 0), (0, 5, 5)], "all": [[(0, 0, 0)], [(0, 1, 1)]]}]
+    case = consistent_case(contigs, ["chrL"], per)
+    assert case.irregular["main"].tolist() == [False, False, True, False, True, False, False] and case.irregular["alt"].tolist() == [False, True, False]
+    return case
+
+
 def joined_py(case):
+    if case.consistent and getattr(case, "_joined", None):           # (a consistent case is not edited once it has its plans)
+        return list(case._joined)
     rows = case.py_rows()
-    return [b"".join(rows[k][i] for i in range(len(case.out[k]))) for k in LISTS]
+    out = [b"".join(rows[k][i] for i in range(len(case.out[k]))) for k in LISTS]
+    if case.consistent:
+        case._joined = list(out)
+    return out
+
+
+def oracle_checked_irregular(T, exp, plans):
+    """Plans of a text_fuzz run the oracle accepts against the I/O oracle alone (exp: text_fuzz.expected()): cut or not, the
+    counts, and on a regular plan the rendered tag -> {list: indices of the irregular plans}."""
+    io, sol, st, out = T.io_oracle(), exp.sol, exp.st, {}
+    paths = [c for c in range(sol["n_contigs"]) for _ in range(int(sol["all_path_off"][c]), int(sol["all_path_off"][c + 1]))]
+    owner = {"main": np.repeat(np.arange(sol["n_contigs"]), np.diff(sol["main_off"])), "alt": np.repeat(np.arange(sol["n_contigs"]), np.diff(sol["alt_off"])),
+             "all": np.repeat(np.array(paths, np.int64), np.diff(sol["all_elem_off"]))}
+    for k in LISTS:
+        assert len(plans[k]) == len(sol[k]) == len(owner[k]), k
+        out[k] = []
+        for i, (e, p) in enumerate(zip(sol[k], plans[k])):
+            row = st.paf_data[int(owner[k][i])][int(e["ctg_index"])]
+            tag, mat, aln, cut = io.get_edited_paf_data(int(e["qs"]), int(e["qe"]), int(e["rs"]), int(e["re"]), row)
+            f = int(p["flags"])
+            assert f & ~AASM_CUT_IRREGULAR == (AASM_CUT_IS_CUT if cut else 0), (k, i, f)
+            if cut:
+                assert (int(p["mat_num"]), int(p["aln_len"])) == (wrap32(mat), wrap32(aln)), (k, i)
+                if f & AASM_CUT_IRREGULAR:
+                    out[k].append(i)
+                else:
+                    assert render_cut(p, row.cs_string) == tag, (k, i)
+    return out

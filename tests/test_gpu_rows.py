@@ -26,6 +26,11 @@ def torch():
     return torch
 
 
+@pytest.fixture(scope="module")
+def emc(tmp_path_factory):
+    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_gpu_rows"))[0]
+
+
 def hand_cases():
     return [("alignment", W.alignment_case, 0), ("long_rows", W.long_case, 0), ("one_row", lambda: W.sized_case(1, 0, 3), 0),
             ("chunk_minus_1", lambda: W.sized_case(W.CHUNK - 1, 0, W.CHUNK), 0), ("chunk", lambda: W.sized_case(W.CHUNK, 1, W.CHUNK + 1), 0),
@@ -149,6 +154,97 @@ def test_text_fuzz_to_torch_rows(T, torch):
                 assert e.value.code == _abi.AASM_E_PARSE and "list %s, element %d, flags 0x%x" % (W.LISTS[l], j, v) in str(e.value), (kind, i)
             res.close(); db.close()
     assert n["ok"] >= 8 and n["err"] >= 2 and n["irregular"] >= 1, n
+
+
+def irregular_cases():
+    from test_rows_cpu import irregular_cases as cpu
+    return [c + (0,) for c in cpu()] + [("nine_chunks_few_blocks", cpu()[-1][1], _abi.AASM_ROWS_H_FEW_BLOCKS)]
+
+
+@pytest.mark.parametrize("name,make,flags", irregular_cases(), ids=[c[0] for c in irregular_cases()])
+def test_irregular_hand_cases(T, torch, emc, name, make, flags):
+    """The CPU tier's hand-made irregular rows with all the lanes of the fill: every chunk of a list irregular (tags rendered in
+    place at every offset and length mod 8, runs of 1 .. 19 digits), irregular rows at chunk, list and path edges beside uncut and
+    regular ones with a chunk that holds none, 70 000-unit and 1 MiB irregular tags beside short rows, 9 irregular chunks on the
+    full grid and on 3 blocks.  The plans are the emulated cut-plan kernel's, checked against the oracle and uploaded; the rows
+    are the I/O oracle's."""
+    from test_rows_cpu import check_irregular_inputs
+    case = W.consistent_plans(emc, make())
+    check_irregular_inputs(name.replace("_few_blocks", ""), case)
+    dc = W.DeviceCase(case)
+    texts = dc.texts(T.api(), flags)
+    assert texts == W.joined_py(case)
+    W.check_offsets(dc.offsets(), texts)
+
+
+def test_irregular_ranges(T, torch, emc):
+    """40-row lists with every third row irregular, the first and the last among them: every split point gives the whole, every
+    irregular row formatted alone is that row, and no range touches a byte outside its own (the 64 guard bytes)."""
+    from test_rows_cpu import ranges_case
+    api, case = T.api(), W.consistent_plans(emc, ranges_case())
+    dc = W.DeviceCase(case)
+    texts = dc.texts(api)
+    assert texts == W.joined_py(case)
+    rows = case.py_rows()
+    assert case.irregular["main"][0] and case.irregular["main"][39]
+    for l, k in enumerate(W.LISTS):
+        for e in range(41):
+            a, b = dc.format(api, l, 0, e), dc.format(api, l, e, 40)
+            assert a[0] == 0 and b[0] == 0 and a[1] + b[1] == texts[l], (l, e)
+        for i in np.flatnonzero(case.irregular[k]):
+            assert dc.format(api, l, int(i), int(i) + 1) == (0, rows[k][int(i)]), (k, i)
+
+
+REFUSAL = b"aasm_rows_format_device: info is not what aasm_rows_sizes_device returned for these row_off arrays"
+
+
+def test_the_64_most_recent_sizes_calls(T, torch):
+    """The library remembers the 64 most recent sizes calls of a device (include/alignasm_amd.h): after 65 calls on distinct
+    row_off arrays the first info is refused, the other 64 format; sizing the first again makes it valid; a sizes call on the same
+    arrays with another result replaces the earlier one, whose info is refused from then on."""
+    api = T.api()
+    case = W.sized_case(1, 0, 0)
+    row = W.joined_py(case)[0]
+    dcs = [W.DeviceCase(case) for _ in range(65)]
+    for dc in dcs:
+        assert dc.sizes(api) == 0 and dc.info.n_flagged == 0 and dc.info.bytes[0] == len(row)
+    assert dcs[0].format(api, 0, 0, 1)[0] == _abi.AASM_E_INVAL and api.LIB.aasm_last_error() == REFUSAL
+    for dc in dcs[1:]:
+        assert dc.format(api, 0, 0, 1) == (0, row)
+    assert dcs[0].sizes(api) == 0 and dcs[0].format(api, 0, 0, 1) == (0, row)
+    # the same arrays sized with another result (a row of another length)
+    other = W.hand_case([("another_name", [{"cs": W.TAG, "fwd": True, "qs": 100, "qe": 134}])], ["chrA"], [{"main": [(100, 134, 7, 41, 0)]}])
+    row2 = W.joined_py(other)[0]
+    assert len(row2) != len(row)
+    dc2 = W.DeviceCase(other)
+    dc2.off, dc2.ro = dcs[0].off, dcs[0].ro
+    assert dc2.sizes(api) == 0 and dc2.info.bytes[0] == len(row2)
+    assert dcs[0].format(api, 0, 0, 1)[0] == _abi.AASM_E_INVAL and api.LIB.aasm_last_error() == REFUSAL
+    assert dc2.format(api, 0, 0, 1) == (0, row2)
+
+
+def test_a_non_default_stream(T, torch, emc):
+    """Sizes and format on a torch.cuda.Stream(): the buffer's 0xEE fill is enqueued on that stream right before the format call
+    with no synchronize in between, so a kernel that ran on another stream shows as wrong bytes.  The same stream through
+    to_torch(stream=..., rows=True)."""
+    api, st = T.api(), torch.cuda.Stream()
+    case = W.consistent_plans(emc, W.irregular_mixed_case())
+    want = W.joined_py(case)
+    dc = W.DeviceCase(case)
+    torch.cuda.synchronize()                                         # (the uploads ran on the default stream)
+    assert dc.sizes(api, stream=st.cuda_stream) == 0 and dc.info.n_flagged == 0
+    for l, k in enumerate(W.LISTS):
+        assert dc.format(api, l, 0, case.n[k], on=st) == (0, want[l])
+        assert dc.format(api, l, W.CHUNK - 1, 2 * W.CHUNK, on=st) == (0, b"".join(case.py_rows({k: range(W.CHUNK - 1, 2 * W.CHUNK)})[k].values()))
+    text = F.joined([F.shaped_text(i) for i in range(3)])
+    exp = F.expected(T, text, *F.RUNS[0])
+    assert exp.kind == "ok"
+    api, paf, db, res = fuzz_on_device(T, torch, text, *F.RUNS[0])
+    d = res.to_torch(stream=st, cuts=db, rows=True)
+    with torch.cuda.stream(st):
+        got = [d[k + "_text"].cpu().numpy().tobytes() for k in W.LISTS]
+    assert got == list(exp.files)
+    res.close(); db.close()
 
 
 def host_files(T, paf, res, d, stem, cuts=None):

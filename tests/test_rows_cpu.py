@@ -261,15 +261,149 @@ def test_record_and_plan_faults(emw, name, flag, mutate):
             assert rc == 0 and t[lo:hi] == b"\xee" * (hi - lo)
 
 
+# ---- irregular rows placed by hand (tests/rows_testlib.py: consistent cases; expected bytes are the I/O oracle's) --------------------
+def irregular_cases():
+    return [("alignment", W.irregular_alignment_case), ("mixed", W.irregular_mixed_case), ("long", W.long_irregular_case),
+            ("nine_chunks", lambda: W.irregular_alignment_case(9 * W.CHUNK))]
+
+
+@pytest.mark.parametrize("name,make", irregular_cases(), ids=[c[0] for c in irregular_cases()])
+def test_irregular_hand_cases(emw, emc, name, make):
+    """Irregular rows in every chunk of a list, at chunk, list and path edges beside uncut and regular rows, long ones beside short
+    ones, 9 chunks on 3 blocks: the emulated cut-plan kernel's plans agree with the oracle and the builder (flags, counts), and the
+    rows are the oracle's, at the full grid and at 3 blocks."""
+    case = W.consistent_plans(emc, make())
+    want = W.joined_py(case)
+    for mb in (0, 3):
+        info, off, texts = W.emul_texts(emw[0], case, max_blocks=mb)
+        assert texts == want, mb
+        W.check_offsets(off, texts)
+    check_irregular_inputs(name, case)
+
+
+def check_irregular_inputs(name, case):
+    """What a hand case must hold, from its inputs and the oracle's rows alone (both tiers)."""
+    irr = {k: np.flatnonzero(case.irregular[k]) for k in W.LISTS}
+    rows = case.py_rows({k: [int(i) for i in irr[k]] for k in W.LISTS})
+    if name in ("alignment", "nine_chunks"):
+        n = case.n["main"]
+        assert len(irr["main"]) == n and set(irr["main"] // W.CHUNK) == set(range((n + W.CHUNK - 1) // W.CHUNK))
+        whole = case.py_rows()["main"]                               # (every row is irregular: the offsets are the text's)
+        at, lens, digits = W.irregular_stats([whole[i] for i in range(n)])
+        assert at == set(range(8)) and lens == set(range(8)) and digits == set(range(1, 20)), (at, lens, digits)
+        assert set(bool(f) for f in case.va["aln_fwd"]) == {True, False} and set(len(case.name_of(c)) for c in range(n)) == set(range(1, 18))
+    elif name == "mixed":
+        for k in W.LISTS:
+            s = set(int(i) for i in irr[k])
+            assert {0, W.CHUNK - 1, W.CHUNK, 2 * W.CHUNK - 1, W.MIXED_N - 1} <= s and not any(i // W.CHUNK == 2 for i in s)
+            assert set(i // W.CHUNK for i in s) == {0, 1, 3}
+            kinds = W.mixed_kinds()[k]
+            beside = set(kinds[j] for i in (0, W.CHUNK - 1, W.CHUNK, 2 * W.CHUNK - 1, W.MIXED_N - 1) for j in (i - 1, i + 1) if 0 <= j < W.MIXED_N)
+            assert beside == {"U", "R", "I"}
+        names = [rows["all"][int(i)].split(b"\t")[0] for i in irr["all"]]
+        for suffix in (b"k0.1", b"k0.10", b"k0.100"):
+            assert names.count(suffix) == 2, suffix                  # both rows of the path
+    elif name == "long":
+        for k, i, units in (("main", 2, 70000), ("alt", 1, 70000), ("all", 0, 70000), ("main", 4, (1 << 20) // len(W.LONG_UNIT))):
+            e = case.out[k][i]
+            r = int(case.va["ctg_rec_off"][case.owners()[k][i][0]]) + int(e["ctg_index"])
+            assert len(case.oracle_cut(k, i)[0]) == len(case.tag_of(r)) - units, (k, i)
+        assert len(case.tag_of(4)) > (1 << 20)
+
+
+def ranges_case():
+    """40 rows per list, every third one irregular (the first and the last among them), the others uncut and regular in turn."""
+    kinds = "".join("I" if i % 3 == 0 else "UR"[i % 2] for i in range(40))
+    return W.kinds_case({"main": kinds, "alt": kinds[::-1], "all": kinds})
+
+
+def test_irregular_ranges(emw, emc):
+    """Every split point of 40-row lists with irregular rows: the two ranges concatenate to the whole; every irregular row formatted
+    alone is that row; the guard bytes around every range stay untouched (emul_format)."""
+    case = W.consistent_plans(emc, ranges_case())
+    info, off, texts = W.emul_texts(emw[0], case)
+    assert texts == W.joined_py(case)
+    rows = case.py_rows()
+    for l, k in enumerate(W.LISTS):
+        for e in range(41):
+            a, b = W.emul_format(emw[0], case, info, off, l, 0, e), W.emul_format(emw[0], case, info, off, l, e, 40)
+            assert a[0] == 0 and b[0] == 0 and a[1] + b[1] == texts[l], (l, e)
+        for i in np.flatnonzero(case.irregular[k]):
+            assert W.emul_format(emw[0], case, info, off, l, int(i), int(i) + 1) == (0, rows[k][int(i)]), (k, i)
+    assert case.irregular["main"][0] and case.irregular["main"][39] and case.irregular["main"].sum() == 14
+
+
+# ---- results of real size (the text fuzz's joined texts) -----------------------------------------------------------------------------
+@pytest.mark.parametrize("first", (0, 10))
+def test_joined_texts(T, emw, emc, first):
+    """Ten shaped texts as one file, both runs: main has three fill chunks or more and irregular rows in three of them or more
+    (counted on plans checked against the oracle); the emulated rows are the oracle's files, at the full grid and at 3 blocks."""
+    text = F.joined([F.shaped_text(i) for i in range(first, first + 10)])
+    for K, nsl in F.RUNS:
+        exp, case = fuzz_case(T, emw, emc, text, K, nsl)
+        assert exp.kind == "ok"
+        irr = W.oracle_checked_irregular(T, exp, case.plans)
+        assert case.n["main"] > 2 * W.CHUNK and len(set(i // W.CHUNK for i in irr["main"])) >= 3, (case.n, irr["main"])
+        for mb in (0, 3):
+            info, off, texts = W.emul_texts(emw[0], case, max_blocks=mb)
+            assert texts == list(exp.files), (K, mb)
+        W.check_offsets(off, texts)
+
+
+# ---- the device writer's pieces (rows_cut_pieces, aasm_rows.h) ---------------------------------------------------------------------
+def piece_offsets(n, shape):
+    """Offsets of n rows: "uniform" (37 bytes each), "random" (seeded, 1 - 400 bytes), ("giant", g): 37 bytes and row g of 10^6."""
+    if shape == "uniform":
+        lens = np.full(n, 37, np.int64)
+    elif shape == "random":
+        lens = np.random.default_rng(1024 + n).integers(1, 401, n).astype(np.int64)
+    else:
+        lens = np.full(n, 37, np.int64)
+        lens[shape[1]] = 10 ** 6
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+
+PIECE_N = (0, 1, 1023, 1024, 1025, 2047, 2048, 2049, 3 * 1024 + 5)
+
+
+def test_cut_pieces_contract(emw):
+    """rows_cut_pieces over host arrays: the pieces cover the list in order without gap or overlap, start and end at the rows'
+    offsets, hold at most `limit` bytes or one row; a limit of the whole text gives one piece; where every block of 1024 rows fits,
+    every piece starts at a sample; the rows' own offsets are fetched only for blocks that do not fit, once each.  Both branches
+    produce several pieces, alone and mixed, also where n is a multiple of 1024 and where the limit is a block's bytes."""
+    lib = emw[0]
+    seen = {"samples_only": 0, "rows_only": 0, "mixed": 0, "limit_is_block": 0, "long_row_in_block": 0}
+    for n in PIECE_N:
+        shapes = ["uniform", "random"] + [("giant", g) for g in sorted(set(g for g in (0, 1023, 1024, n - 1) if 0 <= g < n))]
+        for shape in shapes:
+            off = piece_offsets(n, shape)
+            total, lens = int(off[-1]), np.diff(off)
+            block = int(off[min(n, W.SAMPLE)])
+            limits = {1, total, total - 1, block, block - 1, block + 1, block + block // 2}
+            if n:
+                limits |= {int(lens.min()), int(lens.max()), int(lens.max()) - 1}
+            for limit in sorted(v for v in limits if v >= 1):
+                pieces, calls = W.emul_cut_pieces(lib, off, limit)
+                by_samples, by_rows = W.check_pieces(off, limit, pieces, calls)
+                seen["samples_only"] += by_samples > 1 and by_rows == 0
+                seen["rows_only"] += by_rows > 1 and by_samples == 0
+                seen["mixed"] += by_samples >= 1 and by_rows >= 1
+                seen["limit_is_block"] += limit == block and n > W.SAMPLE
+                seen["long_row_in_block"] += n > 1 and int(lens.max()) > limit >= int(lens.min())
+    assert all(v > 0 for v in seen.values()), seen
+
+
 def test_sanitizer_program(T, emw, emc, tmp_path):
     """rows_emul_san (host address + undefined sanitizers; every tag in a block that ends with it, every list's text in a block of
-    exactly its bytes) on the shaped corpus, the alignment case and the long rows: exit 0 and the expected bytes."""
+    exactly its bytes) on the shaped corpus, the alignment case, the long rows and the hand-made irregular rows (all of three
+    chunks, the long tags): exit 0 and the expected bytes."""
     lib, san = emw
     for i in range(0, 30, 3):
         K, nsl = F.RUNS[i % 2]
         exp, case = fuzz_case(T, emw, emc, F.shaped_text(i), K, nsl)
         assert W.run_san(san, case, tmp_path, "shaped%d" % i) == b"".join(exp.files), i
-    for name, case in (("align", W.alignment_case()), ("long", W.long_case()), ("sized", W.sized_case(2 * W.CHUNK + 1, 5, W.CHUNK + 3))):
+    for name, case in (("align", W.alignment_case()), ("long", W.long_case()), ("sized", W.sized_case(2 * W.CHUNK + 1, 5, W.CHUNK + 3)),
+                       ("irregular_align", W.consistent_plans(emc, W.irregular_alignment_case())), ("irregular_long", W.consistent_plans(emc, W.long_irregular_case()))):
         assert W.run_san(san, case, tmp_path, name) == b"".join(W.joined_py(case)), name
 
 
