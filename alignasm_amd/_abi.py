@@ -17,6 +17,9 @@ AASM_E_OVERFLOW, AASM_E_INTERNAL, AASM_E_PARSE, AASM_E_IO = -5, -6, -7, -8
 # reader flags (aasm_paf_read_opts, aasm_paf_parse_device); AASM_READ_H_*: test hooks of the device reader, 0 in production
 AASM_READ_DEVICE_RANGES, AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS = 1, 0x100, 0x200
 
+# int aasm_debug_poison(int byte): (restype, argtypes); 0 = off, 1..255 = the allocators' fill byte, -1 for anything else
+DEBUG_POISON_SIG = (C.c_int, [C.c_int])
+
 _IN_ARRAYS = [
     ("ctg_rec_off", np.int64), ("qry_str", np.int64), ("qry_end", np.int64), ("ref_str", np.int64),
     ("ref_end", np.int64), ("qry_total", np.int64), ("ref_chr", np.int32), ("aln_fwd", np.uint8),

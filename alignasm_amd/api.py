@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, CUT_DT, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
                    DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +63,7 @@ def _load():
     lib.aasm_last_error.restype = C.c_char_p
     lib.aasm_debug_fetch.restype = C.c_int64
     lib.aasm_debug_counter.restype = C.c_int64
+    lib.aasm_debug_poison.restype, lib.aasm_debug_poison.argtypes = DEBUG_POISON_SIG
     lib.aasm_paf_n_contigs.restype = C.c_int64
     lib.aasm_cs_match_ranges.restype = C.c_int64
     lib.aasm_cs_edit.restype = C.c_int64
@@ -80,7 +81,7 @@ LIB = _load()
 EXPORTED = [
     "aasm_abi_version", "aasm_device_count", "aasm_init", "aasm_last_error", "aasm_solve_batch", "aasm_solve_batch_multi", "aasm_solve_device",
     "aasm_result_stats", "aasm_result_fetch", "aasm_result_free", "aasm_free_out", "aasm_upload_batch", "aasm_upload_free",
-    "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
+    "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_poison", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
     "aasm_paf_parse_device", "aasm_paf_read_device",
@@ -152,6 +153,13 @@ def sssp_dial(g_voff, rowptr, col, cost, src, lim=2, device=0):
 def debug_counter(name):
     """Process-wide diagnostic counter: "range_splits", "device_mallocs", "stream_syncs", "read_slow_rows", "read_host_fallbacks"."""
     return int(LIB.aasm_debug_counter(name.encode()))
+
+
+def debug_poison(byte):
+    """Process-wide debug switch: 0 = off (production); 1..255 = the byte the workspace arena (whole, at the start of every
+    device solve), the generic graph entries' blocks and the device reader's blocks are filled with before use, so that a
+    kernel reading a never-written cell meets it.  Returns the previous value; -1 (nothing changed) outside 0..255."""
+    return int(LIB.aasm_debug_poison(int(byte)))
 
 
 def reserve_workspace(device=0, nbytes=0):

@@ -94,8 +94,12 @@ static_assert(sizeof(EnumLdsT<64>) <= AASM_ENUM2_LDS_BYTES_F(64) && sizeof(EnumL
 
 struct QE { uint64_t sum, key2, nc; int32_t tag; };                  // nc = node << 32 | insertion index; tag: refill only (source level)
 #define QE_INF_SUM 0x7fffffffffffffffull
+// kb_enum_lsm keeps a walk's score sum + QE_SUM_BIAS in QE.sum: a walk's sum is negative where a record's query interval runs past
+// the query's length (qry_end > qry_total, which the reference solves like any other record), and as an unsigned word such a
+// sum sorted behind QE_INF_SUM - the walk was never popped and the enumeration ended early.  Sums are far inside (-2^62, 2^62).
+#define QE_SUM_BIAS ((uint64_t)1 << 62)
 AASM_DEV QE qe_inf() { QE e; e.sum = QE_INF_SUM; e.key2 = 0; e.nc = 0; e.tag = 0; return e; }
-AASM_DEV bool qe_less(const QE &a, const QE &b) {                    // score sums are non-negative: unsigned order == signed order
+AASM_DEV bool qe_less(const QE &a, const QE &b) {                    // score sums are non-negative (kb_enum_lsm: biased): unsigned order == signed order
     return (a.sum < b.sum) | ((a.sum == b.sum) & ((a.key2 < b.key2) | ((a.key2 == b.key2) & (a.nc < b.nc))));
 }
 AASM_DEV bool qe_less_u(const QE &a, const QE &b) {                  // the same on wave-uniform values
@@ -377,7 +381,7 @@ template <int FMAX> AASM_DEV void kb_enum_lsm(const KCtx &k, const WS &w) {   //
     {
         const HNode r0 = nodes[hs];
         const Dist d0 = dist_add(dsrc, hnode_key(r0));
-        QE x; x.sum = (uint64_t)uni(d0.qry + d0.ref); x.key2 = uni_u64(qe_key2(d0.anom, d0.qnz, d0.qtot), 0); x.nc = mk64(0, hs); x.tag = 0;
+        QE x; x.sum = (uint64_t)uni(d0.qry + d0.ref) + QE_SUM_BIAS; x.key2 = uni_u64(qe_key2(d0.anom, d0.qnz, d0.qtot), 0); x.nc = mk64(0, hs); x.tag = 0;
         I4 o0, o1;
         o0.x = uni(lo32((uint64_t)d0.qry)); o0.y = uni(hi32((uint64_t)d0.qry)); o0.z = uni(d0.anom); o0.w = uni(d0.qnz); o1.x = uni(d0.qtot); o1.y = -1; o1.z = 0; o1.w = 0;
         if (lane == 0) { I4 cd; cd.x = hs; cd.y = -1; cd.z = o0.x; cd.w = o0.y; kcand[0] = cd; I4 ce; ce.x = o0.z; ce.y = o0.w; ce.z = o1.x; ce.w = 0; kcand[1] = ce; }
@@ -524,7 +528,7 @@ template <int FMAX> AASM_DEV void kb_enum_lsm(const KCtx &k, const WS &w) {   //
             const I4 t0 = q.L->slot[sl][0];
             const int32_t tt = q.L->slot[sl][1].x;
             const uint64_t tq = mk64(t0.x, t0.y);
-            Dist dtop; dtop.qry = (int64_t)tq; dtop.ref = (int64_t)(f.sum - tq); dtop.anom = t0.z; dtop.qnz = t0.w; dtop.qtot = tt; dtop.pad = 0;
+            Dist dtop; dtop.qry = (int64_t)tq; dtop.ref = (int64_t)(f.sum - QE_SUM_BIAS - tq); dtop.anom = t0.z; dtop.qnz = t0.w; dtop.qtot = tt; dtop.pad = 0;
             const int32_t at = found + (lane - hd);
             kd[at] = dtop; klast[at] = lo32(f.nc);
             q.L->freel[ftop + (lane - hd)] = sl;

@@ -331,6 +331,12 @@ static DevCtx g_ctx[16];
 static std::mutex g_init_mu;
 static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0}, g_n_read_slow_rows{0}, g_n_read_fallbacks{0};
 
+// aasm_debug_poison: 0 = off (production), 1..255 = the byte the three allocators below fill fresh working memory with, so that
+// a kernel reading a cell nobody wrote meets it instead of a harmless left-over.  Left alone: the scans' ticket / tile words
+// (d_scratch, d_scratch2: zero between solves by contract), the pinned buffers, g_rows_words, aasm_upload memory (written whole by H2D).
+static std::atomic<int> g_poison{0};
+static inline int poison_byte() { return g_poison.load(std::memory_order_relaxed); }
+
 static std::string hip_err(const char *what, hipError_t e) {
     return std::string(what) + ": " + hipGetErrorString(e);
 }
@@ -428,6 +434,11 @@ struct GpuBackend {
             }
             cx.blocks.push_back(ArenaBlock{p, cap, 0});
             cur_block = cx.blocks.size() - 1;
+            if (const int pz = poison_byte()) {                      // (waits: the block's first user may be on another of the solve's streams)
+                e = hipMemsetAsync(p, pz, cap, stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(stream);
+                if (e != hipSuccess) { hip_fail("hipMemsetAsync(poison)", e); return nullptr; }
+            }
         }
         ArenaBlock &b = cx.blocks[cur_block];
         void *p = b.p + b.used;
@@ -436,6 +447,15 @@ struct GpuBackend {
         if (bytes > cx.peak_bytes) cx.peak_bytes = bytes;
         named[name] = {p, n};
         return p;
+    }
+    // aasm_debug_poison: every block's whole capacity, before the solve's first allocation (used is 0 everywhere, the exports
+    // have drained): the attached backends, which allocate behind the solve's arrays, start from the byte too
+    void poison_arena(int pz) {
+        for (auto &b : cx.blocks) {
+            if (fail) return;
+            hipError_t e = hipMemsetAsync(b.p, pz, b.cap, stream);
+            if (e != hipSuccess) hip_fail("hipMemsetAsync(poison)", e);
+        }
     }
     bool failed() const { return fail; }
     bool test_dirty_scan = false;
@@ -599,6 +619,7 @@ struct GraphGpu {
         if (e != hipSuccess) return nullptr;
         if ((e = hipMalloc(&p, n)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         blocks.push_back(p);
+        if (const int pz = poison_byte()) { if ((e = hipMemsetAsync(p, pz, n, stream)) != hipSuccess) return nullptr; }
         return p;
     }
     size_t mark() const { return blocks.size(); }
@@ -746,6 +767,7 @@ int aasm_solve_device(const aasm_batch_in *dev_in, const aasm_opts *opts, void *
     hipSetDevice(o.device);
     hipStream_t s = stream ? (hipStream_t)stream : cx.stream;
     GpuBackend be(cx, s, o.collect_timing != 0);
+    if (const int pz = poison_byte()) be.poison_arena(pz);
     GpuBackend *bp = &be;
     return solve_on_device(cx, *dev_in, o, s, res, &bp);
 }
@@ -1018,6 +1040,11 @@ int aasm_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_t
 
 void aasm_ksw_free(aasm_ksw_out *out) { ksw_free_out(out); }
 
+int aasm_debug_poison(int byte) {
+    if (byte < 0 || byte > 255) return -1;
+    return g_poison.exchange(byte, std::memory_order_relaxed);
+}
+
 int64_t aasm_debug_counter(const char *name) {
     if (!name) return -1;
     const std::string n(name);
@@ -1141,6 +1168,7 @@ struct ReadGpu {
         const hipError_t r = hipMalloc(&p, n ? n : 8);
         if (r != hipSuccess) { (void)hipGetLastError(); if (r == hipErrorOutOfMemory) oom = true; else e = r; return nullptr; }
         blocks.push_back(p);
+        if (const int pz = poison_byte()) { if ((e = hipMemsetAsync(p, pz, n ? n : 8, cx.stream)) != hipSuccess) return nullptr; }
         return p;
     }
     void release(void *p) {

@@ -369,6 +369,13 @@ int64_t aasm_debug_fetch(aasm_result *res, const char *name, void *dst, int64_t 
  * out-of-memory), "device_mallocs" (hipMalloc calls of the arenas), "stream_syncs" (host waits on a
  * pipeline stream), "read_slow_rows" / "read_host_fallbacks" (aasm_paf_parse_device).  Unknown name: -1.                                                         */
 int64_t aasm_debug_counter(const char *name);
+/* Process-wide debug switch (tests): 0 = off (production); 1..255 = the byte every allocator of device working memory fills
+ * fresh memory with: the whole workspace arena at the start of each aasm_solve_device (and a block created during it), each
+ * block of the generic graph entries (aasm_sssp_*, aasm_k_shortest_walks, the debug entries) and of the device reader.  A
+ * kernel that reads a cell nobody wrote then meets the byte, not what the last tenant left.  Not filled: the scans' ticket /
+ * tile words, pinned buffers, the rows' persistent words, aasm_upload memory.  Returns the previous value; -1 (nothing
+ * changed) for a value outside 0..255.  Needs no device.                                                               */
+int aasm_debug_poison(int byte);
 /* Test entry for row T1: the device's PafDistance predicates (paf_data.hpp:142-168) on n pairs of
  * {qry, ref, anom, qul_nonzero, qul_total} tuples.  out[i] bit 0: a < b in CALC_SUM mode, bit 1: a < b in
  * QRY_SCORE mode, bit 2: a == b, bit 3: K7's node-key test, bit 4: K8's queue order (equal node / index), bit 5: the

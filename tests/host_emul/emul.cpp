@@ -31,7 +31,7 @@ struct EmuBackend {
     void *alloc(const char *name, size_t bytes) {
         void *p = malloc(bytes + 64);
         if (!p) { fail = true; return nullptr; }
-        memset(p, 0xA5, bytes + 64);               // poison: catches reads of never-written cells
+        memset(p, 0xA5, bytes + 64);               // poison: catches reads of never-written cells (on the card: aasm_debug_poison fills the allocators' memory, tests/test_gpu_poison.py)
         blocks.push_back(p);
         named[name] = {p, bytes};
         return p;

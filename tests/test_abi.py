@@ -99,6 +99,25 @@ def test_hook_constants_match_header():
     assert hdr == _abi.HOOK_CONSTANTS
 
 
+def test_debug_poison_switch(T):
+    """aasm_debug_poison: declared in the header, bound in _abi.py / api.py, off by default; it returns the previous value, and
+    -1 - changing nothing - for a value outside 0..255.  No device is touched."""
+    from alignasm_amd import _abi
+    api = T.api()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "alignasm_amd.h")).read(), flags=re.S)
+    assert re.search(r"\bint\s+aasm_debug_poison\s*\(\s*int\s+byte\s*\)\s*;", src)
+    assert "aasm_debug_poison" in api.EXPORTED
+    assert (api.LIB.aasm_debug_poison.restype, api.LIB.aasm_debug_poison.argtypes) == _abi.DEBUG_POISON_SIG == (C.c_int, [C.c_int])
+    try:
+        assert api.debug_poison(0xA5) == 0                           # off by default
+        assert api.debug_poison(256) == -1 and api.debug_poison(-1) == -1
+        assert api.debug_poison(0xFF) == 0xA5                        # ... and nothing was changed by those two
+        assert api.debug_poison(1 << 20) == -1 and api.debug_poison(0) == 0xFF
+        assert api.debug_poison(0) == 0
+    finally:
+        api.debug_poison(0)
+
+
 def test_hook_encoder_rejects_unknown_hooks_and_values(T):
     """make_opts packs hooks by name; an unknown name is a TypeError, an unknown value a ValueError, at every entry point."""
     import types
