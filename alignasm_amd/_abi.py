@@ -16,6 +16,8 @@ AASM_E_OVERFLOW, AASM_E_INTERNAL, AASM_E_PARSE, AASM_E_IO = -5, -6, -7, -8
 
 # reader flags (aasm_paf_read_opts, aasm_paf_parse_device); AASM_READ_H_*: test hooks of the device reader, 0 in production
 AASM_READ_DEVICE_RANGES, AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS = 1, 0x100, 0x200
+# aasm_paf_parse_device_rows: the row columns stay resident (implied by the entry); text is device memory
+AASM_READ_ROW_COLS, AASM_READ_TEXT_ON_DEVICE = 2, 4
 
 # int aasm_debug_poison(int byte): (restype, argtypes); 0 = off, 1..255 = the allocators' fill byte, -1 for anything else
 DEBUG_POISON_SIG = (C.c_int, [C.c_int])

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
                    DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,6 +72,11 @@ def _load():
     lib.aasm_paf_parse_device.restype = C.c_int
     lib.aasm_paf_read_device.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.aasm_paf_read_device.restype = C.c_int
+    # ... with the row columns: one more pointer, aasm_row_cols *; text may be a device address (c_void_p takes bytes and ints)
+    lib.aasm_paf_parse_device_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aasm_paf_parse_device_rows.restype = C.c_int
+    lib.aasm_paf_read_device_rows.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aasm_paf_read_device_rows.restype = C.c_int
     return lib
 
 
@@ -84,7 +89,7 @@ EXPORTED = [
     "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_poison", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
-    "aasm_paf_parse_device", "aasm_paf_read_device",
+    "aasm_paf_parse_device", "aasm_paf_read_device", "aasm_paf_parse_device_rows", "aasm_paf_read_device_rows",
     "aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device",
 ]
 
@@ -151,7 +156,7 @@ def sssp_dial(g_voff, rowptr, col, cost, src, lim=2, device=0):
 
 
 def debug_counter(name):
-    """Process-wide diagnostic counter: "range_splits", "device_mallocs", "stream_syncs", "read_slow_rows", "read_host_fallbacks"."""
+    """Process-wide diagnostic counter: "range_splits", "device_mallocs", "stream_syncs", "read_slow_rows", "read_host_fallbacks", "read_containers"."""
     return int(LIB.aasm_debug_counter(name.encode()))
 
 
@@ -203,18 +208,24 @@ class Paf:
         return Paf(h)
 
     @staticmethod
-    def parse_device(text: bytes, device=0, _flags=0):
+    def parse_device(text: bytes, device=0, _flags=0, container=True):
         """The device reader (aasm_paf_parse_device): PAF text in host memory -> (Paf, DeviceBatch).  The rows are framed and parsed
         on the GPU; the batch is resident in its cs form, as DeviceBatch(Paf.parse(text, device_ranges=True)) would leave it, and
-        the Paf equals that parse.  _flags: AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS (tests)."""
+        the Paf equals that parse.  _flags: AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS (tests).
+        container=False (aasm_paf_parse_device_rows without a container): -> (None, DeviceBatch); the batch carries its row columns
+        and names on the device (row_cols()), so to_torch(cuts=db, rows=True) and db.write_outputs work without a Paf."""
+        if not container:
+            return None, DeviceBatch._read_rows(lambda *out: LIB.aasm_paf_parse_device_rows(C.cast(C.c_char_p(text), C.c_void_p), len(text), int(_flags), int(device), None, *out), device)
         h, up, view = C.c_void_p(), C.c_void_p(), BatchIn()
         _check(LIB.aasm_paf_parse_device(text, len(text), int(_flags), int(device), C.byref(h), C.byref(up), C.byref(view)))
         paf = Paf(h)
         return paf, DeviceBatch._from_upload(up, view, device, paf)
 
     @staticmethod
-    def read_device(path, device=0, _flags=0):
-        """parse_device on a file (aasm_paf_read_device: the file is mapped, not copied)."""
+    def read_device(path, device=0, _flags=0, container=True):
+        """parse_device on a file (aasm_paf_read_device / aasm_paf_read_device_rows: the file is mapped, not copied)."""
+        if not container:
+            return None, DeviceBatch._read_rows(lambda *out: LIB.aasm_paf_read_device_rows(os.fsencode(path), int(_flags), int(device), None, *out), device)
         h, up, view = C.c_void_p(), C.c_void_p(), BatchIn()
         _check(LIB.aasm_paf_read_device(os.fsencode(path), int(_flags), int(device), C.byref(h), C.byref(up), C.byref(view)))
         paf = Paf(h)
@@ -270,22 +281,7 @@ class Paf:
         """The three output files with the rows formatted on the device (aasm_writer_append_device).  db: the DeviceBatch of this
         container (its tags on the device); res: a DeviceResult solved from it, or the dict of its to_torch(cuts=db).  Errors as
         write_outputs: a row that cannot be formatted raises with the host codec's code and message and leaves no file behind."""
-        d = res if isinstance(res, dict) else res.to_torch(cuts=db)
-        if "main_cut" not in d:
-            raise AlignasmError(AASM_E_INVAL, "write_outputs_device: the result dict holds no cut plans (to_torch(cuts=...))")
-        sizes, dst, dc = _dev_structs(d)
-        cols = db.row_cols()
-        w = C.c_void_p()
-        _check(LIB.aasm_writer_open(os.fsencode(main_path), os.fsencode(alt_path), os.fsencode(all_path), C.byref(w)))
-        import torch
-        torch.cuda.synchronize(db.device)                            # (the writer runs on the library's own streams)
-        rc = LIB.aasm_writer_append_device(w, self._h, C.byref(db.dev_view), C.byref(cols), C.byref(sizes), C.byref(dst), C.byref(dc), C.c_int64(0),
-                                           C.c_int64(int(piece_bytes)), int(db.device))
-        msg = (LIB.aasm_last_error() or b"").decode(errors="replace")
-        rc2 = LIB.aasm_writer_close(w, 1 if rc == AASM_OK else 0)     # (a failed append leaves no file behind)
-        if rc != AASM_OK:
-            raise AlignasmError(rc, msg)
-        _check(rc2)
+        _write_outputs_device(self, db, res, main_path, alt_path, all_path, piece_bytes)
 
     def close(self):
         if self._h:
@@ -297,6 +293,26 @@ class Paf:
             self.close()
         except Exception:
             pass
+
+
+def _write_outputs_device(paf, db, res, main_path, alt_path, all_path, piece_bytes):
+    """aasm_writer_append_device in a session of its own; paf: the container, or None for a batch that has none."""
+    d = res if isinstance(res, dict) else res.to_torch(cuts=db)
+    if "main_cut" not in d:
+        raise AlignasmError(AASM_E_INVAL, "write_outputs_device: the result dict holds no cut plans (to_torch(cuts=...))")
+    sizes, dst, dc = _dev_structs(d)
+    cols = db.row_cols()
+    w = C.c_void_p()
+    _check(LIB.aasm_writer_open(os.fsencode(main_path), os.fsencode(alt_path), os.fsencode(all_path), C.byref(w)))
+    import torch
+    torch.cuda.synchronize(db.device)                                # (the writer runs on the library's own streams)
+    rc = LIB.aasm_writer_append_device(w, paf._h if paf is not None else None, C.byref(db.dev_view), C.byref(cols), C.byref(sizes), C.byref(dst), C.byref(dc),
+                                       C.c_int64(0), C.c_int64(int(piece_bytes)), int(db.device))
+    msg = (LIB.aasm_last_error() or b"").decode(errors="replace")
+    rc2 = LIB.aasm_writer_close(w, 1 if rc == AASM_OK else 0)         # (a failed append leaves no file behind)
+    if rc != AASM_OK:
+        raise AlignasmError(rc, msg)
+    _check(rc2)
 
 
 def solve_batch_raw(view: BatchIn, opts: Opts) -> BatchOut:
@@ -353,6 +369,39 @@ class DeviceBatch:
         self.n_contigs, self.n_records = int(dev_view.n_contigs), int(dev_view.n_records)
         return self
 
+    @classmethod
+    def _read_rows(cls, call, device):
+        """A batch read by aasm_paf_*_device_rows without a container: call(up, view, cols) -> code.  One handle owns the batch's
+        arrays and the row columns'."""
+        up, view, cols = C.c_void_p(), BatchIn(), RowCols()
+        _check(call(C.byref(up), C.byref(view), C.byref(cols)))
+        self = cls._from_upload(up, view, device)
+        self._row_cols = cols
+        return self
+
+    @classmethod
+    def from_device_text(cls, tensor, _flags=0):
+        """PAF text that is already on the device -> a resident batch with its row columns (aasm_paf_parse_device_rows with
+        AASM_READ_TEXT_ON_DEVICE, no container).  tensor: a 1-D contiguous uint8 torch tensor on a GPU whose first byte is 16-byte
+        aligned; it is neither copied nor written, and may be freed after the call.  The tensor's current stream is waited for
+        first: what was enqueued there to write the text has finished before the reader looks at it."""
+        import torch
+        _check_one_hip_runtime()
+        if tensor.dtype != torch.uint8 or tensor.dim() != 1 or not tensor.is_cuda or not tensor.is_contiguous():
+            raise AlignasmError(AASM_E_INVAL, "from_device_text: a 1-D contiguous uint8 tensor on the device is needed")
+        device = tensor.device.index if tensor.device.index is not None else torch.cuda.current_device()
+        torch.cuda.current_stream(device).synchronize()
+        n = int(tensor.numel())
+        return cls._read_rows(lambda *out: LIB.aasm_paf_parse_device_rows(C.c_void_p(tensor.data_ptr() if n else 0), n, int(_flags) | AASM_READ_TEXT_ON_DEVICE,
+                                                                          int(device), None, *out), device)
+
+    def write_outputs(self, res, main_path, alt_path, all_path, piece_bytes=0):
+        """The three output files from a batch that has no container (parse_device(container=False), from_device_text): the rows
+        are formatted on the device (aasm_writer_append_device with paf = NULL).  res: a DeviceResult solved from this batch, or the
+        dict of its to_torch(cuts=self).  A row that cannot be formatted raises AASM_E_PARSE / AASM_E_INVAL with
+        rows_flagged_error's message and leaves no file behind."""
+        _write_outputs_device(None, self, res, main_path, alt_path, all_path, piece_bytes)
+
     def solve(self, max_paths=10000, non_skip_linkable=False, timing=False, keep_debug=False, stream=None, **hooks):
         """hooks: _abi.HOOKS, except the two aasm_solve_device never reads (the range limit, device wrap)."""
         for name in ("test_max_contigs", "wrap_devices"):
@@ -364,8 +413,8 @@ class DeviceBatch:
         return DeviceResult(res, self.device)
 
     def row_cols(self) -> RowCols:
-        """What an output row prints beyond the batch (aasm_paf_upload_rows), uploaded once from the Paf the batch was made from
-        and freed with the batch."""
+        """What an output row prints beyond the batch: resident already where the device reader left it (container=False,
+        from_device_text), else uploaded once from the Paf the batch was made from (aasm_paf_upload_rows) and freed with the batch."""
         if getattr(self, "_row_cols", None) is None:
             if not isinstance(self._keep, Paf):
                 raise AlignasmError(AASM_E_INVAL, "row_cols: the batch was not made from a Paf (names and row columns are the container's)")

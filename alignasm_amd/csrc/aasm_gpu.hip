@@ -16,6 +16,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <fcntl.h>
@@ -329,7 +330,7 @@ static void drain_exports(DevCtx &cx) {
 }
 static DevCtx g_ctx[16];
 static std::mutex g_init_mu;
-static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0}, g_n_read_slow_rows{0}, g_n_read_fallbacks{0};
+static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0}, g_n_read_slow_rows{0}, g_n_read_fallbacks{0}, g_n_read_containers{0};
 
 // aasm_debug_poison: 0 = off (production), 1..255 = the byte the three allocators below fill fresh working memory with, so that
 // a kernel reading a cell nobody wrote meets it instead of a harmless left-over.  Left alone: the scans' ticket / tile words
@@ -1053,6 +1054,7 @@ int64_t aasm_debug_counter(const char *name) {
     if (n == "stream_syncs") return g_n_stream_syncs.load();
     if (n == "read_slow_rows") return g_n_read_slow_rows.load();
     if (n == "read_host_fallbacks") return g_n_read_fallbacks.load();
+    if (n == "read_containers") return g_n_read_containers.load();
     return -1;
 }
 
@@ -1213,12 +1215,33 @@ struct ReadGpu {
 };
 }  // namespace
 
-int aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view) {
+// the text of a device read that failed, for the host reader's verdict: host text as it is, device text copied back once
+static int read_verdict(const char *text, int64_t len, bool on_dev, int device) {
+    if (!on_dev || len == 0) return read_host_verdict(on_dev ? "" : text, len);
+    std::string host;
+    try { host.resize((size_t)len); } catch (...) { set_last_error("out of host memory (device reader)"); return AASM_E_NOMEM; }
+    hipSetDevice(device);
+    const hipError_t e = hipMemcpy(&host[0], text, (size_t)len, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_last_error(hip_err("device reader", e)); return AASM_E_HIP; }
+    return read_host_verdict(host.data(), len);
+}
+
+// aasm_paf_parse_device (dev_cols = nullptr) and aasm_paf_parse_device_rows
+static int parse_device(const char *entry, const char *text, int64_t len, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view,
+                        aasm_row_cols *dev_cols) {
     if (paf_out) *paf_out = nullptr;
     if (up_out) *up_out = nullptr;
-    if (!text || len < 0 || (up_out == nullptr) != (dev_view == nullptr) || (!paf_out && !up_out)) { set_last_error("aasm_paf_parse_device: bad argument"); return AASM_E_INVAL; }
+    const bool on_dev = (flags & AASM_READ_TEXT_ON_DEVICE) != 0;
+    if ((!text && !(on_dev && len == 0)) || len < 0 || (up_out == nullptr) != (dev_view == nullptr) || (!paf_out && !up_out) || (on_dev && paf_out)) {
+        set_last_error(std::string(entry) + ": bad argument");
+        return AASM_E_INVAL;
+    }
     int rc = ctx_init(device);
     if (rc != AASM_OK) return rc;
+    if (on_dev && len > 0) {
+        hipSetDevice(device);
+        if (!dev_buffer_ok(text, len, 16, device)) { set_last_error(std::string(entry) + ": text is not device memory of the device, or not 16-byte aligned"); return AASM_E_INVAL; }
+    }
     DevCtx &cx = g_ctx[device];
     aasm_paf *paf = paf_out ? new aasm_paf() : nullptr;
     ReadOut o;
@@ -1245,23 +1268,46 @@ int aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, 
             v.n_contigs = o.C; v.n_records = o.R; v.n_ranges = o.n_ranges;
             v.ctg_rec_off = o.ctg_rec_off; v.qry_str = o.qry_str; v.qry_end = o.qry_end; v.ref_str = o.ref_str; v.ref_end = o.ref_end; v.qry_total = o.qry_total;
             v.ref_chr = o.ref_chr; v.aln_fwd = o.aln_fwd; v.map_qul = o.map_qul; v.rec_rng_off = o.rec_rng_off; v.cs_text = o.cs_text; v.rec_cs_off = o.rec_cs_off;
+            if (dev_cols) {                                         // (the same handle owns the columns' arrays)
+                for (void *p : {(void *)o.ref_total, (void *)o.mat_num, (void *)o.aln_len, (void *)o.row_index, (void *)o.cord_type, (void *)o.names, (void *)o.ctg_name_off, (void *)o.chr_name_off})
+                    up->ptrs.push_back(p);
+                dev_cols->n_chr = o.n_chr; dev_cols->ref_total = o.ref_total; dev_cols->mat_num = o.mat_num; dev_cols->aln_len = o.aln_len;
+                dev_cols->row_index = o.row_index; dev_cols->cord_type = o.cord_type; dev_cols->names = o.names;
+                dev_cols->ctg_name_off = o.ctg_name_off; dev_cols->chr_name_off = o.chr_name_off;
+            }
             *dev_view = v;
             *up_out = up;
         }
     }
     if (rc == AASM_OK) {
         g_n_read_slow_rows.store(o.slow_rows);
-        if (paf_out) *paf_out = paf;
+        if (paf_out) { *paf_out = paf; g_n_read_containers++; }
         return AASM_OK;
     }
     delete paf;
-    if (rc < 0) { set_last_error("aasm_paf_parse_device: " + why); return rc; }
+    if (rc < 0) { set_last_error(std::string(entry) + ": " + why); return rc; }
     // a text the device does not take: not a hot path, and the host reader's code and message are the contract
     g_n_read_fallbacks++;
-    return read_host_verdict(text, len);
+    return read_verdict(text, len, on_dev, device);
 }
 
-int aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view) {
+int aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view) {
+    return parse_device("aasm_paf_parse_device", text, len, flags & ~(AASM_READ_ROW_COLS | AASM_READ_TEXT_ON_DEVICE), device, paf_out, up_out, dev_view, nullptr);
+}
+
+int aasm_paf_parse_device_rows(const char *text, int64_t len, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view,
+                               aasm_row_cols *dev_cols) {
+    if (!up_out || !dev_view || !dev_cols) {
+        if (paf_out) *paf_out = nullptr;
+        if (up_out) *up_out = nullptr;
+        set_last_error("aasm_paf_parse_device_rows: bad argument");
+        return AASM_E_INVAL;
+    }
+    return parse_device("aasm_paf_parse_device_rows", text, len, flags | AASM_READ_ROW_COLS, device, paf_out, up_out, dev_view, dev_cols);
+}
+
+// a file's bytes, mapped (or read into memory where it is no regular file), through parse(text, len)
+static int with_file_text(const char *path, const std::function<int(const char *, int64_t)> &parse) {
     if (!path) return AASM_E_INVAL;
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) { set_last_error(std::string("cannot open ") + path); return AASM_E_IO; }
@@ -1272,16 +1318,26 @@ int aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf
         ssize_t n;
         while ((n = ::read(fd, buf, sizeof buf)) > 0) data.append(buf, (size_t)n);
         ::close(fd);
-        return aasm_paf_parse_device(data.data(), (int64_t)data.size(), flags, device, paf_out, up_out, dev_view);
+        return parse(data.data(), (int64_t)data.size());
     }
-    if (st.st_size == 0) { ::close(fd); return aasm_paf_parse_device("", 0, flags, device, paf_out, up_out, dev_view); }
+    if (st.st_size == 0) { ::close(fd); return parse("", 0); }
     void *m = ::mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
     ::close(fd);
     if (m == MAP_FAILED) { set_last_error(std::string("cannot map ") + path); return AASM_E_IO; }
     ::madvise(m, (size_t)st.st_size, MADV_WILLNEED);
-    const int rc = aasm_paf_parse_device((const char *)m, (int64_t)st.st_size, flags, device, paf_out, up_out, dev_view);
+    const int rc = parse((const char *)m, (int64_t)st.st_size);
     ::munmap(m, (size_t)st.st_size);
     return rc;
+}
+
+int aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view) {
+    return with_file_text(path, [&](const char *text, int64_t len) { return aasm_paf_parse_device(text, len, flags, device, paf_out, up_out, dev_view); });
+}
+
+int aasm_paf_read_device_rows(const char *path, int flags, int device, aasm_paf **paf_out, aasm_upload **up_out, aasm_batch_in *dev_view, aasm_row_cols *dev_cols) {
+    return with_file_text(path, [&](const char *text, int64_t len) {
+        return aasm_paf_parse_device_rows(text, len, flags & ~AASM_READ_TEXT_ON_DEVICE, device, paf_out, up_out, dev_view, dev_cols);
+    });
 }
 
 // ---- output rows on the device (aasm_rows.h) ----------------------------------------------------------------------------------
@@ -1456,8 +1512,8 @@ struct RowsOffFetch {
 
 int aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const aasm_out_sizes *sz,
                               const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts, int64_t contig0, int64_t piece_bytes, int device) {
-    if (!w || !paf || !sz || piece_bytes < 0) return AASM_E_INVAL;
-    int rc = writer_device_begin(w, paf, contig0, sz->n_contigs);
+    if (!w || !sz || piece_bytes < 0 || (!paf && !dev_in)) return AASM_E_INVAL;
+    int rc = writer_device_begin(w, paf, contig0, sz->n_contigs, paf ? paf->has_cs : dev_in->cs_text != nullptr);
     if (rc != AASM_OK) return rc;
     RowsArgs a;
     aasm_dev_rows ro = {nullptr, nullptr, nullptr};
@@ -1487,6 +1543,18 @@ int aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_ba
     aasm_rows_info info;
     if ((rc = rows_sizes_locked(cx, a, 0, device, cx.stream, &info)) != AASM_OK) { cleanup(); if (rc == AASM_E_NOMEM) return rc; writer_device_end(w, sz->n_contigs, rc); return rc; }
     const int64_t C = a.c.C;
+    if (info.n_flagged != 0 && !paf) {
+        // no container, no host codec to ask: the count and the first element's list, index and flags
+        static const char *const lists[3] = {"main", "alt", "all"};
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "%lld output elements cannot be formatted; the first: list %s, element %lld, flags 0x%x", (long long)info.n_flagged,
+                      lists[info.bad_list >= 0 && info.bad_list < 3 ? info.bad_list : 0], (long long)info.bad_elem, (unsigned)info.bad_flags);
+        cleanup();
+        rc = (info.bad_flags & (AASM_ROWS_CUT_ERRORS & ~AASM_CUT_E_RECORD)) ? AASM_E_PARSE : AASM_E_INVAL;
+        set_last_error(msg);
+        writer_device_end(w, sz->n_contigs, rc);
+        return rc;
+    }
     if (info.n_flagged != 0) {
         // the first element that cannot be formatted, through the planned writer's own check: its code and message are the contract
         const int l = info.bad_list;

@@ -1146,9 +1146,9 @@ static int writer_append(aasm_writer *w, const aasm_paf *paf, const aasm_batch_o
 
 // ---- the device writer's hooks (aasm_paf.hpp) ----
 namespace aasm {
-int writer_device_begin(aasm_writer *w, const aasm_paf *paf, int64_t contig0, int64_t n_contigs) {
-    if (!w || !paf || n_contigs < 0 || contig0 != w->next_contig || contig0 + n_contigs > paf->n_contigs()) return AASM_E_INVAL;
-    if (!paf->has_cs) { set_last_error("PAF was generated without cs strings"); return AASM_E_INVAL; }
+int writer_device_begin(aasm_writer *w, const aasm_paf *paf, int64_t contig0, int64_t n_contigs, bool has_cs) {
+    if (!w || n_contigs < 0 || contig0 != w->next_contig || (paf && contig0 + n_contigs > paf->n_contigs())) return AASM_E_INVAL;
+    if (!has_cs) { set_last_error("PAF was generated without cs strings"); return AASM_E_INVAL; }
     return w->failed ? AASM_E_IO : AASM_OK;
 }
 bool writer_device_has(const aasm_writer *w, int file) { return file >= 0 && file < 3 && w->fd[file] >= 0; }

@@ -67,7 +67,7 @@ bool read_slow_row(const char *s, const char *e, ReadRowCols &out);
 // begin: aasm_writer_append's argument and session checks for contigs [contig0, contig0 + n_contigs), nothing changed;
 // has: file i of the session is open;  put: append these bytes to file i of the session;  end: the range is done with rc (a
 // failure marks the session failed);  row_verdict: emit_line's code and message for one element and its plan (0: it formats).
-int writer_device_begin(aasm_writer *w, const aasm_paf *paf, int64_t contig0, int64_t n_contigs);
+int writer_device_begin(aasm_writer *w, const aasm_paf *paf /* or nullptr: no container */, int64_t contig0, int64_t n_contigs, bool has_cs);
 bool writer_device_has(const aasm_writer *w, int file);
 int writer_device_put(aasm_writer *w, int file, const char *bytes, int64_t n);
 void writer_device_end(aasm_writer *w, int64_t n_contigs, int rc);

@@ -18,6 +18,9 @@
 //   ref ids     the table's entries, a few, are listed, ordered by first row on the host and numbered; every row looks its
 //               name up and takes the number: chr_map's first-appearance order (alignasm.cpp:119-123).
 //   pack        tag lengths scanned into rec_cs_off, ':' counts into rec_rng_off; sixteen lanes per tag copy it into cs_text.
+//   row columns (AASM_READ_ROW_COLS) what an output row prints beyond the batch stays resident as aasm_row_cols: the three numeric
+//               columns as parsed, row_index / cord_type, and `names` - contig-name lengths scanned into ctg_name_off, the
+//               reference names' offsets made on the host from the few table entries, sixteen lanes per name copying it.
 // No load touches a byte outside [0, len): wide loads are taken only where their bytes are inside the text.
 // The driver (read_run) is shared by the product backend (aasm_gpu.hip) and the 1-lane host emulation (tests/host_emul/read_emul.cpp).
 #pragma once
@@ -63,6 +66,14 @@ struct ReadArgs {
     const int32_t *chr_sorted;           // [n_chr] the entries' first rows, ascending
     const int64_t *cs_off;               // [R + 1]
     char *cs_text;
+    // AASM_READ_ROW_COLS
+    int64_t C;
+    const int64_t *ctg_name_off;         // [C + 1] into names
+    const int64_t *chr_name_off;         // [n_chr + 1] into names, chr_name_off[0] = ctg_name_off[C]
+    const int64_t *chr_pos;              // [n_chr] the reference names in the text, in first-appearance order
+    char *names;
+    int32_t *row_index;                  // [R]
+    uint8_t *cord_type;                  // [R]
 };
 
 // the row starts among the bytes [o, o + 16) of the text, bit t for byte o + t (o a multiple of 16, o < len)
@@ -283,6 +294,24 @@ AASM_DEV void kb_read_pack(const KCtx &k, const ReadArgs &a) {
         for (int64_t o = (n & ~(int64_t)7) + gl; o < n; o += G) dst[o] = (char)src[o];
     }
 }
+// AASM_READ_PACK_LANES lanes per name, contig names first, then the reference names: kb_read_pack's steps.  A load lies inside its
+// name's span of the text, a store inside its span of `names`.
+AASM_DEV void kb_read_names(const KCtx &k, const ReadArgs &a) {
+    const int G = AASM_READ_PACK_LANES, gl = k.tid % G;
+    const int64_t per_block = k.nthreads / G, n_names = a.C + a.n_chr;
+    for (int64_t i = k.bid * per_block + k.tid / G; i < n_names; i += k.nblocks * per_block) {
+        const int64_t j = i - a.C;
+        const uint8_t *src = a.text + (j < 0 ? a.ctg_pos[i] : a.chr_pos[j]);
+        const int64_t d0 = j < 0 ? a.ctg_name_off[i] : a.chr_name_off[j], n = (j < 0 ? a.ctg_name_off[i + 1] : a.chr_name_off[j + 1]) - d0;
+        char *dst = a.names + d0;
+        for (int64_t o = (int64_t)gl * 8; o + 8 <= n; o += G * 8) read_copy8(dst + o, src + o);
+        for (int64_t o = (n & ~(int64_t)7) + gl; o < n; o += G) dst[o] = (char)src[o];
+    }
+}
+// row_index[r] = r, cord_type[r] = TYPE_MAIN: what the host reader's container holds before a --alt merge
+AASM_DEV void kb_read_row_ids(const KCtx &k, const ReadArgs &a) {
+    for (int64_t i = k.bid * k.nthreads + k.tid; i < a.R; i += k.nblocks * k.nthreads) { a.row_index[i] = (int32_t)i; a.cord_type[i] = 0; }
+}
 
 // The reader's kernels (row shapes: aasm_dev.h), body called as body(k, a).  One lane per block in the host emulation:
 // every body strides by k.nthreads, and a wave is one lane there.
@@ -294,7 +323,9 @@ AASM_DEV void kb_read_pack(const KCtx &k, const ReadArgs &a) {
     K(KR_GROUPS, aasm_read_groups, 256, 1, kb_read_groups) \
     K(KR_CHR_LIST, aasm_read_chr_list, 256, 1, kb_read_chr_list) \
     K(KR_REF_IDS, aasm_read_ref_ids, 256, 1, kb_read_ref_ids) \
-    K(KR_PACK, aasm_read_pack, 256, 1, kb_read_pack)
+    K(KR_PACK, aasm_read_pack, 256, 1, kb_read_pack) \
+    K(KR_NAMES, aasm_read_names, 256, 1, kb_read_names) \
+    K(KR_ROW_IDS, aasm_read_row_ids, 256, 1, kb_read_row_ids)
 enum ReadKern { AASM_READ_KERNELS(AASM_ROW_ID, AASM_ROW_ID) KR_N };
 constexpr int read_block[] = {AASM_READ_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
 AASM_KERNEL_BODY(run_read_body, AASM_READ_KERNELS, ReadArgs)
@@ -309,6 +340,12 @@ struct ReadOut {
     int32_t *ref_chr = nullptr;
     uint8_t *aln_fwd = nullptr, *map_qul = nullptr;
     char *cs_text = nullptr;
+    // AASM_READ_ROW_COLS (with want_dev): aasm_row_cols' arrays, rows_host_cols' layout (aasm_rows.h)
+    int64_t n_chr = 0, names_bytes = 0;
+    int64_t *ref_total = nullptr, *ctg_name_off = nullptr, *chr_name_off = nullptr;
+    int32_t *mat_num = nullptr, *aln_len = nullptr, *row_index = nullptr;
+    uint8_t *cord_type = nullptr;
+    char *names = nullptr;
 };
 #define AASM_READ_FALLBACK 1             // read_run: the text is no PAF the device takes; the host reader says why
 
@@ -318,7 +355,9 @@ struct ReadOut {
 //   h2d / d2h(dst, src, n)         d2h waits;   fill32(p, value, count)
 //   scan_i32 / scan_u8(in, n, out) exclusive scan into int64 out[n + 1]
 //   launch_read(kernel, blocks, threads, ReadArgs);   stage(name): a launch group's name, for timing;   bool ok()
-// text: HOST memory.  paf: the container to fill, or nullptr; want_dev: hand the batch's arrays out in `out` (else they are freed).
+// text: HOST memory; under AASM_READ_TEXT_ON_DEVICE device memory, 16-byte aligned, that is neither copied nor written (paf is
+// nullptr then: the container is cut from host text).  paf: the container to fill, or nullptr; want_dev: hand the batch's arrays out
+// in `out` (else they are freed), under AASM_READ_ROW_COLS the row columns' arrays with them.
 // Returns AASM_OK, AASM_READ_FALLBACK, or the backend's failure as AASM_E_NOMEM / AASM_E_HIP through be.code().
 template <class B> int read_run(B &be, const char *text, int64_t len, int flags, aasm_paf *paf, bool want_dev, ReadOut &out) {
     const int64_t max_blocks = (flags & AASM_READ_H_FEW_BLOCKS) ? 3 : AASM_READ_MAX_BLOCKS;   // (the hook: fewer blocks than items)
@@ -329,9 +368,11 @@ template <class B> int read_run(B &be, const char *text, int64_t len, int flags,
     ReadArgs a;
     std::memset(&a, 0, sizeof a);
     if (len <= 0) return AASM_READ_FALLBACK;
+    const bool on_dev = (flags & AASM_READ_TEXT_ON_DEVICE) != 0, row_cols = (flags & AASM_READ_ROW_COLS) != 0 && want_dev;
+    if (on_dev && paf) return AASM_E_INVAL;
     be.stage("upload");
-    uint8_t *d_text = u8s(len);
-    be.h2d(d_text, text, (size_t)len);
+    uint8_t *d_text = on_dev ? (uint8_t *)const_cast<char *>(text) : u8s(len);
+    if (!on_dev) be.h2d(d_text, text, (size_t)len);
     a.text = d_text; a.len = len; a.weak_hash = (flags & AASM_READ_H_WEAK_HASH) ? 1 : 0;
     // ---- row starts
     be.stage("row starts");
@@ -380,15 +421,25 @@ template <class B> int read_run(B &be, const char *text, int64_t len, int flags,
         std::vector<int64_t> starts;
         if (n_slow > 64) { starts.resize((size_t)R); be.d2h(starts.data(), a.row_start, (size_t)R * 8); }
         if (!be.ok()) return be.code();
+        std::vector<char> fetched;                                   // (device text: the row's bytes come back, up to the next row's start)
         for (int32_t r : rows) {
-            int64_t p = 0;
+            int64_t p = 0, p1 = len;
             if (starts.empty()) be.d2h(&p, a.row_start + r, 8); else p = starts[(size_t)r];
+            if (on_dev && r + 1 < R) { if (starts.empty()) be.d2h(&p1, a.row_start + r + 1, 8); else p1 = starts[(size_t)r + 1]; }
             if (!be.ok()) return be.code();
-            const char *nl = (const char *)std::memchr(text + p, '\n', (size_t)(len - p));
-            int64_t e = nl ? nl - text : len;
-            if (e > p && text[e - 1] == '\r') e--;
+            const char *row = on_dev ? nullptr : text + p;           // the row and what follows it: row[0, avail)
+            const int64_t avail = p1 - p;
+            if (on_dev) {
+                fetched.resize((size_t)avail);
+                be.d2h(fetched.data(), d_text + p, (size_t)avail);
+                if (!be.ok()) return be.code();
+                row = fetched.data();
+            }
+            const char *nl = (const char *)std::memchr(row, '\n', (size_t)avail);
+            int64_t e = nl ? nl - row : avail;
+            if (e > 0 && row[e - 1] == '\r') e--;
             ReadRowCols w;
-            if (!read_slow_row(text + p, text + e, w)) return AASM_READ_FALLBACK;   // ROW_NUMBER: the host reader names the first one
+            if (!read_slow_row(row, row + e, w)) return AASM_READ_FALLBACK;   // ROW_NUMBER: the host reader names the first one
             be.h2d(a.qs + r, &w.qry_str, 8); be.h2d(a.qe + r, &w.qry_end, 8); be.h2d(a.rs + r, &w.ref_str, 8); be.h2d(a.re + r, &w.ref_end, 8);
             be.h2d(a.qtot + r, &w.qry_total, 8); be.h2d(a.rtot + r, &w.ref_total, 8); be.h2d(a.mat + r, &w.mat_num, 4); be.h2d(a.aln + r, &w.aln_len, 4);
             be.h2d(a.mq + r, &w.map_qul, 1);
@@ -424,7 +475,28 @@ template <class B> int read_run(B &be, const char *text, int64_t len, int flags,
     be.stage("pack");
     a.cs_text = (char *)u8s(cs_bytes);
     be.launch_read(KR_PACK, blocks_for(R, read_block[KR_PACK] / AASM_READ_PACK_LANES), read_block[KR_PACK], a);
-    be.release(d_text);                                              // (waits for the launches; nothing reads the raw text on the device any more)
+    // ---- the row columns: names back to back (contigs, then references by first appearance), row_index, cord_type
+    int64_t *ctg_name_off = nullptr, *chr_name_off = nullptr;
+    int64_t names_bytes = 0;
+    if (row_cols) {
+        be.stage("names");
+        ctg_name_off = i64s(C + 1); chr_name_off = i64s(n_chr + 1);
+        int64_t *chr_pos = i64s(n_chr);
+        be.scan_i32(a.ctg_len, C, ctg_name_off);
+        int64_t ctg_bytes = 0;
+        be.d2h(&ctg_bytes, ctg_name_off + C, 8);
+        if (!be.ok()) return be.code();
+        std::vector<int64_t> off((size_t)n_chr + 1, ctg_bytes), pos((size_t)n_chr);
+        for (int64_t j = 0; j < n_chr; j++) { pos[(size_t)j] = info[(size_t)order[(size_t)j] * 3 + 1]; off[(size_t)j + 1] = off[(size_t)j] + info[(size_t)order[(size_t)j] * 3 + 2]; }
+        names_bytes = off[(size_t)n_chr];
+        be.h2d(chr_name_off, off.data(), off.size() * 8); be.h2d(chr_pos, pos.data(), pos.size() * 8);
+        a.C = C; a.ctg_name_off = ctg_name_off; a.chr_name_off = chr_name_off; a.chr_pos = chr_pos;
+        a.names = (char *)u8s(names_bytes); a.row_index = i32s(R); a.cord_type = u8s(R);
+        be.launch_read(KR_NAMES, blocks_for(C + n_chr, read_block[KR_NAMES] / AASM_READ_PACK_LANES), read_block[KR_NAMES], a);
+        be.launch_read(KR_ROW_IDS, blocks_for(R, read_block[KR_ROW_IDS]), read_block[KR_ROW_IDS], a);
+    }
+    if (on_dev) { int64_t w = 0; be.d2h(&w, cs_off, 8); }             // (the caller's text: nothing is released, the launches are waited for)
+    else be.release(d_text);                                              // (waits for the launches; nothing reads the raw text on the device any more)
     be.stage("container");
     if (!be.ok()) return be.code();
     // ---- the writers' container: columns and offsets from the device, names and tags from the host's own text
@@ -469,6 +541,13 @@ template <class B> int read_run(B &be, const char *text, int64_t len, int flags,
         for (void *p : {(void *)a.ctg_rec_off, (void *)a.qs, (void *)a.qe, (void *)a.rs, (void *)a.re, (void *)a.qtot, (void *)rng_off, (void *)cs_off,
                         (void *)a.ref_chr, (void *)a.fwd, (void *)a.mq, (void *)a.cs_text})
             be.keep(p);
+        if (row_cols) {
+            out.n_chr = n_chr; out.names_bytes = names_bytes;
+            out.ref_total = a.rtot; out.mat_num = a.mat; out.aln_len = a.aln; out.row_index = a.row_index; out.cord_type = a.cord_type;
+            out.names = a.names; out.ctg_name_off = ctg_name_off; out.chr_name_off = chr_name_off;
+            for (void *p : {(void *)a.rtot, (void *)a.mat, (void *)a.aln, (void *)a.row_index, (void *)a.cord_type, (void *)a.names, (void *)ctg_name_off, (void *)chr_name_off})
+                be.keep(p);
+        }
     }
     be.stage("free");
     return be.ok() ? AASM_OK : be.code();

@@ -8,6 +8,10 @@
 // the per-contig parallelism the reference drives with it now lives on the GPU.
 // --timing prints the wall time of read / solve / write to stderr.
 // --device-writer formats the output rows on the GPU (export -> cut plans -> aasm_writer_append_device); the files are the same.
+// --device-reader --device-writer together (no --alt, one GPU) build no container at all: aasm_paf_read_device_rows leaves batch, row
+// columns and names resident, and the writer runs without one.  Anything on that way short of a HIP error - a text the device
+// rejects, out of device memory, a malformed tag, a row that cannot be formatted - reads the file with the host reader and goes on
+// as the command without the two flags does, with its messages and exit codes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -110,32 +114,111 @@ int main(int argc, char **argv) {
         for (int g = 0; g < (gpus > 0 ? gpus : 1); g++) warm.emplace_back([=] { (void)aasm_reserve_workspace(opts.device + g, per_gpu); });
     }
     aasm_paf *paf = nullptr;
-    // the reader only indexes the rows; the cs tags are turned into match ranges on the GPU
-    // --device-reader: the rows are framed and parsed on the GPU, which leaves the batch resident (up, dev_view) beside the container
     aasm_upload *up = nullptr;
-    aasm_batch_in dev_view;
-    int rc = device_reader ? aasm_paf_read_device(std::filesystem::absolute(p).c_str(), 0, opts.device, &paf, &up, &dev_view)
-                           : aasm_paf_read_opts(std::filesystem::absolute(p).c_str(), host_ranges ? 0 : AASM_READ_DEVICE_RANGES, &paf);
-    if (rc != AASM_OK && device_reader && rc != AASM_E_PARSE && rc != AASM_E_IO) { std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; return 2; }
-    if (rc != AASM_OK) { std::cerr << aasm_last_error() << "\n"; return 1; }    // e.g. "Missing cs:Z tag ..." (:165-168)
-    if (up && (use_alt || gpus > 1)) { aasm_upload_free(up); up = nullptr; }    // the merge changes the records, shards are uploaded per GPU: on from the container
-    if (use_alt) {
-        rc = aasm_paf_merge_alt(paf, std::filesystem::absolute(alt_loc).c_str(), alt_baseline);
-        if (rc != AASM_OK) { std::cerr << aasm_last_error() << "\n"; aasm_paf_free(paf); return 1; }
-    }
-    std::cout << "File read complete" << std::endl;                              // :340
-    aasm_batch_in view;
-    aasm_paf_batch(paf, &view);
-    std::cout << "Analyze PAF " << view.n_contigs << " data in parallel" << std::endl;   // :349
-    const auto t1 = clk::now();                                                 // (the warm-up threads are not waited for: the upload runs beside them, the solve takes the context's lock after them)
+    aasm_batch_in dev_view, view;
+    std::memset(&view, 0, sizeof view);
     auto ap = std::filesystem::absolute(p);
     auto f_main = ap; f_main.replace_extension(".aln.paf");
     auto f_alt = ap; f_alt.replace_extension(".aln.alt.paf");
     auto f_all = ap; f_all.replace_extension(".aln.all.paf");
     double upload_s = 0, device_s = 0, fetch_s = 0, solve_busy_s = 0, write_busy_s = 0;
     int64_t n_internal = 0;
-    clk::time_point t2 = t1;
-    bool done = false;
+    clk::time_point t1 = t0, t2 = t0;
+    bool done = false, said_read = false;
+    int rc = AASM_OK, container = 1;
+    if (device_reader && device_writer && !use_alt && gpus <= 1) {
+        // ---- no container: read -> solve -> sizes -> export -> cut plans -> device writer, all from resident arrays
+        aasm_row_cols cols;
+        rc = aasm_paf_read_device_rows(ap.c_str(), 0, opts.device, nullptr, &up, &dev_view, &cols);
+        if (rc != AASM_OK && rc != AASM_E_PARSE && rc != AASM_E_IO && rc != AASM_E_NOMEM) { std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; return 2; }
+        if (rc == AASM_OK) {
+            std::cout << "File read complete" << std::endl;                      // :340
+            std::cout << "Analyze PAF " << dev_view.n_contigs << " data in parallel" << std::endl;   // :349
+            said_read = true;
+            view.n_contigs = dev_view.n_contigs; view.n_records = dev_view.n_records;   // (the counts of --timing)
+            t1 = clk::now();
+            aasm_result *res = nullptr;
+            aasm_out_sizes sz;
+            aasm_dev_out d_out;
+            aasm_dev_cuts d_cuts;
+            std::memset(&d_out, 0, sizeof d_out); std::memset(&d_cuts, 0, sizeof d_cuts);
+            std::vector<void *> mem;
+            bool oom = false, unwritten = false;
+            auto dalloc = [&](int64_t bytes) -> void * {
+                void *q = nullptr;
+                if (oom || hipMalloc(&q, (size_t)(bytes > 0 ? bytes : 8)) != hipSuccess) { (void)hipGetLastError(); oom = true; return nullptr; }
+                mem.push_back(q);
+                return q;
+            };
+            // The device read holds the context's lock from start to end, so a warm-up that came second is still waiting to make the
+            // arena.  It is waited for here: a solve that got the lock first would grow the arena block by block between its kernels.
+            for (auto &th : warm) if (th.joinable()) th.join();
+            const auto tu = clk::now();
+            rc = aasm_solve_device(&dev_view, &opts, nullptr, &res);
+            const auto ts = clk::now();
+            if (rc == AASM_OK) rc = aasm_result_sizes(res, &sz);
+            if (rc == AASM_OK) {
+                (void)hipSetDevice(opts.device);
+                const int64_t C = sz.n_contigs;
+                d_out.main_off = (int64_t *)dalloc((C + 1) * 8); d_out.alt_off = (int64_t *)dalloc((C + 1) * 8); d_out.all_path_off = (int64_t *)dalloc((C + 1) * 8);
+                d_out.all_elem_off = (int64_t *)dalloc((sz.n_all_paths + 1) * 8); d_out.ctg_status = (int32_t *)dalloc(C * 4);
+                d_out.main_elems = (aasm_out_elem *)dalloc(sz.n_main * 40); d_out.alt_elems = (aasm_out_elem *)dalloc(sz.n_alt * 40); d_out.all_elems = (aasm_out_elem *)dalloc(sz.n_all_elems * 40);
+                d_cuts.main = (aasm_cut_plan *)dalloc(sz.n_main * 48); d_cuts.alt = (aasm_cut_plan *)dalloc(sz.n_alt * 48); d_cuts.all = (aasm_cut_plan *)dalloc(sz.n_all_elems * 48);
+                if (oom) rc = AASM_E_NOMEM;
+            }
+            if (rc == AASM_OK) rc = aasm_result_export(res, &sz, &d_out, nullptr);
+            if (rc == AASM_OK) rc = aasm_cut_plans_device(&dev_view, &sz, &d_out, &d_cuts, opts.device, nullptr);
+            aasm_stats st;
+            std::memset(&st, 0, sizeof st);
+            if (rc == AASM_OK) (void)aasm_result_stats(res, &st);
+            if (rc == AASM_OK) {
+                (void)hipDeviceSynchronize();
+                t2 = clk::now();
+                upload_s = secs(t1, tu);                                         // (no upload: the wait for the arena)
+                aasm_writer *wr = nullptr;
+                rc = aasm_writer_open(f_main.c_str(), f_alt.c_str(), f_all.c_str(), &wr);
+                if (rc != AASM_OK) { std::cerr << "alignasm: writing outputs failed: " << aasm_last_error() << "\n"; return 3; }
+                rc = aasm_writer_append_device(wr, nullptr, &dev_view, &cols, &sz, &d_out, &d_cuts, 0, 0, opts.device);
+                unwritten = rc == AASM_E_NOMEM || rc == AASM_E_PARSE || rc == AASM_E_INVAL;   // (out of memory, a row that cannot be formatted: nothing was written)
+                if (!unwritten) {
+                    device_s = secs(tu, ts); fetch_s = secs(ts, t2); solve_busy_s = secs(t1, t2);   // (fetch: sizes, export and plans)
+                    if (st.n_internal_errors) std::cerr << "alignasm: " << st.n_internal_errors << " contig(s) hit an internal error state\n";
+                    std::cout << "Write output PAF file" << std::endl;               // :487
+                    const std::string msg = rc != AASM_OK ? aasm_last_error() : "";
+                    const int crc = aasm_writer_close(wr, rc == AASM_OK ? 1 : 0);
+                    if (rc != AASM_OK) std::cerr << "alignasm: writing outputs failed: " << msg << "\n";
+                    else if ((rc = crc) != AASM_OK) std::cerr << "alignasm: writing outputs failed: " << aasm_last_error() << "\n";
+                    write_busy_s = secs(t2, clk::now());
+                    done = true;
+                    container = 0;
+                } else (void)aasm_writer_close(wr, 0);
+            }
+            aasm_result_free(res);
+            for (void *q : mem) (void)hipFree(q);
+            aasm_upload_free(up);
+            up = nullptr;
+            if (!done && !unwritten && rc != AASM_E_NOMEM && rc != AASM_E_PARSE) { std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; return 2; }
+        }
+        device_reader = device_writer = false;                                  // done; or on with the host reader, as the command without the two flags
+    }
+    if (!done) {
+        // the reader only indexes the rows; the cs tags are turned into match ranges on the GPU
+        // --device-reader: the rows are framed and parsed on the GPU, which leaves the batch resident (up, dev_view) beside the container
+        rc = device_reader ? aasm_paf_read_device(std::filesystem::absolute(p).c_str(), 0, opts.device, &paf, &up, &dev_view)
+                               : aasm_paf_read_opts(std::filesystem::absolute(p).c_str(), host_ranges ? 0 : AASM_READ_DEVICE_RANGES, &paf);
+        if (rc != AASM_OK && device_reader && rc != AASM_E_PARSE && rc != AASM_E_IO) { std::cerr << "alignasm: solver failed (" << rc << "): " << aasm_last_error() << "\n"; return 2; }
+        if (rc != AASM_OK) { std::cerr << aasm_last_error() << "\n"; return 1; }    // e.g. "Missing cs:Z tag ..." (:165-168)
+        if (up && (use_alt || gpus > 1)) { aasm_upload_free(up); up = nullptr; }    // the merge changes the records, shards are uploaded per GPU: on from the container
+        if (use_alt) {
+            rc = aasm_paf_merge_alt(paf, std::filesystem::absolute(alt_loc).c_str(), alt_baseline);
+            if (rc != AASM_OK) { std::cerr << aasm_last_error() << "\n"; aasm_paf_free(paf); return 1; }
+        }
+        if (!said_read) std::cout << "File read complete" << std::endl;              // :340
+        aasm_paf_batch(paf, &view);
+        if (!said_read) std::cout << "Analyze PAF " << view.n_contigs << " data in parallel" << std::endl;   // :349
+        t1 = clk::now();                                                 // (the warm-up threads are not waited for: the upload runs beside them, the solve takes the context's lock after them)
+        t2 = t1;
+    }
     if (device_writer) {
         // ---- the batch is solved in one piece on the device - resident from --device-reader, else uploaded in its cs form from the
         //      container (after --alt: the merged one) - and the rows are formatted there: export -> cut plans -> device writer.  Out of
@@ -310,7 +393,7 @@ int main(int argc, char **argv) {
     if (timing)
         std::cerr << "alignasm timing: records " << view.n_records << " contigs " << view.n_contigs << " read_s " << secs(t0, t1) << " solve_s " << solve_busy_s
                   << " (upload " << upload_s << " device " << device_s << " fetch " << fetch_s << ") write_s " << write_busy_s
-                  << " overlap_s " << (solve_busy_s + write_busy_s - secs(t1, t3)) << " total_s " << secs(t0, t3) << "\n";
+                  << " overlap_s " << (solve_busy_s + write_busy_s - secs(t1, t3)) << " total_s " << secs(t0, t3) << " container " << container << "\n";
     // the process ends here: the GBs of parsed text and results go back to the OS in one piece
     // instead of vector by vector (1.7 s of page freeing for a 5M-record file)
     std::cout.flush(); std::cerr.flush();

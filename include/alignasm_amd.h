@@ -367,7 +367,8 @@ int  aasm_reserve_workspace(int device, int64_t bytes);
 int64_t aasm_debug_fetch(aasm_result *res, const char *name, void *dst, int64_t dst_bytes);
 /* Process-wide diagnostic counters (tests / tuning): "range_splits" (contig ranges halved after an
  * out-of-memory), "device_mallocs" (hipMalloc calls of the arenas), "stream_syncs" (host waits on a
- * pipeline stream), "read_slow_rows" / "read_host_fallbacks" (aasm_paf_parse_device).  Unknown name: -1.                                                         */
+ * pipeline stream), "read_slow_rows" / "read_host_fallbacks" (aasm_paf_parse_device), "read_containers" (containers built by
+ * device reads).  Unknown name: -1.                                                                                    */
 int64_t aasm_debug_counter(const char *name);
 /* Process-wide debug switch (tests): 0 = off (production); 1..255 = the byte every allocator of device working memory fills
  * fresh memory with: the whole workspace arena at the start of each aasm_solve_device (and a block created during it), each
@@ -426,6 +427,27 @@ int  aasm_paf_parse_mem_opts(const char *text, int64_t len, int flags, aasm_paf 
 #define AASM_READ_H_FEW_BLOCKS 0x200  /* test hook, 0 in production: every reader grid is capped at 3 blocks (grid-stride loops) */
 int  aasm_paf_parse_device(const char *text, int64_t len, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view);
 int  aasm_paf_read_device(const char *path, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view);
+/* The device reader that also leaves the row columns resident: *dev_cols is, array for array and byte for byte, what
+ * aasm_paf_upload_rows(P, 0, n_contigs, ...) gives for the host reader's container P of the same text (names: the contig names back
+ * to back, then the reference names in first-appearance order; row_index[r] = r, cord_type[r] = 0).  The numeric columns are the
+ * ones the device parsed, the names are copied out of the text on the device.  up, dev_view and dev_cols are required; *up owns
+ * the batch's arrays and the columns' arrays, one aasm_upload_free releases both.  paf may be NULL: then no container is built -
+ * no tag pool, no column fetch, no host pass over the text - and solve, cut plans, rows and aasm_writer_append_device (paf = NULL)
+ * run from the resident arrays alone.  Errors, host fallback, slow rows and counters as aasm_paf_parse_device; aasm_debug_counter
+ * "read_containers": containers built by device reads in this process.
+ *   AASM_READ_ROW_COLS        what these entries add to a device read (they imply it; aasm_paf_parse_device ignores it).
+ *   AASM_READ_TEXT_ON_DEVICE  text is device memory of `device`, 16-byte aligned, complete before the call; the library does not
+ *                             copy it and never frees or writes it.  Only with paf = NULL (AASM_E_INVAL otherwise, as for a
+ *                             misaligned pointer, host memory or memory of another device; nothing is enqueued).  The host steps
+ *                             fetch what they need: a slow row's bytes, and the whole text once when the read has failed and
+ *                             the host reader says why.  The call is synchronous.                                          */
+#define AASM_READ_ROW_COLS 2
+#define AASM_READ_TEXT_ON_DEVICE 4
+struct aasm_row_cols;
+int  aasm_paf_parse_device_rows(const char *text, int64_t len, int flags, int device, aasm_paf **paf, aasm_upload **up,
+                                aasm_batch_in *dev_view, struct aasm_row_cols *dev_cols);
+int  aasm_paf_read_device_rows(const char *path, int flags, int device, aasm_paf **paf, aasm_upload **up, aasm_batch_in *dev_view,
+                               struct aasm_row_cols *dev_cols);
 /* --alt merge of a second PAF of sub-contig re-alignments (alignasm.cpp:186-332) */
 int  aasm_paf_merge_alt(aasm_paf *paf, const char *alt_path, double alt_baseline);
 int  aasm_paf_merge_alt_mem(aasm_paf *paf, const char *text, int64_t len, double alt_baseline);
@@ -509,7 +531,12 @@ int  aasm_rows_format_device(const aasm_batch_in *dev_in, const aasm_row_cols *d
  * piece k + 1 being formatted while piece k is copied back and written.  dev_in .. cuts: the resident batch, the row columns of the
  * same contigs, the exported result and its plans, all on `device`; the files are byte for byte those of aasm_writer_append for
  * the same result, and the session rules are its own.  A result with an element that cannot be formatted writes nothing and fails
- * the append with the code and message of aasm_writer_append_cuts on the same inputs.                                        */
+ * the append with the code and message of aasm_writer_append_cuts on the same inputs.
+ * paf may be NULL (a batch read by aasm_paf_parse_device_rows without a container): the session's checks then take the contig
+ * count from sz and the presence of tags from dev_in->cs_text, the bytes written are the same, and a result with an element that
+ * cannot be formatted writes nothing and fails with AASM_E_PARSE (a tag, insert-clip or edit flag) or AASM_E_INVAL (a record or
+ * plan fault) and the message "<count> output elements cannot be formatted; the first: list <main|alt|all>, element <index>,
+ * flags 0x<flags>".                                                                                                         */
 int  aasm_writer_append_device(aasm_writer *w, const aasm_paf *paf, const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols,
                                const aasm_out_sizes *sz, const aasm_dev_out *dev_out, const aasm_dev_cuts *cuts,
                                int64_t contig0, int64_t piece_bytes, int device);
