@@ -147,7 +147,7 @@ AASM_DEV unsigned long long atomic_add(int64_t *p, int64_t v) {
 }
 AASM_DEV int32_t atomic_min_i32(int32_t *p, int32_t v) { return atomicMin(p, v); }
 AASM_DEV int32_t atomic_cas_i32(int32_t *p, int32_t cmp, int32_t v) { return atomicCAS(p, cmp, v); }
-AASM_DEV void atomic_max_i64(int64_t *p, int64_t v) { atomicMax((long long *)p, (long long)v); }   // (non-negative values)
+AASM_DEV void atomic_max_i64(int64_t *p, int64_t v) { atomicMax((long long *)p, (long long)v); }   // (signed; its callers pass counts - vertices, records - which are non-negative.  Walk sums and d[] towards dest are not: see K8)
 AASM_DEV void atomic_min_i64(int64_t *p, int64_t v) { atomicMin((long long *)p, (long long)v); }
 AASM_DEV int popc64(uint64_t m) { return __popcll(m); }
 AASM_DEV int ffs64(uint64_t m) { return __ffsll((long long)m); }

@@ -3365,9 +3365,15 @@ AASM_DEV void kb_heap_mw(const KCtx &k, const WS &w) {              // MW_WAVES 
 // K8  k-walk enumeration (k_shortest_walks.hpp:217-249)
 // ====================================================================================
 // std::greater<tuple<Distance, heap_t*, int64_t>>: entries in the queue are distances of
-// real walks (non-negative components), on which operator< is a strict weak order, so the
+// real walks (never Distance::max()), on which operator< is a strict weak order, so the
 // tuple order is total and any correct min-queue pops the same sequence.  The pointer is
 // replaced by the arena index (DESIGN.md "hazard B3").
+// Non-negative in such a distance: anom, qul_nonzero, qul_total (counts) and the score sum of
+// every sidetrack key (a detour never beats the tree).  NOT non-negative: the score components and their sum -
+// a record with qry_end >= qry_total (the --alt merge's appended rows read qry_total = 0)
+// has a dest edge of (qry_total - qry_end - 1) * 2 < 0, so d[] towards dest and whole contigs'
+// walk sums are negative.  Every compare of a sum here is signed; kb_enum_lsm, which orders
+// unsigned words, biases it (QE_SUM_BIAS, aasm_enum.h).  tests/test_gpu_overhang.py.
 //
 // The queue is a wave-cooperative 8-ARY heap of 32-byte keys {score sum, anom, qul_nonzero, qul_total, heap
 // node, insertion index}: everything the order needs (the query / reference split of the score is not part of
@@ -3380,7 +3386,7 @@ AASM_DEV void kb_heap_mw(const KCtx &k, const WS &w) {              // MW_WAVES 
 #define PQ8_LDS_N 585
 #define AASM_ENUM_LDS_BYTES (PQ8_LDS_N * 32 + 32)
 struct __attribute__((aligned(16))) PqK { int64_t sum; int32_t anom, qnz, qtot, node, cur, pad; };
-// std::tuple order of (Distance, node, cur) for distances of real walks (never max(), all components >= 0):
+// std::tuple order of (Distance, node, cur) for distances of real walks (never max(); counts >= 0, score sums of either sign):
 // paf_data.hpp:142-159 then node index then insertion index
 AASM_DEV bool pq_full_less(const Dist &a, int32_t a_node, int32_t a_cur, const Dist &b, int32_t b_node, int32_t b_cur) {
     const int64_t sa = a.qry + a.ref, sb = b.qry + b.ref;

@@ -11,6 +11,8 @@ all weight fields, anom_dis[dest], d / best, both Kahn orders, every heap node a
     python tests/golden/make_ref_prefix.py          # ref_prefix.npz
     python tests/golden/make_ref_prefix.py wide     # ref_prefix_wide.npz: the same from tests/wide_cases.py's batches
                                                     # (coordinates, weights and score sums above 2^31 / 2^32, up to 2^40 - 1)
+    python tests/golden/make_ref_prefix.py overhang # ref_prefix_overhang.npz: the same from tests/overhang_cases.py's rewrites
+                                                    # (qry_end >= qry_total - 1: negative dest edges and walk sums)
 """
 import os
 import sys
@@ -24,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import aasm_testlib as T   # noqa: E402
 from test_fuzz import make_batch   # noqa: E402
 import wide_cases as W   # noqa: E402
+import overhang_cases as O   # noqa: E402
 
 KD = ("kd_qry", "kd_ref", "kd_anom", "kd_qnz", "kd_qtot")
 KD_SHORT = 64
@@ -75,6 +78,19 @@ WIDE_BATCHES = [
     ("syn_x32", lambda: _shifted(T.synth(1, 60, 5, dup_every=3), "x32"), False, False),
     ("syn_top", lambda: _shifted(T.synth(1, 60, 9), "top"), False, False),
     ("dense_5g", lambda: _shifted(T.synth(1, 50, 31, dense=True), "5g"), False, False),
+]
+
+
+# six fuzz contigs of at most 30 records per mode at large coordinates (at L = 400 hardly a walk sum is negative), one contig whose
+# 10 000 walks cross zero half-way, and one whose 10 000 negative sums spread over more than 50 000
+OVERHANG_BATCHES = [
+    ("ov_zero", lambda: O.overhang(make_batch(60, 6, 30, 10 ** 8, 0), "zero"), False, False),
+    ("ov_longest", lambda: O.overhang(make_batch(61, 6, 30, 10 ** 8, 1), "longest"), False, False),
+    ("ov_touch", lambda: O.overhang(make_batch(62, 6, 30, 10 ** 8, 2), "touch"), False, False),
+    ("ov_median_n", lambda: O.overhang(make_batch(63, 6, 30, 10 ** 8, 0), "median"), True, False),
+    ("ov_mixed", lambda: O.overhang(make_batch(64, 6, 30, 10 ** 8, 2), "mixed", 64), False, True),
+    ("ov_centre", lambda: O.centre(T.synth(1, 300, 5, dup_every=3), 10000), False, True),
+    ("ov_spread", lambda: O.overhang(T.synth(6, 30, 4).subset([3]), "zero"), False, True),
 ]
 
 
@@ -140,5 +156,7 @@ def main(batches=BATCHES, name="ref_prefix.npz", packed=False):
 if __name__ == "__main__":
     if sys.argv[1:] == ["wide"]:
         main(WIDE_BATCHES, "ref_prefix_wide.npz", packed=True)
+    elif sys.argv[1:] == ["overhang"]:
+        main(OVERHANG_BATCHES, "ref_prefix_overhang.npz", packed=True)
     else:
         main()

@@ -22,8 +22,14 @@ CASES = [(3, 1000, 21, 10000, False, 0),     # the bench's k10000 shape
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "c%dx%d_s%d_k%d_%s%s" % (c[0], c[1], c[2], c[3], "D" if c[4] else "S", "_dup%d" % c[5] if c[5] else ""))
 def test_enumeration_queue_forms_agree_with_each_other_and_the_oracle(T, case):
     nc, nr, seed, K, dense, dup = case
+    check_queue_forms(T, T.synth(nc, nr, seed, dense=dense, dup_every=dup), K)
+
+
+def check_queue_forms(T, hb, K, expect=None):
+    """The three queue forms of K8 on one batch (tests/test_gpu_overhang.py calls this too; `expect(c)`: the oracle's
+    intermediates of contig c where the caller has them already)."""
+    nc = hb.n_contigs
     api = T.api()
-    hb = T.synth(nc, nr, seed, dense=dense, dup_every=dup)
     db = api.DeviceBatch(hb)
     got = {}
     for form in ("runs", "runs40", "heap"):                          # 64-entry front, the 40-entry front of big batches, the d-ary heap
@@ -36,7 +42,7 @@ def test_enumeration_queue_forms_agree_with_each_other_and_the_oracle(T, case):
         knodes, kprev = cand[:, 0].copy(), cand[:, 1].copy()
         got[form] = (kf, kd, klast, knodes, kprev, res.fetch())
         if form == "runs":
-            assert T.diff_intermediates(hb, res.debug, K) == []      # kfound + every popped distance vs the oracle
+            assert T.diff_intermediates(hb, res.debug, K, expect=expect) == []      # kfound + every popped distance vs the oracle
         res.close()
     db.close()
     for other in ("heap", "runs40"):

@@ -7,14 +7,26 @@ distances - recorded by tests/golden/make_ref_prefix.py from oracle/_ref/libaasm
 lines compiled in place; oracle/Makefile).  Checked against them here:
   CPU tier: the oracle (so "HIP == oracle" elsewhere means "== reference" for these stages) and the product's
             kernel bodies in the 1-lane emulation;
-  GPU tier: the HIP kernels' intermediates on the card, at K = 10 000 and at small K, with either K7 kernel."""
+  GPU tier: the HIP kernels' intermediates on the card, at K = 10 000 and at small K, with either K7 kernel.
+tests/golden/ref_prefix_overhang.npz holds the same for batches of tests/overhang_cases.py (records that run to or past the
+query's end: negative dest edges and walk sums); every check here runs over both files - one body per check, a test per
+file (the first file's tests keep their names)."""
+import os
+
 import numpy as np
 import pytest
+
+HIP_FORMS = [("auto", "auto"), ("all", "auto"), ("none", "auto"), ("auto", "none"), ("auto", "half")]
 
 
 @pytest.fixture(scope="module")
 def V(T):
     return T.RefPrefixVectors()
+
+
+@pytest.fixture(scope="module")
+def VO(T):
+    return T.RefPrefixVectors(os.path.join(T.GOLDEN, "ref_prefix_overhang.npz"))
 
 
 def test_fixture_covers_the_stages(T, V):
@@ -31,7 +43,38 @@ def test_fixture_covers_the_stages(T, V):
     assert n_pairs > 2000 and n_nodes > 100000 and n_dist > 100000 and n_nsl >= 4
 
 
+def test_overhang_fixture_holds_its_input_class(T, VO):
+    """What the reference itself computed on the overhang batches: dest edges below zero, contigs whose recorded walks are all
+    negative, contigs whose 10 000 walks cross zero, and negative sums spread over more than 50 000 in one contig."""
+    V = VO
+    assert len(V.tags) >= 7
+    n_neg_edges = n_all_neg = n_cross = n_dist = n_nsl = n_touch = spread = 0
+    for tag in V.tags:
+        hb, nsl, full = V.batch(tag)
+        assert (np.diff(hb.arrays["ctg_rec_off"]) <= 30).all() or hb.n_contigs == 1
+        n_nsl += nsl
+        for c in range(hb.n_contigs):
+            r = V.contig(tag, c)
+            if not r:
+                continue
+            assert set(T.PREFIX_NAMES) <= set(r)
+            s = r["kd_qry"] + r["kd_ref"]
+            n_dist += len(s); n_neg_edges += int((r["csr_w_qry"] < 0).sum()); n_touch += int(r["csr_w_qry"].min() == 0)
+            n_all_neg += bool((s < 0).all()); n_cross += bool(s.min() < 0 <= s.max())
+            if full and (s < 0).all():
+                spread = max(spread, int(s.max() - s.min()))
+    assert n_neg_edges > 300 and n_all_neg >= 10 and n_cross >= 3 and n_touch >= 6 and n_dist > 50000 and n_nsl >= 1 and spread > 50000
+
+
 def test_oracle_matches_recorded_reference_prefix(T, V):
+    _oracle_matches(T, V)
+
+
+def test_oracle_matches_recorded_reference_prefix_overhang(T, VO):
+    _oracle_matches(T, VO)
+
+
+def _oracle_matches(T, V):
     for tag in V.tags:
         hb, nsl, full = V.batch(tag)
         for c in range(hb.n_contigs):
@@ -46,6 +89,14 @@ def test_oracle_matches_recorded_reference_prefix(T, V):
 
 
 def test_kernel_bodies_match_recorded_reference_prefix(T, V):
+    _kernel_bodies_match(T, V)
+
+
+def test_kernel_bodies_match_recorded_reference_prefix_overhang(T, VO):
+    _kernel_bodies_match(T, VO)
+
+
+def _kernel_bodies_match(T, V):
     for tag in V.tags:
         hb, nsl, full = V.batch(tag)
         for K in ((10000, 4) if full else (64,)):
@@ -54,8 +105,18 @@ def test_kernel_bodies_match_recorded_reference_prefix(T, V):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("heap_waves,chain", [("auto", "auto"), ("all", "auto"), ("none", "auto"), ("auto", "none"), ("auto", "half")])
+@pytest.mark.parametrize("heap_waves,chain", HIP_FORMS)
 def test_hip_intermediates_match_recorded_reference_prefix(T, V, heap_waves, chain):
+    _hip_intermediates_match(T, V, heap_waves, chain)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("heap_waves,chain", HIP_FORMS)
+def test_hip_intermediates_match_recorded_reference_prefix_overhang(T, VO, heap_waves, chain):
+    _hip_intermediates_match(T, VO, heap_waves, chain)
+
+
+def _hip_intermediates_match(T, V, heap_waves, chain):
     """The HIP path's intermediates on the card against what the reference's own statements computed - with either K7 kernel
     forced, and with the sparse contigs in the chain class (aasm_k67_chain; the default for batches this small), in the three
     launches, or split between the two."""
