@@ -77,6 +77,9 @@ def _load():
     lib.aasm_paf_parse_device_rows.restype = C.c_int
     lib.aasm_paf_read_device_rows.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.aasm_paf_read_device_rows.restype = C.c_int
+    # the --alt merge on a resident batch: (aasm_batch_in *, aasm_row_cols *, text, len, baseline, flags, device, aasm_upload **, aasm_batch_in *, aasm_row_cols *)
+    lib.aasm_paf_merge_alt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aasm_paf_merge_alt_device.restype = C.c_int
     return lib
 
 
@@ -90,7 +93,7 @@ EXPORTED = [
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
     "aasm_paf_parse_device", "aasm_paf_read_device", "aasm_paf_parse_device_rows", "aasm_paf_read_device_rows",
-    "aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device",
+    "aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device", "aasm_paf_merge_alt_device",
 ]
 
 
@@ -411,6 +414,22 @@ class DeviceBatch:
         opts = make_opts(max_paths, non_skip_linkable, self.device, timing, keep_debug, **hooks)
         _check(LIB.aasm_solve_device(C.byref(self.dev_view), C.byref(opts), C.c_void_p(stream or 0), C.byref(res)))
         return DeviceResult(res, self.device)
+
+    def merge_alt(self, text: bytes, alt_baseline=0.5, _flags=0):
+        """--alt on the device (aasm_paf_merge_alt_device): the second PAF joins this batch, which must be in its cs form -> a new
+        DeviceBatch without a container that carries its row columns (solve, row_cols, write_outputs, to_torch(cuts=..., rows=True)).
+        This batch stays valid.  A text the device declines (a zeroed group, a piece name off the fast path, a row the reader does
+        not take) raises AASM_E_PARSE - with the host's message where the host finds the text bad - and leaves this batch as it
+        was.  A malformed cs tag in a well-formed alt row is reported by the merged batch's solve.  _flags: AASM_READ_H_* (tests)."""
+        if getattr(self, "_row_cols", None) is None and not isinstance(self._keep, Paf):
+            raise AlignasmError(AASM_E_INVAL, "merge_alt: the batch has no row columns and no Paf to make them from")
+        cols = self.row_cols()
+        up, view, merged = C.c_void_p(), BatchIn(), RowCols()
+        _check(LIB.aasm_paf_merge_alt_device(C.byref(self.dev_view), C.byref(cols), text, C.c_int64(len(text)), C.c_double(alt_baseline), int(_flags), int(self.device),
+                                             C.byref(up), C.byref(view), C.byref(merged)))
+        db = DeviceBatch._from_upload(up, view, self.device)
+        db._row_cols = merged
+        return db
 
     def row_cols(self) -> RowCols:
         """What an output row prints beyond the batch: resident already where the device reader left it (container=False,

@@ -28,6 +28,7 @@
 #include "aasm_ksw.h"
 #include "aasm_cut.h"
 #include "aasm_read.h"
+#include "aasm_alt.h"
 #include "aasm_rows.h"
 #include "aasm_paf.hpp"
 
@@ -82,6 +83,10 @@ AASM_CUT_KERNELS(K, KL)
 #define AASM_FAMILY (ReadArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_READ_KERNELS(K, KL)
 #undef AASM_FAMILY
+// the --alt merge on a resident batch (aasm_paf_merge_alt_device; bodies in aasm_alt.h)
+#define AASM_FAMILY (AltArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_ALT_KERNELS(K, KL)
+#undef AASM_FAMILY
 // output rows on the device (aasm_rows_sizes_device / aasm_rows_format_device; bodies in aasm_rows.h)
 #define AASM_FAMILY (RowsArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_ROWS_KERNELS(K, KL)
@@ -99,6 +104,7 @@ static const KernelSym<SsspArgs> sssp_syms[] = {AASM_SSSP_KERNELS(K, K)};
 static const KernelSym<int64_t, KswArgs> ksw_syms[] = {AASM_KSW_KERNELS(K, K)};
 static const KernelSym<CutArgs> cut_syms[] = {AASM_CUT_KERNELS(K, K)};
 static const KernelSym<ReadArgs> read_syms[] = {AASM_READ_KERNELS(K, K)};
+static const KernelSym<AltArgs> alt_syms[] = {AASM_ALT_KERNELS(K, K)};
 static const KernelSym<RowsArgs> rows_syms[] = {AASM_ROWS_KERNELS(K, K)};
 #undef K
 template <size_t N, class... P> static void launch_row(const KernelSym<P...> (&rows)[N], int id, int64_t nblocks, int nthreads, hipStream_t s, const P &...args) {
@@ -330,7 +336,7 @@ static void drain_exports(DevCtx &cx) {
 }
 static DevCtx g_ctx[16];
 static std::mutex g_init_mu;
-static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0}, g_n_read_slow_rows{0}, g_n_read_fallbacks{0}, g_n_read_containers{0};
+static std::atomic<int64_t> g_n_range_splits{0}, g_n_device_mallocs{0}, g_n_stream_syncs{0}, g_n_read_slow_rows{0}, g_n_read_fallbacks{0}, g_n_read_containers{0}, g_n_alt_verdicts{0}, g_n_alt_merges{0};
 
 // aasm_debug_poison: 0 = off (production), 1..255 = the byte the three allocators below fill fresh working memory with, so that
 // a kernel reading a cell nobody wrote meets it instead of a harmless left-over.  Left alone: the scans' ticket / tile words
@@ -1055,6 +1061,8 @@ int64_t aasm_debug_counter(const char *name) {
     if (n == "read_slow_rows") return g_n_read_slow_rows.load();
     if (n == "read_host_fallbacks") return g_n_read_fallbacks.load();
     if (n == "read_containers") return g_n_read_containers.load();
+    if (n == "alt_host_verdicts") return g_n_alt_verdicts.load();
+    if (n == "alt_device_merges") return g_n_alt_merges.load();
     return -1;
 }
 
@@ -1205,6 +1213,11 @@ struct ReadGpu {
             std::fprintf(stderr, "aasm read kernel: %-20s %9.3f ms (%lld blocks)\n", (unsigned)kr < KR_N ? read_syms[kr].name : "", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, (long long)nblocks);
         }
     }
+    void launch_alt(int ka, int64_t nblocks, int nthreads, const AltArgs &a) {
+        if (!ok()) return;
+        launch_row(alt_syms, ka, nblocks, nthreads, cx.stream, a);
+        e = hipGetLastError();
+    }
     void stage(const char *name) {
         if (!timing) return;
         if (ok()) e = hipStreamSynchronize(cx.stream);
@@ -1338,6 +1351,56 @@ int aasm_paf_read_device_rows(const char *path, int flags, int device, aasm_paf 
     return with_file_text(path, [&](const char *text, int64_t len) {
         return aasm_paf_parse_device_rows(text, len, flags & ~AASM_READ_TEXT_ON_DEVICE, device, paf_out, up_out, dev_view, dev_cols);
     });
+}
+
+// ---- the --alt merge on a resident batch (aasm_alt.h): the reader's backend, the merged arrays in a handle of their own
+int aasm_paf_merge_alt_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const char *alt_text, int64_t alt_len, double alt_baseline,
+                              int flags, int device, aasm_upload **up_out, aasm_batch_in *merged_view, aasm_row_cols *merged_cols) {
+    if (up_out) *up_out = nullptr;
+    auto inval = [](const char *what) { set_last_error(std::string("aasm_paf_merge_alt_device: ") + what); return AASM_E_INVAL; };
+    if (!dev_in || !dev_cols || !up_out || !merged_view || !merged_cols || alt_len < 0 || (!alt_text && alt_len > 0)) return inval("bad argument");
+    if (dev_in->rng_qry_l || dev_in->rng_qry_r || dev_in->rng_ref_l || !dev_in->cs_text || !dev_in->rec_cs_off) return inval("the batch is not in its cs form (cs_text / rec_cs_off, no rng_*)");
+    const int64_t C = dev_in->n_contigs, R = dev_in->n_records;
+    if (C <= 0 || R <= 0 || R > INT32_MAX || dev_cols->n_chr < 0 || dev_cols->n_chr > INT32_MAX / 2) return inval("bad counts");
+    int rc = ctx_init(device);
+    if (rc != AASM_OK) return rc;
+    hipSetDevice(device);
+    const aasm_batch_in &in = *dev_in;
+    const aasm_row_cols &cl = *dev_cols;
+    if (!dev_buffer_ok(in.ctg_rec_off, C + 1, 8, device) || !dev_buffer_ok(in.qry_str, R, 8, device) || !dev_buffer_ok(in.qry_end, R, 8, device) ||
+        !dev_buffer_ok(in.ref_str, R, 8, device) || !dev_buffer_ok(in.ref_end, R, 8, device) || !dev_buffer_ok(in.qry_total, R, 8, device) ||
+        !dev_buffer_ok(in.ref_chr, R, 4, device) || !dev_buffer_ok(in.aln_fwd, R, 1, device) || !dev_buffer_ok(in.map_qul, R, 1, device) ||
+        !dev_buffer_ok(in.rec_rng_off, R + 1, 8, device) || !dev_buffer_ok(in.rec_cs_off, R + 1, 8, device) || !dev_buffer_ok(in.cs_text, 1, 1, device) ||
+        !dev_buffer_ok(cl.ref_total, R, 8, device) || !dev_buffer_ok(cl.mat_num, R, 4, device) || !dev_buffer_ok(cl.aln_len, R, 4, device) ||
+        !dev_buffer_ok(cl.row_index, R, 4, device) || !dev_buffer_ok(cl.cord_type, R, 1, device) || !dev_buffer_ok(cl.names, 1, 1, device) ||
+        !dev_buffer_ok(cl.ctg_name_off, C + 1, 8, device) || !dev_buffer_ok(cl.chr_name_off, cl.n_chr + 1, 8, device))
+        return inval("an array of the batch or of its row columns is NULL or not device memory of the device");
+    DevCtx &cx = g_ctx[device];
+    AltOut o;
+    std::string why;
+    {
+        std::lock_guard<std::mutex> lk(cx.mu);                      // (the scans' scratch words are the context's)
+        hipSetDevice(device);
+        ReadGpu be(cx);
+        rc = alt_merge_run(be, in, cl, alt_text, alt_len, alt_baseline, flags, o);
+        if (rc < 0) {
+            why = be.why();
+            (void)hipDeviceSynchronize();                           // (a scan that did not run to its end leaves its words behind: parse_device)
+            if (cx.d_scratch) (void)hipMemset(cx.d_scratch, 0, cx.d_scratch_cap * 8);
+            cx.pinned[SCAN_STALL_SLOT] = 0;
+            (void)hipGetLastError();
+        }
+    }
+    if (rc < 0) { set_last_error("aasm_paf_merge_alt_device: " + why); return rc; }
+    if (rc == AASM_ALT_DECLINED) { g_n_alt_verdicts++; return alt_host_says(alt_text, alt_len, o); }
+    aasm_upload *up = new aasm_upload();
+    up->device = device;
+    up->ptrs = alt_out_arrays(o);
+    alt_out_views(o, up->view, *merged_cols);
+    *merged_view = up->view;
+    *up_out = up;
+    g_n_alt_merges++;
+    return AASM_OK;
 }
 
 // ---- output rows on the device (aasm_rows.h) ----------------------------------------------------------------------------------

@@ -386,7 +386,7 @@ bool read_slow_row(const char *s, const char *e, ReadRowCols &o) {
     if (parse_row(s, e, w) != ROW_OK) return false;
     const Rec r = record_of(w, 0, 0, 0);
     o.qry_str = r.qry_str; o.qry_end = r.qry_end; o.ref_str = r.ref_str; o.ref_end = r.ref_end; o.qry_total = r.qry_total; o.ref_total = r.ref_total;
-    o.mat_num = r.mat_num; o.aln_len = r.aln_len; o.aln_fwd = r.aln_fwd; o.map_qul = r.map_qul;
+    o.mat_num = r.mat_num; o.aln_len = r.aln_len; o.aln_fwd = r.aln_fwd; o.map_qul = r.map_qul; o.aln_len64 = w.aln;
     return true;
 }
 
@@ -672,6 +672,16 @@ static int scan_alt_rows(const char *text, int64_t len, aasm_paf &paf, std::unor
         rows.push_back(std::move(r));
     }
     return AASM_OK;
+}
+
+int alt_host_verdict(const char *text, int64_t len, std::string &err) {
+    aasm_paf none;                                                                  // (no message of scan_alt_rows depends on the main file)
+    std::unordered_map<std::string, int32_t> chr_map;
+    const std::unordered_map<std::string_view, int32_t> ctg_of;
+    std::vector<AltRec> rows;
+    const int rc = scan_alt_rows(text, len, none, chr_map, ctg_of, rows);
+    if (rc != AASM_OK) err = none.error;
+    return rc;
 }
 
 static int merge_alt_text(const char *text, int64_t len, double baseline, aasm_paf &paf) {

@@ -61,8 +61,10 @@ const char *last_error_text();
 std::string cs_error_message(const char *cs, int64_t cs_len, bool aln_fwd, int64_t qry_str, int64_t qry_end, int64_t ref_str, int64_t ref_end);
 int host_threads();                          // aasm_set_host_threads (0 = all hardware threads), resolved
 // the device reader's slow path (aasm_read.h): one line without its line end through the host's parse_row + record_of; false: no row
-struct ReadRowCols { int64_t qry_str, qry_end, ref_str, ref_end, qry_total, ref_total; int32_t mat_num, aln_len; uint8_t aln_fwd, map_qul; };
+struct ReadRowCols { int64_t qry_str, qry_end, ref_str, ref_end, qry_total, ref_total; int32_t mat_num, aln_len; uint8_t aln_fwd, map_qul; int64_t aln_len64; };   // aln_len64: column 11 in full
 bool read_slow_row(const char *s, const char *e, ReadRowCols &out);
+// the --alt merge on the device (aasm_alt.h) declined a text: scan_alt_rows' code and message for it (AASM_OK: the host takes it)
+int alt_host_verdict(const char *text, int64_t len, std::string &err);
 // The device writer's (aasm_writer_append_device, aasm_gpu.hip) way into a writer session, whose struct stays aasm_paf.cpp's:
 // begin: aasm_writer_append's argument and session checks for contigs [contig0, contig0 + n_contigs), nothing changed;
 // has: file i of the session is open;  put: append these bytes to file i of the session;  end: the range is done with rc (a

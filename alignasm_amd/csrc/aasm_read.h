@@ -50,6 +50,7 @@ struct ReadArgs {
     int64_t *row_start;                  // [R]
     int64_t *qs, *qe, *rs, *re, *qtot, *rtot;
     int32_t *mat, *aln, *ref_chr;
+    int64_t *aln64;                      // [R] column 11 as a full 64-bit value, or nullptr (the reader): the --alt merge's ratio
     uint8_t *fwd, *mq;
     int64_t *tag_start, *rn_start;       // [R] the tag and the reference name in the text
     int32_t *tag_len, *n_colon, *qn_len, *rn_len;
@@ -211,6 +212,7 @@ AASM_DEV void read_row_lane(const ReadArgs &a, int64_t i) {
     v_qe -= 1; v_re -= 1;                                            // closed intervals, the reference span in query order (:141-159)
     a.qs[i] = v_qs; a.qe[i] = v_qe; a.rs[i] = fwd ? v_rs : v_re; a.re[i] = fwd ? v_re : v_rs;
     a.qtot[i] = v_qtot; a.rtot[i] = v_rtot; a.mat[i] = (int32_t)v_mat; a.aln[i] = (int32_t)v_aln;
+    if (a.aln64) a.aln64[i] = v_aln;
     a.fwd[i] = fwd ? 1 : 0; a.mq[i] = (uint8_t)v_mq;
     a.tag_start[i] = tag_s; a.tag_len[i] = (int32_t)tag_l; a.n_colon[i] = tag_colons;
     a.qn_len[i] = (int32_t)qn_l; a.rn_start[i] = rn_s; a.rn_len[i] = (int32_t)rn_l;
@@ -349,31 +351,20 @@ struct ReadOut {
 };
 #define AASM_READ_FALLBACK 1             // read_run: the text is no PAF the device takes; the host reader says why
 
-// read_run(be, ...) over a backend that provides
-//   void *alloc(size_t)            device memory, nullptr after a failure (every later call is then a no-op); freed with the backend
-//   void release(void *)           ... or now;   void keep(void *): the caller's from here on
-//   h2d / d2h(dst, src, n)         d2h waits;   fill32(p, value, count)
-//   scan_i32 / scan_u8(in, n, out) exclusive scan into int64 out[n + 1]
-//   launch_read(kernel, blocks, threads, ReadArgs);   stage(name): a launch group's name, for timing;   bool ok()
-// text: HOST memory; under AASM_READ_TEXT_ON_DEVICE device memory, 16-byte aligned, that is neither copied nor written (paf is
-// nullptr then: the container is cut from host text).  paf: the container to fill, or nullptr; want_dev: hand the batch's arrays out
-// in `out` (else they are freed), under AASM_READ_ROW_COLS the row columns' arrays with them.
-// Returns AASM_OK, AASM_READ_FALLBACK, or the backend's failure as AASM_E_NOMEM / AASM_E_HIP through be.code().
-template <class B> int read_run(B &be, const char *text, int64_t len, int flags, aasm_paf *paf, bool want_dev, ReadOut &out) {
-    const int64_t max_blocks = (flags & AASM_READ_H_FEW_BLOCKS) ? 3 : AASM_READ_MAX_BLOCKS;   // (the hook: fewer blocks than items)
-    auto blocks_for = [&](int64_t items, int per_block) { return std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, max_blocks)); };
+// The front of a device read, which the --alt merge (aasm_alt.h) shares: row starts, the rows' columns, and the host's word on the
+// rows with a number off the fast path.  a.text, a.len and a.weak_hash are set; want_aln64: a.aln64 takes column 11 in full.
+// behind_rows(): what the caller enqueues behind the rows kernel, before the host waits for the words (a.R is known by then).
+// Returns AASM_OK with the words in `words`, AASM_READ_FALLBACK (a.R says how many rows were framed), or the backend's failure.
+static inline int64_t read_blocks_for(int64_t items, int64_t per_block, int64_t max_blocks) {
+    return std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, max_blocks));
+}
+template <class B, class F> int read_front(B &be, ReadArgs &a, const char *text, bool on_dev, int64_t max_blocks, int32_t (&words)[RW_N], bool want_aln64, F behind_rows) {
+    auto blocks_for = [&](int64_t items, int per_block) { return read_blocks_for(items, per_block, max_blocks); };
     auto i64s = [&](int64_t n) { return (int64_t *)be.alloc((size_t)n * 8); };
     auto i32s = [&](int64_t n) { return (int32_t *)be.alloc((size_t)n * 4); };
     auto u8s = [&](int64_t n) { return (uint8_t *)be.alloc((size_t)n); };
-    ReadArgs a;
-    std::memset(&a, 0, sizeof a);
-    if (len <= 0) return AASM_READ_FALLBACK;
-    const bool on_dev = (flags & AASM_READ_TEXT_ON_DEVICE) != 0, row_cols = (flags & AASM_READ_ROW_COLS) != 0 && want_dev;
-    if (on_dev && paf) return AASM_E_INVAL;
-    be.stage("upload");
-    uint8_t *d_text = on_dev ? (uint8_t *)const_cast<char *>(text) : u8s(len);
-    if (!on_dev) be.h2d(d_text, text, (size_t)len);
-    a.text = d_text; a.len = len; a.weak_hash = (flags & AASM_READ_H_WEAK_HASH) ? 1 : 0;
+    const int64_t len = a.len;
+    const uint8_t *d_text = a.text;
     // ---- row starts
     be.stage("row starts");
     a.n_tiles = (len + AASM_READ_TILE - 1) / AASM_READ_TILE;
@@ -385,31 +376,23 @@ template <class B> int read_run(B &be, const char *text, int64_t len, int flags,
     int64_t R = 0;
     be.d2h(&R, tile_off + a.n_tiles, 8);
     if (!be.ok()) return be.code();
-    if (R <= 0 || R > INT32_MAX) return AASM_READ_FALLBACK;          // "empty PAF", "more than 2147483647 rows"
     a.R = R;
+    if (R <= 0 || R > INT32_MAX) return AASM_READ_FALLBACK;          // "empty PAF", "more than 2147483647 rows"
     a.row_start = i64s(R);
     be.launch_read(KR_STARTS, blocks_for(a.n_tiles, 1), read_block[KR_STARTS], a);
     // ---- rows
     be.stage("rows");
     a.qs = i64s(R); a.qe = i64s(R); a.rs = i64s(R); a.re = i64s(R); a.qtot = i64s(R); a.rtot = i64s(R);
-    a.mat = i32s(R); a.aln = i32s(R); a.ref_chr = i32s(R); a.fwd = u8s(R); a.mq = u8s(R);
+    a.mat = i32s(R); a.aln = i32s(R); a.fwd = u8s(R); a.mq = u8s(R);
+    if (want_aln64) a.aln64 = i64s(R);
     a.tag_start = i64s(R); a.rn_start = i64s(R); a.tag_len = i32s(R); a.n_colon = i32s(R); a.qn_len = i32s(R); a.rn_len = i32s(R);
     a.rn_hash = (uint64_t *)i64s(R);
-    a.words = i32s(RW_N); a.slow_row = i32s(R); a.head = u8s(R); a.cnew = u8s(R);
-    int64_t *head_off = i64s(R + 1), *cs_off = i64s(R + 1), *rng_off = i64s(R + 1);
-    a.head_off = head_off; a.cs_off = cs_off;
-    int32_t words[RW_N] = {INT32_MAX, 0, 0, 0};
-    be.h2d(a.words, words, sizeof words);
+    a.words = i32s(RW_N); a.slow_row = i32s(R);
+    const int32_t words0[RW_N] = {INT32_MAX, 0, 0, 0};
+    be.h2d(a.words, words0, sizeof words0);
     be.launch_read(KR_ROWS, blocks_for(R, read_block[KR_ROWS]), read_block[KR_ROWS], a);
-    be.stage("contigs");
-    be.launch_read(KR_HEADS, blocks_for(R, read_block[KR_HEADS]), read_block[KR_HEADS], a);
-    be.scan_u8(a.head, R, head_off);
-    be.stage("offsets");
-    be.scan_i32(a.tag_len, R, cs_off);
-    be.scan_i32(a.n_colon, R, rng_off);
-    int64_t C = 0, cs_bytes = 0, n_ranges = 0;
+    behind_rows();
     be.d2h(words, a.words, sizeof words);
-    be.d2h(&C, head_off + R, 8); be.d2h(&cs_bytes, cs_off + R, 8); be.d2h(&n_ranges, rng_off + R, 8);
     if (!be.ok()) return be.code();
     if (words[RW_FAULT] != INT32_MAX) return AASM_READ_FALLBACK;     // a row that is none: the first one in file order
     // ---- numbers off the fast path: the host's own parse_row decides, and patches the row's columns on the device
@@ -443,8 +426,57 @@ template <class B> int read_run(B &be, const char *text, int64_t len, int flags,
             be.h2d(a.qs + r, &w.qry_str, 8); be.h2d(a.qe + r, &w.qry_end, 8); be.h2d(a.rs + r, &w.ref_str, 8); be.h2d(a.re + r, &w.ref_end, 8);
             be.h2d(a.qtot + r, &w.qry_total, 8); be.h2d(a.rtot + r, &w.ref_total, 8); be.h2d(a.mat + r, &w.mat_num, 4); be.h2d(a.aln + r, &w.aln_len, 4);
             be.h2d(a.mq + r, &w.map_qul, 1);
+            if (a.aln64) be.h2d(a.aln64 + r, &w.aln_len64, 8);
         }
     }
+    return be.ok() ? AASM_OK : be.code();
+}
+
+// read_run(be, ...) over a backend that provides
+//   void *alloc(size_t)            device memory, nullptr after a failure (every later call is then a no-op); freed with the backend
+//   void release(void *)           ... or now;   void keep(void *): the caller's from here on
+//   h2d / d2h(dst, src, n)         d2h waits;   fill32(p, value, count)
+//   scan_i32 / scan_u8(in, n, out) exclusive scan into int64 out[n + 1]
+//   launch_read(kernel, blocks, threads, ReadArgs);   stage(name): a launch group's name, for timing;   bool ok()
+// text: HOST memory; under AASM_READ_TEXT_ON_DEVICE device memory, 16-byte aligned, that is neither copied nor written (paf is
+// nullptr then: the container is cut from host text).  paf: the container to fill, or nullptr; want_dev: hand the batch's arrays out
+// in `out` (else they are freed), under AASM_READ_ROW_COLS the row columns' arrays with them.
+// Returns AASM_OK, AASM_READ_FALLBACK, or the backend's failure as AASM_E_NOMEM / AASM_E_HIP through be.code().
+template <class B> int read_run(B &be, const char *text, int64_t len, int flags, aasm_paf *paf, bool want_dev, ReadOut &out) {
+    const int64_t max_blocks = (flags & AASM_READ_H_FEW_BLOCKS) ? 3 : AASM_READ_MAX_BLOCKS;   // (the hook: fewer blocks than items)
+    auto blocks_for = [&](int64_t items, int per_block) { return read_blocks_for(items, per_block, max_blocks); };
+    auto i64s = [&](int64_t n) { return (int64_t *)be.alloc((size_t)n * 8); };
+    auto i32s = [&](int64_t n) { return (int32_t *)be.alloc((size_t)n * 4); };
+    auto u8s = [&](int64_t n) { return (uint8_t *)be.alloc((size_t)n); };
+    ReadArgs a;
+    std::memset(&a, 0, sizeof a);
+    if (len <= 0) return AASM_READ_FALLBACK;
+    const bool on_dev = (flags & AASM_READ_TEXT_ON_DEVICE) != 0, row_cols = (flags & AASM_READ_ROW_COLS) != 0 && want_dev;
+    if (on_dev && paf) return AASM_E_INVAL;
+    be.stage("upload");
+    uint8_t *d_text = on_dev ? (uint8_t *)const_cast<char *>(text) : u8s(len);
+    if (!on_dev) be.h2d(d_text, text, (size_t)len);
+    a.text = d_text; a.len = len; a.weak_hash = (flags & AASM_READ_H_WEAK_HASH) ? 1 : 0;
+    // ---- row starts, rows, slow rows; the contig heads and both offset scans are enqueued behind the rows kernel
+    int64_t *head_off = nullptr, *cs_off = nullptr, *rng_off = nullptr;
+    int32_t words[RW_N];
+    const int frc = read_front(be, a, text, on_dev, max_blocks, words, false, [&] {
+        const int64_t R = a.R;
+        a.ref_chr = i32s(R); a.head = u8s(R); a.cnew = u8s(R);
+        head_off = i64s(R + 1); cs_off = i64s(R + 1); rng_off = i64s(R + 1);
+        a.head_off = head_off; a.cs_off = cs_off;
+        be.stage("contigs");
+        be.launch_read(KR_HEADS, blocks_for(R, read_block[KR_HEADS]), read_block[KR_HEADS], a);
+        be.scan_u8(a.head, R, head_off);
+        be.stage("offsets");
+        be.scan_i32(a.tag_len, R, cs_off);
+        be.scan_i32(a.n_colon, R, rng_off);
+    });
+    if (frc != AASM_OK) return frc;
+    const int64_t R = a.R, n_slow = words[RW_SLOW];
+    int64_t C = 0, cs_bytes = 0, n_ranges = 0;
+    be.d2h(&C, head_off + R, 8); be.d2h(&cs_bytes, cs_off + R, 8); be.d2h(&n_ranges, rng_off + R, 8);
+    if (!be.ok()) return be.code();
     // ---- contigs, reference names by first appearance
     be.stage("reference ids");
     const int64_t n_new = words[RW_NEW];

@@ -12,8 +12,12 @@
 //      IO, INVAL are the library's AASM_E_* codes.  "exit 1" prints the library's text, as the reference does for a bad file;
 //      "exit 2" prints "alignasm: solver failed (<rc>): <text>"; "exit 3" prints "alignasm: writing outputs failed: <text>".
 //
-//   1 no container   --device-reader --device-writer, no --alt (an empty alt file is none), --gpus <= 1
-//        aasm_paf_read_device_rows            PARSE, IO, NOMEM -> GoOn;  other -> exit 2.  Then the two stdout lines, once per run.
+//   1 no container   --device-reader --device-writer, --gpus <= 1, and no --alt (an empty alt file is none) or --device-alt
+//        aasm_paf_read_device_rows            PARSE, IO, NOMEM -> GoOn;  other -> exit 2.
+//        --device-alt with --alt: aasm_paf_merge_alt_device on the mapped alt file, the merged batch takes the resident one's place
+//                                             PARSE (a text the device declines, or a bad one), IO, NOMEM -> GoOn;  other -> exit 2
+//        Then the two stdout lines, once per run; after a device merge they wait until the route is sure to write, because the
+//        plain command says nothing before its message for a bad --alt file, and a tag the solve rejects is such a file.
 //        the warm-up threads are joined, then the device rows (below) without a container
 //        GoOn from here on means the plain command: host reader, both flags off, its messages and exit codes.
 //   - container read  aasm_paf_read_device with --device-reader (leaves the batch resident beside the container), else the host reader
@@ -36,7 +40,7 @@
 //                                     that session checks every row before it writes one);  every other result -> Written
 //
 // ---- --timing prints one line to stderr after a Written outcome: records, contigs, then
-//        read_s    start -> the batch is read (routes 2 - 5: merged and indexed too)
+//        read_s    start -> the batch is read (routes 2 - 5: merged and indexed too;  1 with --device-alt: merged on the device too)
 //        solve_s   routes 1 - 3, 5: read -> results ready for the writer;  4: the solver thread's busy time
 //        upload / device / fetch    1: wait for the arena / solve / sizes, export, plans;  2: the uploads / solve / sizes, export, plans;
 //                  3: 0 / solve / fetch;  4: sums of the ranges' stats.reserved_f[0], [2], [1];  5: the same of the one solve
@@ -56,6 +60,11 @@
 #include <iostream>
 #include <string>
 
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/alignasm_amd.h"
@@ -65,7 +74,7 @@ static double secs(clk::time_point a, clk::time_point b) { return std::chrono::d
 
 static void usage(std::ostream &os) {
     os << "Usage: alignasm [--help] [--version] [--thread THREAD] [--alt PAF_ALT_LOC] [--alt_baseline ALT_BASELINE] "
-          "[--non_skip_linkable] [--max-paths K] [--gpus N] [--device D] [--timing] [--host-ranges] [--device-reader] [--device-writer] PAF_LOC\n\n"
+          "[--non_skip_linkable] [--max-paths K] [--gpus N] [--device D] [--timing] [--host-ranges] [--device-reader] [--device-writer] [--device-alt] PAF_LOC\n\n"
           "Positional arguments:\n  PAF_LOC              Location of PAF file [required]\n\n"
           "Optional arguments:\n  -h, --help           shows help message and exits\n  -v, --version        prints version information and exits\n"
           "  -t, --thread THREAD  Number of host threads for reading / writing PAF [default: all]\n"
@@ -78,7 +87,9 @@ static void usage(std::ostream &os) {
           "  --timing             print read / solve / write wall time to stderr\n"
           "  --host-ranges        build the cs match ranges in the reader instead of on the GPU\n"
           "  --device-reader      frame and parse the PAF rows on the GPU (not with --host-ranges)\n"
-          "  --device-writer      format the output rows on the GPU (not with --host-ranges, not with --gpus above 1)\n";
+          "  --device-writer      format the output rows on the GPU (not with --host-ranges, not with --gpus above 1)\n"
+          "  --device-alt         with --device-reader --device-writer: merge the --alt file on the GPU into the resident batch\n"
+          "                       (not with --host-ranges, not with --gpus above 1)\n";
 }
 
 struct Cli {
@@ -87,7 +98,7 @@ struct Cli {
     int gpus = 1;
     double alt_baseline = 0.5;
     bool use_alt = false;                                                       // --alt with a file that is not empty
-    bool timing = false, host_ranges = false, device_reader = false, device_writer = false;
+    bool timing = false, host_ranges = false, device_reader = false, device_writer = false, device_alt = false;
 };
 
 // -1: go on with cli;  else the exit code (--help, --version, a usage error)
@@ -108,6 +119,7 @@ static int parse_args(int argc, char **argv, Cli &cli) {
         else if (a == "--host-ranges") cli.host_ranges = true;
         else if (a == "--device-reader") cli.device_reader = true;
         else if (a == "--device-writer") cli.device_writer = true;
+        else if (a == "--device-alt") cli.device_alt = true;
         else if (a == "-a" || a == "--alt") cli.alt_loc = need("--alt");
         else if (a == "-b" || a == "--alt_baseline") cli.alt_baseline = std::atof(need("--alt_baseline"));
         else if (a == "--non_skip_linkable") cli.opts.non_skip_linkable = 1;
@@ -120,7 +132,9 @@ static int parse_args(int argc, char **argv, Cli &cli) {
     }
     if (cli.host_ranges && cli.device_reader) { std::cerr << "--device-reader: not with --host-ranges\n"; bad = true; }
     if (cli.host_ranges && cli.device_writer) { std::cerr << "--device-writer: not with --host-ranges\n"; bad = true; }
+    if (cli.host_ranges && cli.device_alt) { std::cerr << "--device-alt: not with --host-ranges\n"; bad = true; }
     if (cli.gpus > 1 && cli.device_writer) { std::cerr << "--device-writer: not with --gpus above 1\n"; bad = true; }
+    if (cli.gpus > 1 && cli.device_alt) { std::cerr << "--device-alt: not with --gpus above 1\n"; bad = true; }
     if (bad || cli.paf_loc.empty()) { usage(std::cerr); return 1; }             // alignasm.cpp:59-65
     for (const std::string *loc : {&cli.paf_loc, &cli.alt_loc}) {               // :67-72, :186-201
         if (loc->empty() || std::filesystem::path(*loc).extension() == ".paf") continue;
@@ -174,6 +188,7 @@ struct Run {
     aasm_batch_in dev_view, view;
     std::string in, f_main, f_alt, f_all;
     bool said_read = false;
+    int64_t held_contigs = -1;
 
     explicit Run(const Cli &c) : cli(c) {
         tm.t0 = tm.t1 = tm.t2 = clk::now();
@@ -196,11 +211,18 @@ struct Run {
     }
     void join_warm() { for (auto &t : warm) if (t.joinable()) t.join(); }
     void drop_upload() { aasm_upload_free(up); up = nullptr; }
-    void say_read(int64_t n_contigs, int64_t n_records) {                       // once per run: a route that falls back has said it
-        if (!said_read) std::cout << "File read complete" << std::endl << "Analyze PAF " << n_contigs << " data in parallel" << std::endl;   // :340, :349
-        said_read = true;
+    // hold: the lines wait until the route is sure to write (said_held): the plain command says nothing before a bad --alt file's
+    // message, and a tag the device merge leaves to the solve is such a file
+    void say_read(int64_t n_contigs, int64_t n_records, bool hold = false) {    // once per run: a route that falls back has said it
+        held_contigs = hold ? n_contigs : -1;
+        if (!hold) say_lines(n_contigs);
         tm.n_contigs = n_contigs; tm.n_records = n_records;
         tm.t1 = tm.t2 = clk::now();
+    }
+    void say_held() { if (held_contigs >= 0) say_lines(held_contigs); held_contigs = -1; }
+    void say_lines(int64_t n_contigs) {
+        if (!said_read) std::cout << "File read complete" << std::endl << "Analyze PAF " << n_contigs << " data in parallel" << std::endl;   // :340, :349
+        said_read = true;
     }
 };
 
@@ -261,6 +283,7 @@ static Outcome device_rows(Run &run, const aasm_row_cols &cols, const aasm_paf *
     if (rc == AASM_E_NOMEM || (!container && (rc == AASM_E_PARSE || rc == AASM_E_INVAL))) { (void)aasm_writer_close(wr, 0); return {Outcome::GoOn, rc}; }
     tm.upload_s = secs(tm.t1, tu); tm.device_s = secs(tu, ts); tm.fetch_s = secs(ts, tm.t2); tm.solve_busy_s = secs(tm.t1, tm.t2);   // (upload: what the caller did since t1; fetch: sizes, export and plans)
     report_internal(st.n_internal_errors);
+    run.say_held();
     std::cout << "Write output PAF file" << std::endl;                          // :487
     const std::string msg = rc != AASM_OK ? aasm_last_error() : "";
     const int crc = aasm_writer_close(wr, rc == AASM_OK ? 1 : 0);
@@ -271,13 +294,34 @@ static Outcome device_rows(Run &run, const aasm_row_cols &cols, const aasm_paf *
     return {Outcome::Written, rc};
 }
 
-// ---- 1: no container: read -> solve -> sizes -> export -> cut plans -> device writer, all from resident arrays
+// --device-alt: the alt file, mapped, joins the resident batch on the device; the merged batch and its columns take their place
+static int merge_alt_on_device(Run &run, aasm_row_cols &cols) {
+    const std::string path = std::filesystem::absolute(run.cli.alt_loc).string();
+    const int fd = ::open(path.c_str(), O_RDONLY);
+    struct stat st;
+    if (fd < 0 || ::fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0) { if (fd >= 0) ::close(fd); return AASM_E_IO; }
+    void *m = ::mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    ::close(fd);
+    if (m == MAP_FAILED) return AASM_E_IO;
+    aasm_upload *merged = nullptr;
+    aasm_batch_in merged_view;
+    aasm_row_cols merged_cols;
+    const int rc = aasm_paf_merge_alt_device(&run.dev_view, &cols, (const char *)m, (int64_t)st.st_size, run.cli.alt_baseline, 0, run.cli.opts.device, &merged, &merged_view, &merged_cols);
+    ::munmap(m, (size_t)st.st_size);
+    if (rc != AASM_OK) return rc;
+    run.drop_upload();
+    run.up = merged; run.dev_view = merged_view; cols = merged_cols;
+    return AASM_OK;
+}
+
+// ---- 1: no container: read -> [--alt merge] -> solve -> sizes -> export -> cut plans -> device writer, all from resident arrays
 static Outcome route_no_container(Run &run) {
     aasm_row_cols cols;
-    const int rc = aasm_paf_read_device_rows(run.in.c_str(), 0, run.cli.opts.device, nullptr, &run.up, &run.dev_view, &cols);
-    if (rc == AASM_E_PARSE || rc == AASM_E_IO || rc == AASM_E_NOMEM) return {Outcome::GoOn, rc};
+    int rc = aasm_paf_read_device_rows(run.in.c_str(), 0, run.cli.opts.device, nullptr, &run.up, &run.dev_view, &cols);
+    if (rc == AASM_OK && run.cli.use_alt) rc = merge_alt_on_device(run, cols);
+    if (rc == AASM_E_PARSE || rc == AASM_E_IO || rc == AASM_E_NOMEM) { run.drop_upload(); return {Outcome::GoOn, rc}; }
     if (rc != AASM_OK) return solver_failed(rc, aasm_last_error());
-    run.say_read(run.dev_view.n_contigs, run.dev_view.n_records);
+    run.say_read(run.dev_view.n_contigs, run.dev_view.n_records, run.cli.use_alt);
     // The device read holds the context's lock from start to end, so a warm-up that came second is still waiting to make the
     // arena.  It is waited for here: a solve that got the lock first would grow the arena block by block between its kernels.
     run.join_warm();
@@ -434,7 +478,7 @@ int main(int argc, char **argv) {
     run.warm_up();
     Outcome o{Outcome::GoOn, AASM_OK};
     bool device_reader = cli.device_reader, device_writer = cli.device_writer;
-    if (device_reader && device_writer && !cli.use_alt && cli.gpus <= 1) {
+    if (device_reader && device_writer && (!cli.use_alt || cli.device_alt) && cli.gpus <= 1) {
         o = route_no_container(run);
         device_reader = device_writer = false;                                  // done; or on with the host reader, as the command without the two flags
     }

@@ -493,6 +493,29 @@ typedef struct aasm_row_cols {
 /* the row columns of contigs [c0, c1) of a container (after a --alt merge too), uploaded once; release with aasm_upload_free */
 int  aasm_paf_upload_rows(const aasm_paf *paf, int64_t c0, int64_t c1, int device, aasm_upload **up, aasm_row_cols *dev_cols);
 
+/* The --alt merge on the device: the second PAF joins a batch that is resident in its cs form (cs_text / rec_cs_off, rng_* NULL)
+ * with its row columns - what aasm_paf_parse_device_rows gives, or aasm_upload_batch plus aasm_paf_upload_rows.  The merged batch
+ * equals, array for array and byte for byte, aasm_paf_parse_mem_opts(main, AASM_READ_DEVICE_RANGES) -> aasm_paf_merge_alt_mem(alt,
+ * baseline) -> aasm_paf_batch / aasm_paf_upload_rows(0, C): every contig is its main records followed by the kept alt rows in
+ * alt-file order, rec_rng_off holds the ':' counts, row_index is the alt row's number among the non-empty lines (cord_type 1), new
+ * reference names are numbered behind the main file's in first-appearance order over all alt rows and appended to `names`.
+ *   dev_in, dev_cols  DEVICE arrays, read only, never freed; the input batch stays usable whatever the call returns.
+ *   alt_text          HOST memory, the bytes of the alt PAF.  A text without rows gives a merged batch equal to the input.
+ *   flags             0; AASM_READ_H_WEAK_HASH, AASM_READ_H_FEW_BLOCKS: the reader's test hooks, for every table and grid of the merge.
+ *   *up               a new handle that owns every array of *merged_view and *merged_cols (one aasm_upload_free); NULL on failure.
+ * Declined texts (AASM_E_PARSE, nothing built, counter "alt_host_verdicts"): a row with fewer than 12 columns, without a cs:Z: tag
+ * or with a number that is none; a piece name that is not <name>:<1 - 18 digits>[-...]; a group of rows without a positive
+ * aln_len / qry_total ratio (its zeroed stand-in is the host's to rebuild); more than INT32_MAX records.  The host's own scan of
+ * the alt rows then speaks: if it finds the text bad, the message is its text for the first bad row in file order, else
+ * "aasm_paf_merge_alt_device: the device does not merge this alt text (<reason>, alt row <n>); merge on the host".
+ * A malformed cs tag in an otherwise well-formed alt row is NOT found here (the host merge finds it): as with
+ * AASM_READ_DEVICE_RANGES it is reported by the solve of the merged batch, AASM_E_PARSE.  Numbers off the fast path are resolved by
+ * the host, row by row.  Other errors: AASM_E_INVAL (a NULL or host pointer where device memory is required, a batch with rng_* or
+ * without cs_text, a negative alt_len; nothing enqueued), AASM_E_NODEVICE, AASM_E_NOMEM, AASM_E_HIP (never retried).
+ * aasm_debug_counter "alt_device_merges": merges the device completed.                                                        */
+int  aasm_paf_merge_alt_device(const aasm_batch_in *dev_in, const aasm_row_cols *dev_cols, const char *alt_text, int64_t alt_len, double alt_baseline,
+                               int flags, int device, aasm_upload **up, aasm_batch_in *merged_view, aasm_row_cols *merged_cols);
+
 typedef struct aasm_dev_rows { int64_t *main_off, *alt_off, *all_off; } aasm_dev_rows;  /* DEVICE, caller-owned: [n_main+1], [n_alt+1], [n_all_elems+1] */
 typedef struct aasm_rows_info {
     int64_t bytes[3];          /* text bytes of main / alt / all */
