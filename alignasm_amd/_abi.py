@@ -290,7 +290,7 @@ class HostBatch:
 
 
 # ---- k shortest walks on caller graphs (aasm_k_shortest_walks) ----------------------------------------------------------------
-AASM_KSW_WALKS, AASM_KSW_TREE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA = 0x1, 0x2, 0x4, 0x100
+AASM_KSW_WALKS, AASM_KSW_TREE, AASM_KSW_CYCLES, AASM_KSW_NEGATIVE, AASM_KSW_HOOK_ARENA = 0x1, 0x2, 0x4, 0x8, 0x100
 
 
 class KswOut(C.Structure):
@@ -327,6 +327,17 @@ def graph_inputs(g_voff, rowptr, col, source, sink=None, w5=None, cost=None, sca
         if a is not None and len(a) // width < n:
             raise ValueError(f"{name}: {len(a) // width} rows, {n} needed")
     return g_voff, rowptr, col, source, sink, w5, cost
+
+
+def bellman_ford_outputs(g_voff):
+    """The caller's arrays of aasm_sssp_bellman_ford for a batch: d5 [VT, 5], prev [VT], status [G], cycle_off [G + 1], cycle [VT + G]."""
+    G, VT = len(g_voff) - 1, int(g_voff[-1])
+    return (np.zeros((VT, 5), np.int64), np.zeros(VT, np.int32), np.zeros(G, np.int32), np.zeros(G + 1, np.int64), np.zeros(VT + G, np.int32))
+
+
+def unpack_cycles(cycle_off, cycle):
+    """Per graph its cycle as an int32 array (empty where none was reported)."""
+    return [cycle[int(cycle_off[g]):int(cycle_off[g + 1])].copy() for g in range(len(cycle_off) - 1)]
 
 
 def ksw_inputs(g_voff, rowptr, col, w, source, sink):

@@ -14,8 +14,8 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
-                   DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, graph_inputs, ksw_inputs, make_opts, unpack_ksw, unpack_out)
+from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+                   DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, bellman_ford_outputs, graph_inputs, ksw_inputs, unpack_cycles, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AASM_LIB_OVERRIDE") or os.path.join(_HERE, "libalignasm_amd.so")   # override: diagnostic builds (tools/)
@@ -89,7 +89,7 @@ LIB = _load()
 EXPORTED = [
     "aasm_abi_version", "aasm_device_count", "aasm_init", "aasm_last_error", "aasm_solve_batch", "aasm_solve_batch_multi", "aasm_solve_device",
     "aasm_result_stats", "aasm_result_fetch", "aasm_result_free", "aasm_free_out", "aasm_upload_batch", "aasm_upload_free",
-    "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_poison", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
+    "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_sssp_bellman_ford", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_poison", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
     "aasm_paf_parse_device", "aasm_paf_read_device", "aasm_paf_parse_device_rows", "aasm_paf_read_device_rows",
@@ -123,7 +123,20 @@ def sssp_dijkstra(g_voff, rowptr, col, w5, src, device=0):
     return d, prev
 
 
-def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=False, device=0, _hooks=0, cycles=False):
+def sssp_bellman_ford(g_voff, rowptr, col, w5, src, device=0):
+    """bellman_ford() of the reference's solver (k_shortest_walks.hpp:91-129) on the GPU over a batch of graphs whose edges may
+    have negative score sums.  Returns (d: [V, 5] int64, prev: [V] int32, status: [G] int32, cycles: a list of int32 arrays).
+    status 0: d / prev are the reference's vectors; 1: a negative cycle, d is max and prev -1 for that graph and cycles[g] holds
+    the closed cycle (first entry == last entry, edge direction, local ids); < 0: an AASM_E_* for that graph alone."""
+    g_voff, rowptr, col, src, _, w5, _ = graph_inputs(g_voff, rowptr, col, src, w5=w5)
+    d, prev, status, cycle_off, cycle = bellman_ford_outputs(g_voff)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(LIB.aasm_sssp_bellman_ford(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(src), P(d), P(prev), P(status),
+                                      P(cycle_off), P(cycle), int(device)))
+    return d, prev, status, unpack_cycles(cycle_off, cycle)
+
+
+def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=False, device=0, _hooks=0, cycles=False, negative=False):
     """k_shortest_walks(source, sink, k) of the reference's solver with is_dag = true, and every walk recovered
     (k_shortest_walks.hpp:177-290), on the GPU over a batch of DAGs in sssp_dijkstra's layout.  w: [E, 5] int64
     {qry_score, ref_score, anom, qul_nonzero, qul_total} or [E] (scalar weights, taken as (w, 0, 0, 0, 1)).
@@ -133,9 +146,11 @@ def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=F
     cycles=True solves every graph as the solver does with is_dag = false (the tree of dijkstra() from the sink): graphs may
     hold cycles, and walks may repeat vertices and pass through the sink.  status is then AASM_E_OVERFLOW for a graph that
     meets one of the limits include/alignasm_amd.h lists (a cycle that improves a distance for ever, distances out of range,
-    more than 2^28 walk edges) and AASM_E_INVAL for one whose best[] is no tree into the sink."""
+    more than 2^28 walk edges) and AASM_E_INVAL for one whose best[] is no tree into the sink.
+    negative=True accepts edges whose score sum is negative; with cycles=True the tree is then the one bellman_ford() leaves
+    (negative_edge = true), and a graph with a negative cycle gets AASM_E_INVAL and no walks."""
     g_voff, rowptr, col, w5, source, sink = ksw_inputs(g_voff, rowptr, col, w, source, sink)
-    flags = (AASM_KSW_WALKS if walks else 0) | (AASM_KSW_TREE if tree else 0) | (AASM_KSW_CYCLES if cycles else 0) | int(_hooks)
+    flags = (AASM_KSW_WALKS if walks else 0) | (AASM_KSW_TREE if tree else 0) | (AASM_KSW_CYCLES if cycles else 0) | (AASM_KSW_NEGATIVE if negative else 0) | int(_hooks)
     out = KswOut()
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     rc = LIB.aasm_k_shortest_walks(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(source), P(sink), C.c_int64(int(k)),

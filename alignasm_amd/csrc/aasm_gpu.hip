@@ -67,7 +67,7 @@ AASM_PIPELINE_KERNELS(K, KL)
 #define AASM_FAMILY (PackArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_PACK_KERNELS(K, KL)
 #undef AASM_FAMILY
-// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, K5 Dial) ...
+// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, ★L bellman_ford, K5 Dial) ...
 #define AASM_FAMILY (SsspArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_SSSP_KERNELS(K, KL)
 #undef AASM_FAMILY
@@ -1025,6 +1025,16 @@ int aasm_sssp_dijkstra(int64_t n_graphs, const int64_t *g_voff, const int64_t *r
     const char *why = "";
     const int rc = dijkstra_check_args(n_graphs, g_voff, rowptr, col, w5, src, d5, prev, &why);
     return graph_entry("aasm_sssp_dijkstra", rc, why, device, [&](GraphGpu &be) { return dijkstra_run(be, n_graphs, g_voff, rowptr, col, w5, src, d5, prev, &why); });
+}
+
+// bellman_ford (k_shortest_walks.hpp:91-129) over a batch of graphs; host pointers in and out
+int aasm_sssp_bellman_ford(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                           const int32_t *src, int64_t *d5, int32_t *prev, int32_t *status, int64_t *cycle_off, int32_t *cycle, int device) {
+    const char *why = "";
+    const int rc = bellman_ford_check_args(n_graphs, g_voff, rowptr, col, w5, src, d5, prev, status, cycle_off, cycle, &why);
+    return graph_entry("aasm_sssp_bellman_ford", rc, why, device, [&](GraphGpu &be) {
+        return bellman_ford_run(be, n_graphs, g_voff, rowptr, col, w5, src, d5, prev, status, cycle_off, cycle, nullptr, &why);
+    });
 }
 
 // Dial's bucketed BFS (k_weighted_bfs.hpp:16-37) over a batch of graphs; host pointers in and out

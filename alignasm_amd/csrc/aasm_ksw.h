@@ -1,6 +1,6 @@
 // aasm_ksw.h -- batched k shortest walks on caller-supplied graphs (row ★K): the solver's k_shortest_walks()
-// (k_shortest_walks.hpp:177-249) with is_dag = true, or with is_dag = false, negative_edge = false under AASM_KSW_CYCLES, and
-// kth_shortest_walk_recover() (:252-290), one workgroup per graph.
+// (k_shortest_walks.hpp:177-249) with is_dag = true, or with is_dag = false under AASM_KSW_CYCLES (negative_edge = true with
+// AASM_KSW_NEGATIVE beside it), and kth_shortest_walk_recover() (:252-290), one workgroup per graph.
 //
 // Kernel bodies (KCtx style, so tests/host_emul/graphs_emul.cpp compiles them for one lane on the host):
 //   kb_ksw_tree   reversed CSR in the reference's list order (:180-183), Kahn order of the reversed graph (:132-156) fused
@@ -10,6 +10,7 @@
 //   kb_ksw_tree_cyc   the same stage for graphs that may hold cycles: the tree is the one dijkstra() from the sink over the
 //                 reversed graph leaves (:69-87, kb_sssp_dijkstra's formulation), with a bound on its pushes and a guard that
 //                 best[] is a tree into the sink; the number of walks is k as soon as a cycle lies between source and sink
+//   kb_ksw_tree_bf    the same with the tree of bellman_ford() (:91-129, bf_spfa's formulation): negative weights, no bound on pushes
 //   kb_ksw_heap   the persistent leftist heaps (:196-215, leftist_heap.hpp:29-40) in the reference's allocation order
 //   kb_ksw_enum   k pops of the min-queue of (distance, node, insertion index) (:230-249): ties by arena index, the
 //                 monotonic allocator's order (hazard B3)
@@ -63,7 +64,8 @@ struct KswArgs {
     int32_t *qnode, *qprev, *rlast;
     Dist *rdist;
     int64_t *woff, *wedges;
-    // AASM_KSW_CYCLES: graph g's dijkstra heap is [hoff[g], hoff[g + 1]) of dheap (empty: the graph is left as it is)
+    // AASM_KSW_CYCLES: graph g's dijkstra heap is [hoff[g], hoff[g + 1]) of dheap (empty: the graph is left as it is); with
+    // AASM_KSW_NEGATIVE its bellman_ford queue ring
     int32_t cycles;
     const int64_t *hoff;
     DjEnt *dheap;
@@ -164,76 +166,38 @@ AASM_DEV void kb_ksw_tree(const KCtx &k, const KswArgs &a) {
     ksw_tree_bfs(a, g);                                              // (the Kahn countdown deg[] is 0 everywhere now)
 }
 
-// ---- stage 1-2 under AASM_KSW_CYCLES: the tree of dijkstra() from the sink over the reversed graph (:185, :69-87) ---------------
-// kb_sssp_dijkstra's formulation on the reversed lists: wave-uniform control, lane 0 stores; bedge[to] is the edge whose
-// relaxation last set best[to].  CALC_SUM's third key is not monotone under addition (a larger qnz / qtot ratio is "smaller"),
-// so a cycle can improve a distance for ever while the heap holds a few entries: the pushes are counted and a graph that makes
-// more than 64 * (E + 2) of them ends with AASM_E_OVERFLOW (the reference does not return on it).  A graph whose heap room
-// runs out first is marked ins = -1 and run again by the host with more.  The rest runs on lane 0 as kb_ksw_tree.
-AASM_DEV void kb_ksw_tree_cyc(const KCtx &k, const KswArgs &a) {
-    const int64_t g = k.bid;
-    if (g >= a.n_graphs || k.tid >= AASM_WAVE) return;
-    const int64_t cap = a.hoff[g + 1] - a.hoff[g];
-    if (cap <= 0) return;                                            // solved with less heap room
-    const int lane = k.lane;
+// What the two tree kernels for graphs with cycles share, on one lane.  ksw_cyc_prepare: every per-vertex array at its start value
+// and the reversed lists, g_rev[v] as in kb_ksw_tree (ascending edge id within a head).  ksw_cyc_tail, after the tree is found: the
+// tree guard, the BFS with the insert count, and the bound on the number of walks.
+AASM_DEV void ksw_cyc_prepare(const KswArgs &a, int64_t g) {
     const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], E = a.rowptr[vb + V] - eb;
-    const int32_t s = a.src[g], t = a.sink[g];
-    int32_t *roff = a.roff + vb, *deg = a.deg + vb, *order = a.order + vb, *best = a.best + vb, *bedge = a.bedge + vb;
-    int32_t *koff = a.koff + vb, *kids = a.kids + vb, *depth = a.depth + vb;
+    int32_t *roff = a.roff + vb, *deg = a.deg + vb, *best = a.best + vb, *bedge = a.bedge + vb, *koff = a.koff + vb, *depth = a.depth + vb;
     int32_t *rev = a.rev + eb, *etail = a.etail + eb;
     Dist *d = a.d + vb;
     int64_t *cnt = a.cnt + vb;
     const int64_t *rp = a.rowptr + vb;
     const int32_t *col = a.col + eb;
-    if (lane == 0) {
-        for (int64_t v = 0; v < V; v++) {
-            roff[v] = 0; d[v] = dist_max(); best[v] = -1; bedge[v] = -1; cnt[v] = 0; depth[v] = -1; deg[v] = 0;
-            for (int64_t e = rp[v] - eb; e < rp[v + 1] - eb; e++) etail[e] = (int32_t)v;
-        }
-        // g_rev[v] as in kb_ksw_tree: ascending edge id within a head
-        for (int64_t e = 0; e < E; e++) roff[col[e]]++;
-        int32_t run = 0;
-        for (int64_t v = 0; v < V; v++) { const int32_t c = roff[v]; roff[v] = run; run += c; }
-        for (int64_t v = 0; v < V; v++) koff[v] = roff[v];
-        for (int64_t e = 0; e < E; e++) rev[koff[col[e]]++] = (int32_t)e;
-        d[t] = dist_zero();                                          // IDENTITY_DISTANCE (:73)
+    for (int64_t v = 0; v < V; v++) {
+        roff[v] = 0; d[v] = dist_max(); best[v] = -1; bedge[v] = -1; cnt[v] = 0; depth[v] = -1; deg[v] = 0;
+        for (int64_t e = rp[v] - eb; e < rp[v + 1] - eb; e++) etail[e] = (int32_t)v;
     }
-    wave_fence();
-    DjEnt *H = a.dheap + a.hoff[g];
-    const int64_t push_lim = AASM_KSW_DJ_PUSHES * (E + 2);
-    int64_t n = 0, pushes = 0;
-    int over = 0;                                                    // 1: heap room, 2: the bound on pushes
-    auto push = [&](const Dist &dd, int32_t v) {
-        if (++pushes > push_lim) { over = 2; return; }
-        if (n >= cap) { over = 1; return; }
-        dj_heap_push(H, n, lane, dd, v);
-    };
-    push(dist_zero(), t);
-    while (n > 0 && !over) {
-        const DjEnt top = dj_heap_pop(H, n, lane);
-        const int32_t v = uni(top.v);
-        const Dist dv = uni(top.d);
-        if (!uni(dist_eq(dv, d[v]))) continue;                       // :77 (operator!=)
-        const int64_t r0 = uni((int64_t)roff[v]), r1 = v + 1 < V ? uni((int64_t)roff[v + 1]) : E;
-        for (int64_t r = r0; r < r1 && !over; r++) {
-            const int32_t e = uni(rev[r]), to = uni(etail[e]);
-            const Dist cand = uni(dist_add(dv, edge_w5(a.w5, eb + e)));
-            if (uni(dist_lt<CALC_SUM_MODE>(cand, d[to]))) {          // d_[to] > dv + w (:79)
-                if (lane == 0) { d[to] = cand; best[to] = v; bedge[to] = e; }
-                wave_fence();
-                push(cand, to);
-            }
-        }
-    }
-    if (lane != 0) return;
-    a.nbfs[g] = 0; a.ins[g] = 0; a.walks[g] = 0;
-    if (over) {
-        a.status[g] = AASM_E_OVERFLOW;
-        if (over == 1) a.ins[g] = -1;
-        for (int64_t v = 0; v < V; v++) { d[v] = dist_max(); best[v] = -1; bedge[v] = -1; }
-        d[t] = dist_zero();
-        return;
-    }
+    for (int64_t e = 0; e < E; e++) roff[col[e]]++;
+    int32_t run = 0;
+    for (int64_t v = 0; v < V; v++) { const int32_t c = roff[v]; roff[v] = run; run += c; }
+    for (int64_t v = 0; v < V; v++) koff[v] = roff[v];
+    for (int64_t e = 0; e < E; e++) rev[koff[col[e]]++] = (int32_t)e;
+    d[a.sink[g]] = dist_zero();                                      // IDENTITY_DISTANCE (:73)
+}
+AASM_DEV void ksw_cyc_tail(const KswArgs &a, int64_t g) {
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], E = a.rowptr[vb + V] - eb;
+    const int32_t s = a.src[g], t = a.sink[g];
+    int32_t *roff = a.roff + vb, *deg = a.deg + vb, *order = a.order + vb;
+    int32_t *koff = a.koff + vb, *kids = a.kids + vb;
+    int32_t *rev = a.rev + eb, *etail = a.etail + eb;
+    Dist *d = a.d + vb;
+    int64_t *cnt = a.cnt + vb;
+    const int64_t *rp = a.rowptr + vb;
+    const int32_t *col = a.col + eb;
     // best[] must be a tree into the sink: the BFS from the sink over tree[] visits every vertex with a distance, once (where it
     // is none - the sink's own distance improved round a cycle - the reference's BFS does not end)
     int64_t fin = 0;
@@ -278,6 +242,94 @@ AASM_DEV void kb_ksw_tree_cyc(const KCtx &k, const KswArgs &a) {
         }
     }
     a.walks[g] = tail < nS ? a.k : cnt[s];
+}
+
+// ---- stage 1-2 under AASM_KSW_CYCLES: the tree of dijkstra() from the sink over the reversed graph (:185, :69-87) ---------------
+// kb_sssp_dijkstra's formulation on the reversed lists: wave-uniform control, lane 0 stores; bedge[to] is the edge whose
+// relaxation last set best[to].  CALC_SUM's third key is not monotone under addition (a larger qnz / qtot ratio is "smaller"),
+// so a cycle can improve a distance for ever while the heap holds a few entries: the pushes are counted and a graph that makes
+// more than 64 * (E + 2) of them ends with AASM_E_OVERFLOW (the reference does not return on it).  A graph whose heap room
+// runs out first is marked ins = -1 and run again by the host with more.  The rest runs on lane 0 as kb_ksw_tree.
+AASM_DEV void kb_ksw_tree_cyc(const KCtx &k, const KswArgs &a) {
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs || k.tid >= AASM_WAVE) return;
+    const int64_t cap = a.hoff[g + 1] - a.hoff[g];
+    if (cap <= 0) return;                                            // solved with less heap room
+    const int lane = k.lane;
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], E = a.rowptr[vb + V] - eb;
+    const int32_t t = a.sink[g];
+    int32_t *roff = a.roff + vb, *best = a.best + vb, *bedge = a.bedge + vb;
+    int32_t *rev = a.rev + eb, *etail = a.etail + eb;
+    Dist *d = a.d + vb;
+    if (lane == 0) ksw_cyc_prepare(a, g);
+    wave_fence();
+    DjEnt *H = a.dheap + a.hoff[g];
+    const int64_t push_lim = AASM_KSW_DJ_PUSHES * (E + 2);
+    int64_t n = 0, pushes = 0;
+    int over = 0;                                                    // 1: heap room, 2: the bound on pushes
+    auto push = [&](const Dist &dd, int32_t v) {
+        if (++pushes > push_lim) { over = 2; return; }
+        if (n >= cap) { over = 1; return; }
+        dj_heap_push(H, n, lane, dd, v);
+    };
+    push(dist_zero(), t);
+    while (n > 0 && !over) {
+        const DjEnt top = dj_heap_pop(H, n, lane);
+        const int32_t v = uni(top.v);
+        const Dist dv = uni(top.d);
+        if (!uni(dist_eq(dv, d[v]))) continue;                       // :77 (operator!=)
+        const int64_t r0 = uni((int64_t)roff[v]), r1 = v + 1 < V ? uni((int64_t)roff[v + 1]) : E;
+        for (int64_t r = r0; r < r1 && !over; r++) {
+            const int32_t e = uni(rev[r]), to = uni(etail[e]);
+            const Dist cand = uni(dist_add(dv, edge_w5(a.w5, eb + e)));
+            if (uni(dist_lt<CALC_SUM_MODE>(cand, d[to]))) {          // d_[to] > dv + w (:79)
+                if (lane == 0) { d[to] = cand; best[to] = v; bedge[to] = e; }
+                wave_fence();
+                push(cand, to);
+            }
+        }
+    }
+    if (lane != 0) return;
+    a.nbfs[g] = 0; a.ins[g] = 0; a.walks[g] = 0;
+    if (over) {
+        a.status[g] = AASM_E_OVERFLOW;
+        if (over == 1) a.ins[g] = -1;
+        for (int64_t v = 0; v < V; v++) { d[v] = dist_max(); best[v] = -1; bedge[v] = -1; }
+        d[t] = dist_zero();
+        return;
+    }
+    ksw_cyc_tail(a, g);
+}
+
+// ---- stage 1-2 under AASM_KSW_CYCLES | AASM_KSW_NEGATIVE: the tree of bellman_ford() from the sink over the reversed graph (:186) --
+// bf_spfa (aasm_sssp.h) on the reversed lists, bedge[to] again the edge whose relaxation last set best[to].  The queue room is exact
+// (2 * (E + 2) entries, from the driver), so there are no retry rounds, and the algorithm always ends: dijkstra's bound on pushes
+// does not apply.  A graph with a negative cycle has no distance vector in the reference (k_shortest_walks would index an empty
+// one): AASM_E_INVAL, no walks, d / best as max / -1.  The rest runs on lane 0 as kb_ksw_tree_cyc.
+AASM_DEV void kb_ksw_tree_bf(const KCtx &k, const KswArgs &a) {
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs || k.tid >= AASM_WAVE) return;
+    const int lane = k.lane;
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, eb = a.rowptr[vb], E = a.rowptr[vb + V] - eb;
+    int32_t *roff = a.roff + vb, *best = a.best + vb, *bedge = a.bedge + vb;
+    int32_t *rev = a.rev + eb, *etail = a.etail + eb;
+    Dist *d = a.d + vb;
+    if (lane == 0) ksw_cyc_prepare(a, g);
+    wave_fence();
+    int32_t at = -1;
+    int64_t high = 0;
+    const int st = bf_spfa<AASM_BF_CHUNK>(lane, V, a.sink[g], d, a.w5, a.dheap + a.hoff[g], a.hoff[g + 1] - a.hoff[g],
+        [&](int32_t x, int64_t &r0, int64_t &r1) { r0 = uni((int64_t)roff[x]); r1 = x + 1 < V ? uni((int64_t)roff[x + 1]) : E; },
+        [&](int64_t r, int64_t &e, int32_t &nx) { const int32_t el = rev[r]; e = eb + el; nx = etail[el]; },
+        [&](int32_t nx, int32_t x, int64_t e) { best[nx] = x; bedge[nx] = (int32_t)(e - eb); }, at, high);
+    if (lane != 0) return;
+    a.nbfs[g] = 0; a.ins[g] = 0; a.walks[g] = 0;
+    if (st != BF_DONE) {
+        a.status[g] = st == BF_CYCLE ? AASM_E_INVAL : AASM_E_INTERNAL;
+        for (int64_t v = 0; v < V; v++) { d[v] = dist_max(); best[v] = -1; bedge[v] = -1; }
+        return;
+    }
+    ksw_cyc_tail(a, g);
 }
 
 // heap_insert (leftist_heap.hpp:29-40) without recursion: the right spine below which the key goes is walked down first,
@@ -495,14 +547,14 @@ static inline int ksw_check_args(int64_t n_graphs, const int64_t *g_voff, const 
     int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, source, {w5, sink, out}, why);
     if (rc != AASM_OK) return rc;
     if (k < 1 || k > AASM_KSW_MAX_K) return check_fail(why, AASM_E_INVAL, "k outside 1 .. 2^24");
-    if (flags & ~(AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_CYCLES | AASM_KSW_HOOK_ARENA)) return check_fail(why, AASM_E_INVAL, "unknown flag");
+    if (flags & ~(AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_CYCLES | AASM_KSW_NEGATIVE | AASM_KSW_HOOK_ARENA)) return check_fail(why, AASM_E_INVAL, "unknown flag");
     for (int64_t g = 0; g < n_graphs; g++) {
         const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
         if (sink[g] < 0 || sink[g] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": sink outside it");
         if (v1 - v0 > AASM_KSW_MAX_V) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(g) + ": more than 2^20 vertices");
         if (rowptr[v1] - rowptr[v0] > INT32_MAX) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(g) + ": 2^31 edges or more");
     }
-    return check_w5(w5, rowptr[g_voff[n_graphs]], why);
+    return check_w5(w5, rowptr[g_voff[n_graphs]], (flags & AASM_KSW_NEGATIVE) != 0, why);
 }
 
 static inline void ksw_free_out(aasm_ksw_out *o) {
@@ -519,7 +571,8 @@ static inline void ksw_free_out(aasm_ksw_out *o) {
     K(KSW_K_HEAP, aasm_ksw_heap, 64, 1, kb_ksw_heap)   \
     K(KSW_K_ENUM, aasm_ksw_enum, 64, 1, kb_ksw_enum)   \
     K(KSW_K_COUNT, aasm_ksw_count, 64, 1, kb_ksw_count) \
-    K(KSW_K_FILL, aasm_ksw_fill, 64, 1, kb_ksw_fill)
+    K(KSW_K_FILL, aasm_ksw_fill, 64, 1, kb_ksw_fill)   \
+    K(KSW_K_TREE_BF, aasm_ksw_tree_bf, 64, 1, kb_ksw_tree_bf)
 enum { AASM_KSW_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
 constexpr int ksw_block[] = {AASM_KSW_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
 AASM_KERNEL_BODY(run_ksw_body, AASM_KSW_KERNELS, KswArgs)
@@ -559,8 +612,16 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
     std::vector<int64_t> ins((size_t)G), walks((size_t)G);
     const bool cycles = flags & AASM_KSW_CYCLES;
     a.cycles = cycles;
-    if (!cycles) {
+    if (!cycles) {                                                   // (AASM_KSW_NEGATIVE: the DAG relaxation assumes no sign)
         if (!be.launch_from(KSW_K_TREE, 0, G, a)) return be.err();
+    } else if (flags & AASM_KSW_NEGATIVE) {                          // bellman_ford_run's queue room (aasm_sssp.h): exact, one round
+        const std::vector<int64_t> qo = bf_queue_offsets(G, g_voff, rowptr);
+        const size_t mark = be.mark();
+        a.hoff = (const int64_t *)m.up(qo.data(), (size_t)(G + 1) * 8);
+        a.dheap = (DjEnt *)m.alloc((size_t)qo[(size_t)G] * sizeof(DjEnt));
+        if (!m.ok || !be.launch_from(KSW_K_TREE_BF, 0, G, a) || !be.sync()) return be.err();
+        be.release(mark);
+        a.hoff = nullptr; a.dheap = nullptr;
     } else {
         // dijkstra_run's heap room (aasm_sssp.h): E + 2 entries, then 4x, 16x, 64x for the graphs that ran out of it; at 64x
         // the kernel's bound on pushes ends a graph first
@@ -612,6 +673,7 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
     int64_t wdone = 0;
     std::vector<int64_t> aoff((size_t)G, 0), qoff((size_t)G, 0), rofs((size_t)G, 0), wbase((size_t)G, 0);
     auto fail = [&](int rc) { ksw_free_out(out); return rc; };
+    auto down = [&](void *h, const void *d, size_t n) { return n == 0 || be.d2h(h, d, n); };   // (an empty vector's data() may be null)
     for (int64_t g0 = 0; g0 < G;) {
         int64_t g1 = g0, bytes = 0, na = 0, nq = 0, nr = 0;
         while (g1 < G && (g1 == g0 || bytes + per[g1] <= budget)) {
@@ -638,7 +700,7 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
         std::vector<int32_t> st((size_t)ng);
         std::vector<Dist> rd((size_t)nr);
         if (!be.sync() || !be.d2h(nfound.data(), a.nfound + g0, (size_t)ng * 8) || !be.d2h(hcount.data(), a.hcount + g0, (size_t)ng * 8) ||
-            !be.d2h(st.data(), a.status + g0, (size_t)ng * 4) || !be.d2h(rd.data(), c.rdist, (size_t)nr * sizeof(Dist))) return fail(be.err());
+            !be.d2h(st.data(), a.status + g0, (size_t)ng * 4) || !down(rd.data(), c.rdist, (size_t)nr * sizeof(Dist))) return fail(be.err());
         for (int64_t g = g0; g < g1; g++) {
             const int64_t j = g - g0;
             out->n_found[g] = nfound[j]; out->heap_nodes[g] = hcount[j]; out->status[g] = st[j];
@@ -659,7 +721,7 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
             if (!be.h2d(d_wbase, wbase.data(), (size_t)G * 8) || !be.launch_from(KSW_K_FILL, g0, g1, cc)) return fail(be.err());
             std::vector<int64_t> wo((size_t)nr);
             wedges.resize((size_t)(wdone + nw));
-            if (!be.sync() || !be.d2h(wo.data(), cc.woff, (size_t)nr * 8) || !be.d2h(wedges.data() + wdone, cc.wedges, (size_t)nw * 8)) return fail(be.err());
+            if (!be.sync() || !down(wo.data(), cc.woff, (size_t)nr * 8) || !down(wedges.data() + wdone, cc.wedges, (size_t)nw * 8)) return fail(be.err());
             for (int64_t g = g0; g < g1; g++) {
                 const int64_t j = g - g0, base = wdone + wbase[g];
                 for (int64_t i = 0; i < k; i++) out->walk_off[g * k + i] = base + (i < nfound[j] ? wo[(size_t)(rofs[g] + i)] : wtot[j]);
@@ -669,7 +731,7 @@ int ksw_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
         if (want_arena) {                                            // test hook: {rank, key[5], u, v, left, right} per node
             std::vector<KswNode> nodes((size_t)na);
             std::vector<int32_t> et((size_t)ET), cl((size_t)ET);
-            if (!be.d2h(nodes.data(), c.arena, (size_t)na * sizeof(KswNode)) || !be.d2h(et.data(), a.etail, (size_t)ET * 4) ||
+            if (!down(nodes.data(), c.arena, (size_t)na * sizeof(KswNode)) || !down(et.data(), a.etail, (size_t)ET * 4) ||
                 !be.d2h(out->hook_hroot + g_voff[g0], a.hroot + g_voff[g0], (size_t)(g_voff[g1] - g_voff[g0]) * 4)) return fail(be.err());
             for (int64_t g = g0; g < g1; g++) {
                 const int64_t eb = rowptr[g_voff[g]];

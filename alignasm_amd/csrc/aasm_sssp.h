@@ -1,7 +1,8 @@
 // aasm_sssp.h -- single-source shortest paths over a batch of caller graphs, and the checks of the layout that aasm_sssp_dijkstra,
 // aasm_sssp_dial and aasm_k_shortest_walks share (include/alignasm_amd.h), run on the host before a device is touched.
 // Kernel bodies in KCtx style, so tests/host_emul/graphs_emul.cpp compiles them for one lane on the host: kb_sssp_dijkstra, the solver's
-// dijkstra() (row ★J), and kb_sssp_dial, Dial's bucketed BFS (row K5); host drivers dijkstra_run / dial_run as ksw_run (aasm_ksw.h).
+// dijkstra() (row ★J), kb_sssp_bellman_ford, its bellman_ford() (row ★L), and kb_sssp_dial, Dial's bucketed BFS (row K5); host drivers
+// dijkstra_run / bellman_ford_run / dial_run as ksw_run (aasm_ksw.h).
 #pragma once
 #include "aasm_dev.h"
 #include "../../include/alignasm_amd.h"
@@ -20,6 +21,8 @@ struct SsspArgs {
     const int64_t *w5, *hoff; Dist *d; int32_t *prv; DjEnt *heap;            // dijkstra: graph g's heap is [hoff[g], hoff[g + 1])
     const int32_t *cost; int32_t nb; int64_t *dist, *pre; int32_t *spill;    // dial: nb = lim + 1 stacks in graph g's spill,
     const int64_t *soff;                                                     //       [soff[g], soff[g + 1])
+    // bellman_ford: graph g's queue ring is [hoff[g], hoff[g + 1]) of heap; its cycle goes to cyc[voff[g] + g ...], clen[g] entries
+    int32_t *status, *cyc, *mark; int64_t *clen, *qhigh;
 };
 
 AASM_DEV Dist edge_w5(const int64_t *w5, int64_t e) {
@@ -112,6 +115,143 @@ AASM_DEV void kb_sssp_dijkstra(const KCtx &k, const SsspArgs &a) {
         }
     }
     if (over && lane == 0) pg[s] = -2;                               // reported by the host driver
+}
+
+// ---- generic SSSP with negative weights: the solver's bellman_ford() (k_shortest_walks.hpp:91-129) --------------------------------
+// The reference's round-counted SPFA restated exactly, because prv[] depends on the order of the relaxations: a FIFO queue of
+// (Distance, vertex) that starts with (IDENTITY, src); rounds i = 1 .. n, each popping exactly the entries present at its start; an
+// entry is skipped when cur_dis > dis[x] (:114; an equal one is not); the edges of x in list order under the strict test
+// `dis[nx] > dis[x] + w` (:116) with dis[x] as it stands at that moment (a self-loop may have improved it), the stored value being
+// dis[x] + w; a relaxation in round n ends the graph as "negative cycle" after dis / prv are stored (:119-122), any other pushes
+// (dis[nx], nx).  Unlike dijkstra() it always ends: the mapq-ratio key is not monotone under addition, so a graph can keep improving
+// round a cycle whose score sum is not negative; the reference reports a cycle there at round n, and so does this.
+//
+// One wave per graph, wave-uniform control, lane 0 stores.  The popped vertex's list is taken AASM_BF_CHUNK edges at a time: each
+// lane loads its edge's head, its weight and dis[head] and forms the strict predicate with dis[x]; one ballot decides the chunk (no
+// improving lane: one step, the common case after the first rounds).  The improving lanes are committed in lane order, each
+// re-tested against the current dis[head] and dis[x], because heads repeat inside a chunk and an edge can lead back to x.  A lane
+// that did not improve at the chunk's start cannot improve later in it - dis[] only falls in the order, which is a strict weak
+// order inside the w5 domain - unless dis[x] itself fell: after a commit to x the rest of the chunk is evaluated again from the next
+// edge.  So the result is bit for bit what one lane walking the list leaves; with one lane (the host emulation) a chunk is one edge,
+// which is that walk.  -DAASM_BF_EDGEWISE (tools/bf_probe.py's comparison build) takes one edge per step on the device too.
+//
+// Queue room.  An entry of x is live (not skipped) only while its distance is still dis[x], and the pushes of one vertex fall
+// strictly, so at any moment at most one queued entry per vertex is live - but stale ones remain queued.  A round pops what its
+// start holds and relaxes each live vertex's list once: at most one push per edge, E per round.  The queue therefore holds at
+// most the E entries of the previous round (1 in the first) plus the E of this one: <= 2E + 1 < 2 * (E + 2), the room the drivers
+// give.  The room is still checked before every write; a graph that runs out of it ends as BF_QUEUE_FULL (AASM_E_INTERNAL).
+#if defined(AASM_BF_EDGEWISE)
+#define AASM_BF_CHUNK 1
+#else
+#define AASM_BF_CHUNK AASM_WAVE
+#endif
+enum { BF_DONE = 0, BF_CYCLE = 1, BF_QUEUE_FULL = 2 };
+// row(x, r0, r1): x's list as positions; edge(r, e, nx): position r's edge id in w5 and its head; commit(nx, x, e): lane 0's stores
+// beside dis[nx] (prv, and the edge for k-walks).  cyc_at: the vertex relaxed in round n; high: the queue's high-water mark.
+template <int W, class Row, class Edge, class Commit>
+AASM_DEV int bf_spfa(int lane, int64_t n, int32_t s, Dist *dis, const int64_t *w5, DjEnt *Q, int64_t cap, Row row, Edge edge, Commit commit,
+                     int32_t &cyc_at, int64_t &high) {
+    int64_t qh = 0, cnt = 0;
+    high = 0;
+    auto push = [&](const Dist &dd, int32_t v) {
+        if (cnt >= cap) return false;
+        int64_t at = qh + cnt;
+        if (at >= cap) at -= cap;
+        if (lane == 0) { DjEnt x; x.d = dd; x.v = v; x.p0 = x.p1 = x.p2 = 0; Q[at] = x; }
+        wave_fence();
+        if (++cnt > high) high = cnt;
+        return true;
+    };
+    if (lane == 0) dis[s] = dist_zero();                             // IDENTITY_DISTANCE (:109)
+    wave_fence();
+    if (!push(dist_zero(), s)) return BF_QUEUE_FULL;
+    for (int64_t i = 1; i <= n && cnt > 0; i++) {
+        const int64_t sz = cnt;
+        for (int64_t j = 0; j < sz; j++) {
+            const DjEnt ent = Q[qh];
+            if (++qh == cap) qh = 0;
+            cnt--;
+            const int32_t x = uni(ent.v);
+            const Dist cur = uni(ent.d);
+            Dist dx = uni(dis[x]);
+            if (uni(dist_lt<CALC_SUM_MODE>(dx, cur))) continue;      // cur_dis > dis[x] (:114)
+            int64_t r0, r1;
+            row(x, r0, r1);
+            while (r0 < r1) {
+                const int64_t r = r0 + (W > 1 ? lane : 0);
+                bool imp = false;
+                if (r < r1) {
+                    int64_t e; int32_t nx;
+                    edge(r, e, nx);
+                    imp = dist_lt<CALC_SUM_MODE>(dist_add(dx, edge_w5(w5, e)), dis[nx]);
+                }
+                uint64_t m = wave_ballot(imp);
+                if (W == 1) m &= 1;                                  // every lane holds the same edge
+                int64_t next = r0 + W;
+                while (m) {
+                    const int jl = ffs64(m) - 1;                     // the improving lanes in lane order = list order
+                    m &= m - 1;
+                    int64_t e; int32_t nx;
+                    edge(r0 + jl, e, nx);
+                    e = uni(e); nx = uni(nx);
+                    const Dist cand = uni(dist_add(dx, edge_w5(w5, e)));
+                    if (!uni(dist_lt<CALC_SUM_MODE>(cand, dis[nx]))) continue;   // dis[nx] > dis[x] + w (:116), as they stand now
+                    if (lane == 0) { dis[nx] = cand; commit(nx, x, e); }
+                    wave_fence();
+                    if (i == n) { cyc_at = nx; return BF_CYCLE; }    // :119-122
+                    if (!push(cand, nx)) return BF_QUEUE_FULL;
+                    if (nx == x) { dx = cand; next = r0 + jl + 1; break; }       // dis[x] fell: the rest of the chunk again
+                }
+                r0 = next;
+            }
+        }
+    }
+    return BF_DONE;
+}
+// detect_cycle(x) (:94-107) on one lane: follow prv from x until a vertex repeats; the list is closed (first entry == last entry)
+// and runs in edge direction.  mark[] is 0 on entry; out has room for n + 1.  Returns the length, or 0 when the chain meets -1
+// before it repeats a vertex (the reference would index out of bounds there).
+AASM_DEV int64_t bf_cycle(int64_t n, const int32_t *prv, int32_t *mark, int32_t x, int32_t *out) {
+    int64_t m = 0;
+    while (true) {
+        if (x < 0 || m > n) return 0;
+        out[m] = x;
+        if (mark[x]) break;
+        mark[x] = (int32_t)m + 1;
+        m++;
+        x = prv[x];
+    }
+    const int64_t first = mark[x] - 1, len = m - first + 1;          // out[first] == out[m]: reversed, [m .. first] is the answer
+    for (int64_t i = first, j = m; i < j; i++, j--) { const int32_t t = out[i]; out[i] = out[j]; out[j] = t; }
+    for (int64_t i = 0; i < len; i++) out[i] = out[first + i];
+    return len;
+}
+AASM_DEV void kb_sssp_bellman_ford(const KCtx &k, const SsspArgs &a) {
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs) return;
+    const int lane = k.lane;
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb;
+    Dist *dg = a.d + vb;
+    int32_t *pg = a.prv + vb, *mark = a.mark + vb;
+    for (int64_t v = lane; v < V; v += AASM_WAVE) { dg[v] = dist_max(); pg[v] = -1; mark[v] = 0; }
+    wave_fence();
+    int32_t at = -1;
+    int64_t high = 0;
+    const int st = bf_spfa<AASM_BF_CHUNK>(lane, V, a.src[g], dg, a.w5, a.heap + a.hoff[g], a.hoff[g + 1] - a.hoff[g],
+        [&](int32_t x, int64_t &r0, int64_t &r1) { r0 = uni(a.rowptr[vb + x]); r1 = uni(a.rowptr[vb + x + 1]); },
+        [&](int64_t r, int64_t &e, int32_t &nx) { e = r; nx = a.col[r]; },
+        [&](int32_t nx, int32_t x, int64_t) { pg[nx] = x; }, at, high);
+    if (st == BF_DONE) {
+        if (lane == 0) { a.status[g] = 0; a.clen[g] = 0; a.qhigh[g] = high; }
+        return;
+    }
+    if (lane == 0) {
+        const int64_t len = st == BF_CYCLE ? bf_cycle(V, pg, mark, at, a.cyc + vb + g) : 0;
+        a.status[g] = st == BF_QUEUE_FULL ? AASM_E_INTERNAL : len ? 1 : AASM_E_INVAL;
+        a.clen[g] = len; a.qhigh[g] = high;
+    }
+    wave_fence();
+    for (int64_t v = lane; v < V; v += AASM_WAVE) { dg[v] = dist_max(); pg[v] = -1; }   // the reference returns no distance vector
 }
 
 // ---- Dial's bucketed BFS (k_weighted_bfs.hpp:16-37), one wave per graph -------------------------------------------------
@@ -273,13 +413,14 @@ static inline int check_graph_batch(int64_t n_graphs, const int64_t *g_voff, con
 // a distance as the C-ABI's five int64 {qry, ref, anom, qnz, qtot}
 static inline void put_d5(int64_t *o, const Dist &x) { o[0] = x.qry; o[1] = x.ref; o[2] = x.anom; o[3] = x.qnz; o[4] = x.qtot; }
 
-// The w5 weight domain of dijkstra and k-walks.  AASM_OK, or AASM_E_OVERFLOW.
-static inline int check_w5(const int64_t *w5, int64_t n_edges, const char **why) {
+// The w5 weight domain of dijkstra and k-walks; with `negative` (bellman_ford, AASM_KSW_NEGATIVE) without the clause on the score
+// sum's sign.  AASM_OK, or AASM_E_OVERFLOW.
+static inline int check_w5(const int64_t *w5, int64_t n_edges, bool negative, const char **why) {
     const int64_t lim = (int64_t)1 << 39;
     for (int64_t e = 0; e < n_edges; e++) {
         const int64_t *w = w5 + 5 * e;
-        if (w[0] < -lim || w[0] >= lim || w[1] < -lim || w[1] >= lim || w[0] + w[1] < 0 || w[2] < 0 || w[2] > 2 || w[3] < 0 || w[3] > 1 || w[4] < 0 || w[4] > 1)
-            return check_fail(why, AASM_E_OVERFLOW, "edge " + std::to_string(e) + ": weight outside the supported range (score sum >= 0, |scores| < 2^39, anom 0..2, mapq counts 0..1)");
+        if (w[0] < -lim || w[0] >= lim || w[1] < -lim || w[1] >= lim || (!negative && w[0] + w[1] < 0) || w[2] < 0 || w[2] > 2 || w[3] < 0 || w[3] > 1 || w[4] < 0 || w[4] > 1)
+            return check_fail(why, AASM_E_OVERFLOW, "edge " + std::to_string(e) + ": weight outside the supported range (" + (negative ? "" : "score sum >= 0, ") + "|scores| < 2^39, anom 0..2, mapq counts 0..1)");
     }
     return AASM_OK;
 }
@@ -288,7 +429,13 @@ static inline int check_w5(const int64_t *w5, int64_t n_edges, const char **why)
 static inline int dijkstra_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
                                       const int32_t *src, const int64_t *d5, const int32_t *prev, const char **why) {
     const int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, src, {w5, d5, prev}, why);
-    return rc != AASM_OK ? rc : check_w5(w5, rowptr[g_voff[n_graphs]], why);
+    return rc != AASM_OK ? rc : check_w5(w5, rowptr[g_voff[n_graphs]], false, why);
+}
+static inline int bellman_ford_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                                          const int32_t *src, const int64_t *d5, const int32_t *prev, const int32_t *status, const int64_t *cycle_off,
+                                          const int32_t *cycle, const char **why) {
+    const int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, src, {w5, d5, prev, status, cycle_off, cycle}, why);
+    return rc != AASM_OK ? rc : check_w5(w5, rowptr[g_voff[n_graphs]], true, why);
 }
 static inline int dial_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
                                   const int32_t *src, int lim, const int64_t *dist, const int64_t *pre, const char **why) {
@@ -322,7 +469,8 @@ template <class BE> struct DevMem {
 // register budget.
 #define AASM_SSSP_KERNELS(K, KL)                                     \
     K(SSSP_K_DIJKSTRA, aasm_sssp_dijkstra_kernel, 64, 1, kb_sssp_dijkstra) \
-    KL(SSSP_K_DIAL, aasm_sssp_dial_kernel, 64, 1, sizeof(DialLds), 0, kb_sssp_dial)
+    KL(SSSP_K_DIAL, aasm_sssp_dial_kernel, 64, 1, sizeof(DialLds), 0, kb_sssp_dial) \
+    K(SSSP_K_BELLMAN_FORD, aasm_sssp_bellman_ford_kernel, 64, 1, kb_sssp_bellman_ford)
 enum { AASM_SSSP_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
 constexpr int sssp_block[] = {AASM_SSSP_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
 AASM_KERNEL_BODY(run_sssp_body, AASM_SSSP_KERNELS, SsspArgs)
@@ -365,6 +513,57 @@ int dijkstra_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t 
     }
     if (overflowed >= 0) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(overflowed) + ": dijkstra heap capacity exceeded at 64 x (E + 2) entries");
     for (int64_t v = 0; v < VT; v++) put_d5(d5 + 5 * v, hd[(size_t)v]);
+    return AASM_OK;
+}
+
+// graph g's queue ring of bellman_ford: 2 * (E + 2) entries (the bound: bf_spfa's comment), as offsets into one allocation
+static inline std::vector<int64_t> bf_queue_offsets(int64_t G, const int64_t *g_voff, const int64_t *rowptr) {
+    std::vector<int64_t> qo((size_t)G + 1, 0);
+    for (int64_t g = 0; g < G; g++) qo[(size_t)g + 1] = qo[(size_t)g] + 2 * (rowptr[g_voff[g + 1]] - rowptr[g_voff[g]] + 2);
+    return qo;
+}
+
+// status[g]: 0 with d5 / prev the reference's vectors; 1 for a negative cycle, cycle[cycle_off[g] .. cycle_off[g + 1]) holding it and
+// d5 / prev max / -1; a negative AASM_E_* otherwise.  A graph's status never fails the call.  qhigh: nullptr, or G cells for the
+// queues' high-water marks (the emulation's debug return).
+template <class BE>
+int bellman_ford_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                     const int32_t *src, int64_t *d5, int32_t *prev, int32_t *status, int64_t *cycle_off, int32_t *cycle, int64_t *qhigh,
+                     const char **why) {
+    (void)why;
+    const int64_t G = n_graphs, VT = g_voff[G], ET = rowptr[VT];
+    const std::vector<int64_t> qo = bf_queue_offsets(G, g_voff, rowptr);
+    DevMem<BE> m{be};
+    SsspArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_graphs = G;
+    a.voff = (const int64_t *)m.up(g_voff, (size_t)(G + 1) * 8);
+    a.rowptr = (const int64_t *)m.up(rowptr, (size_t)(VT + 1) * 8);
+    a.col = (const int32_t *)m.up(col, (size_t)ET * 4);
+    a.src = (const int32_t *)m.up(src, (size_t)G * 4);
+    a.w5 = (const int64_t *)m.up(w5, (size_t)ET * 40);
+    a.hoff = (const int64_t *)m.up(qo.data(), (size_t)(G + 1) * 8);
+    a.d = (Dist *)m.alloc((size_t)VT * sizeof(Dist));
+    a.prv = (int32_t *)m.alloc((size_t)VT * 4);
+    a.mark = (int32_t *)m.alloc((size_t)VT * 4);
+    a.heap = (DjEnt *)m.alloc((size_t)qo[(size_t)G] * sizeof(DjEnt));
+    a.status = (int32_t *)m.alloc((size_t)G * 4);
+    a.clen = (int64_t *)m.alloc((size_t)G * 8);
+    a.qhigh = (int64_t *)m.alloc((size_t)G * 8);
+    a.cyc = (int32_t *)m.alloc((size_t)(VT + G) * 4);
+    if (!m.ok) return be.err();
+    std::vector<Dist> hd((size_t)VT);
+    std::vector<int64_t> clen((size_t)G);
+    if (!be.launch(SSSP_K_BELLMAN_FORD, G, a) || !be.sync() || !be.d2h(hd.data(), a.d, (size_t)VT * sizeof(Dist)) ||
+        !be.d2h(prev, a.prv, (size_t)VT * 4) || !be.d2h(status, a.status, (size_t)G * 4) || !be.d2h(clen.data(), a.clen, (size_t)G * 8) ||
+        (qhigh && !be.d2h(qhigh, a.qhigh, (size_t)G * 8))) return be.err();
+    for (int64_t v = 0; v < VT; v++) put_d5(d5 + 5 * v, hd[(size_t)v]);
+    cycle_off[0] = 0;
+    for (int64_t g = 0; g < G; g++) {
+        const int64_t len = clen[(size_t)g] < 0 || clen[(size_t)g] > g_voff[g + 1] - g_voff[g] + 1 ? 0 : clen[(size_t)g];
+        if (len && !be.d2h(cycle + cycle_off[g], a.cyc + g_voff[g] + g, (size_t)len * 4)) return be.err();
+        cycle_off[g + 1] = cycle_off[g] + len;
+    }
     return AASM_OK;
 }
 

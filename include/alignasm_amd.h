@@ -225,6 +225,21 @@ int  aasm_partition_costs(const double *cost, int64_t n_contigs, int n_shards, i
 int  aasm_sssp_dijkstra(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
                         const int32_t *src, int64_t *d5, int32_t *prev, int device);
 
+/* The solver's single-source shortest paths for graphs with negative weights, bellman_ford() (src/k_shortest_walks.hpp:91-129: a
+ * round-counted SPFA), over a batch of graphs in aasm_sssp_dijkstra's layout.  The weight domain is dijkstra's without the clause
+ * on the score sum's sign: |scores| < 2^39, anom 0..2, qul counts 0..1 (AASM_E_OVERFLOW outside).  Per graph g:
+ *   status[g] = 0   d5 / prev are exactly the reference's two vectors (prev depends on the order of the relaxations, which is kept)
+ *   status[g] = 1   a negative cycle - a relaxation in round n, n the graph's vertex count; this includes a cycle whose score sum
+ *                   is not negative but round which the qul ratio keeps improving.  The reference returns no distance vector: the
+ *                   graph's d5 is PafDistance::max() everywhere, its prev -1, and cycle[cycle_off[g] .. cycle_off[g + 1]) holds
+ *                   detect_cycle()'s list (:94-107): closed, first entry == last entry, in edge direction, local vertex ids
+ *   status[g] < 0   AASM_E_INVAL: the prev chain from the relaxed vertex met -1 before it repeated a vertex (the reference indexes
+ *                   out of bounds there), no cycle is reported; AASM_E_INTERNAL: the queue's proven room ran out (must not happen)
+ * A graph's status never fails the call, and the rest of the batch is solved.  cycle_off has n_graphs + 1 entries; cycle needs room
+ * for g_voff[n_graphs] + n_graphs entries (a graph's closed cycle holds at most its vertex count + 1). */
+int  aasm_sssp_bellman_ford(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                            const int32_t *src, int64_t *d5, int32_t *prev, int32_t *status, int64_t *cycle_off, int32_t *cycle, int device);
+
 /* Dial's bucketed BFS, k_weighted_bfs() (src/k_weighted_bfs.hpp:16-37; the solver runs it with lim = 2 on the anomaly weights,
  * src/paf_data.cpp:704-713), over a batch of digraphs that may contain cycles and parallel edges: same graph layout as
  * aasm_sssp_dijkstra, cost one int32 per edge in 0 .. lim (lim <= 7), src the local source per graph.  dist (-1 = unreachable)
@@ -252,10 +267,18 @@ int  aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowp
  *    return either) gets AASM_E_INVAL and no walks, with d5 / best as dijkstra left them.
  *  - a walk has any number of edges: when a queued distance leaves |qry_score|, |ref_score| < 2^62 or anom, qul_nonzero,
  *    qul_total < 2^30 the enumeration ends with AASM_E_OVERFLOW; n_found, dist5 and the walks hold what was found before.
- *  - a graph whose walks hold more than 2^28 edges together keeps n_found and dist5, gets empty walk ranges and AASM_E_OVERFLOW. */
+ *  - a graph whose walks hold more than 2^28 edges together keeps n_found and dist5, gets empty walk ranges and AASM_E_OVERFLOW.
+ *
+ * With AASM_KSW_NEGATIVE the weight domain is aasm_sssp_bellman_ford's: edges whose score sum is negative are accepted (without
+ * it they are AASM_E_OVERFLOW, as ever).  Alone, the flag changes nothing else: the reference's is_dag = true ignores negative_edge,
+ * and its DAG relaxation assumes no sign.  Beside AASM_KSW_CYCLES the solver runs as with negative_edge = true: the tree is the one
+ * bellman_ford() from the sink over the reversed graph leaves (:186), which always ends, so the bound on pushes does not apply; a
+ * graph with a negative cycle (aasm_sssp_bellman_ford's status 1) gets AASM_E_INVAL, no walks and d5 / best as max / -1 - the
+ * reference has no distance vector to index there.  The tree guard and the other two limits hold unchanged. */
 #define AASM_KSW_WALKS      0x1     /* fill walk_off / walk_edges                                                     */
 #define AASM_KSW_TREE       0x2     /* fill d5 / best                                                                 */
 #define AASM_KSW_CYCLES     0x4     /* graphs may hold cycles: the reference's is_dag = false                         */
+#define AASM_KSW_NEGATIVE   0x8     /* edges may have a negative score sum: the reference's negative_edge = true      */
 #define AASM_KSW_HOOK_ARENA 0x100   /* test hook, 0 in production: fill hook_arena / hook_hroot                       */
 typedef struct aasm_ksw_out {
     int64_t  n_graphs, k;

@@ -5,6 +5,9 @@ CPU oracle.  One JSON line per (contigs, K):
                same run; n_found and the distances' first keys (score sum, anom) must equal the default mode's
   pipe_ms      minimum over --reps of the pipeline's sptree + heap_prep + heap + enum phases (HIP events, timing=True)
   oracle_ms    the CPU oracle (oracle_generic_kwalks, one thread) on --oracle-sample graphs, scaled to all of them
+With --negative the contigs are overhang contigs (tests/overhang_cases.py, mode --overhang: records run to or past the query's end,
+so dest edges and walk sums are negative) and every aasm_k_shortest_walks call passes negative=True (AASM_KSW_NEGATIVE; with
+--cycles the tree is then bellman_ford()'s).
 The first call of each configuration is a warm-up and is not counted.  Checks n_found / heap_nodes against the pipeline."""
 import argparse
 import json
@@ -30,11 +33,16 @@ ap.add_argument("--seed", type=int, default=21)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--oracle-sample", type=int, default=40)
 ap.add_argument("--cycles", action="store_true", help="time cycles=True beside the default mode")
+ap.add_argument("--negative", action="store_true", help="overhang contigs, negative=True")
+ap.add_argument("--overhang", default="longest", help="tests/overhang_cases.py's mode for --negative")
 a = ap.parse_args()
 
 for nc in (int(x) for x in a.contigs.split(",")):
     paf = A.Paf.synth(nc, a.recs, a.seed, no_cs=True)
     hb = paf.batch(); paf.close()
+    if a.negative:
+        import overhang_cases as OC
+        hb = OC.overhang(hb, a.overhang, a.seed)
     db = A.DeviceBatch(hb)
     for K in (int(x) for x in a.k.split(",")):
         res = db.solve(max_paths=K, keep_debug=True)
@@ -51,7 +59,7 @@ for nc in (int(x) for x in a.contigs.split(",")):
         wall = []
         for r in range(a.reps + 1):
             t = time.perf_counter()
-            got = api.k_shortest_walks(*args, walks=False, tree=False)
+            got = api.k_shortest_walks(*args, walks=False, tree=False, negative=a.negative)
             if r:
                 wall.append((time.perf_counter() - t) * 1e3)
         ok = bool(np.array_equal(got["n_found"], want["kfound"]) and np.array_equal(got["heap_nodes"], want["h_cnt"]))
@@ -60,7 +68,7 @@ for nc in (int(x) for x in a.contigs.split(",")):
             wall_c = []
             for r in range(a.reps + 1):
                 t = time.perf_counter()
-                got_c = api.k_shortest_walks(*args, walks=False, tree=False, cycles=True)
+                got_c = api.k_shortest_walks(*args, walks=False, tree=False, cycles=True, negative=a.negative)
                 if r:
                     wall_c.append((time.perf_counter() - t) * 1e3)
             same = bool(np.array_equal(got_c["n_found"], got["n_found"]) and not got_c["status"].any() and
@@ -78,6 +86,7 @@ for nc in (int(x) for x in a.contigs.split(",")):
                           with_paths=False)
         oracle_ms = (time.perf_counter() - t) * 1e3 * len(contigs) / max(1, len(pick))
         print(json.dumps({"contigs": nc, "graphs": len(contigs), "K": K, "V": int(batch["g_voff"][-1]), "E": int(batch["rowptr"][-1]),
+                          "negative_edges": int((batch["w"][:, 0] + batch["w"][:, 1] < 0).sum()),
                           "ksw_ms": round(min(wall), 2), **cyc, "pipe_ms": round(min(pipe), 3), "oracle_ms": round(oracle_ms, 1),
                           "walks": int(got["n_found"].sum()), "heap_nodes": int(got["heap_nodes"].sum()), "equal_to_pipeline": ok}), flush=True)
     db.close()
