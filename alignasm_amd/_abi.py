@@ -340,6 +340,22 @@ def unpack_cycles(cycle_off, cycle):
     return [cycle[int(cycle_off[g]):int(cycle_off[g + 1])].copy() for g in range(len(cycle_off) - 1)]
 
 
+# aasm_topology_sort / aasm_sssp_dag (include/alignasm_amd.h): the entries' argument types in the header's order; every array is
+# passed as a pointer.  api.py sets them on the library.
+DAG_ARGTYPES = {
+    "aasm_topology_sort": [C.c_int64] + [C.c_void_p] * 5 + [C.c_int],      # n_graphs; g_voff, rowptr, col, order, status; device
+    "aasm_sssp_dag": [C.c_int64] + [C.c_void_p] * 9 + [C.c_int],           # n_graphs; g_voff, rowptr, col, w5, src, d5, prev, order, status; device
+}
+
+
+def dag_outputs(g_voff, relax=True):
+    """The caller's arrays of aasm_sssp_dag for a batch: d5 [VT, 5], prev [VT], order [VT], status [G]; of aasm_topology_sort
+    (relax=False) the last two."""
+    G, VT = len(g_voff) - 1, int(g_voff[-1])
+    out = (np.zeros(VT, np.int32), np.zeros(G, np.int32))
+    return ((np.zeros((VT, 5), np.int64), np.zeros(VT, np.int32)) + out) if relax else out
+
+
 def ksw_inputs(g_voff, rowptr, col, w, source, sink):
     """k_shortest_walks' arrays (graph_inputs with scalar weights allowed): g_voff, rowptr, col, w5, source, sink."""
     g_voff, rowptr, col, source, sink, w5, _ = graph_inputs(g_voff, rowptr, col, source, sink, w5=w, scalar_w=True)

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+from ._abi import (DAG_ARGTYPES, dag_outputs, AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
                    DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, bellman_ford_outputs, graph_inputs, ksw_inputs, unpack_cycles, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,6 +80,9 @@ def _load():
     # the --alt merge on a resident batch: (aasm_batch_in *, aasm_row_cols *, text, len, baseline, flags, device, aasm_upload **, aasm_batch_in *, aasm_row_cols *)
     lib.aasm_paf_merge_alt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.aasm_paf_merge_alt_device.restype = C.c_int
+    for name, argtypes in DAG_ARGTYPES.items():                       # aasm_topology_sort, aasm_sssp_dag
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = argtypes, C.c_int
     return lib
 
 
@@ -89,7 +92,7 @@ LIB = _load()
 EXPORTED = [
     "aasm_abi_version", "aasm_device_count", "aasm_init", "aasm_last_error", "aasm_solve_batch", "aasm_solve_batch_multi", "aasm_solve_device",
     "aasm_result_stats", "aasm_result_fetch", "aasm_result_free", "aasm_free_out", "aasm_upload_batch", "aasm_upload_free",
-    "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_sssp_bellman_ford", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_poison", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
+    "aasm_contig_costs", "aasm_partition_contigs", "aasm_partition_costs", "aasm_solve_batch_range", "aasm_writer_open", "aasm_writer_append", "aasm_writer_close", "aasm_reserve_workspace", "aasm_sssp_dijkstra", "aasm_sssp_dial", "aasm_sssp_bellman_ford", "aasm_topology_sort", "aasm_sssp_dag", "aasm_debug_fetch", "aasm_debug_counter", "aasm_debug_poison", "aasm_debug_predicates", "aasm_debug_sort_replay", "aasm_paf_read", "aasm_paf_read_opts", "aasm_paf_parse_mem", "aasm_paf_parse_mem_opts", "aasm_paf_merge_alt", "aasm_paf_merge_alt_mem", "aasm_paf_free", "aasm_paf_batch", "aasm_paf_n_contigs",
     "aasm_paf_write_outputs", "aasm_set_host_threads", "aasm_cs_match_ranges", "aasm_cs_edit", "aasm_synth_paf", "aasm_synth_paf_range", "aasm_paf_to_text", "aasm_paf_save",
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
     "aasm_paf_parse_device", "aasm_paf_read_device", "aasm_paf_parse_device_rows", "aasm_paf_read_device_rows",
@@ -134,6 +137,31 @@ def sssp_bellman_ford(g_voff, rowptr, col, w5, src, device=0):
     _check(LIB.aasm_sssp_bellman_ford(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(src), P(d), P(prev), P(status),
                                       P(cycle_off), P(cycle), int(device)))
     return d, prev, status, unpack_cycles(cycle_off, cycle)
+
+
+def topology_sort(g_voff, rowptr, col, device=0):
+    """topology_sort() of the reference's solver (k_shortest_walks.hpp:132-156) on the GPU over a batch of graphs in sssp_dijkstra's
+    layout.  Returns (order: [V] int32, status: [G] int32).  status 0: order[g_voff[g] ..] is the reference's vector as local ids -
+    Kahn's algorithm with a FIFO: the vertices of in-degree 0 in ascending id, then each vertex when its last in-edge is processed.
+    status 1: the graph holds a cycle (the reference asserts; with NDEBUG it returns an empty vector) and its order is -1."""
+    g_voff, rowptr, col, _, _, _, _ = graph_inputs(g_voff, rowptr, col, None)
+    order, status = dag_outputs(g_voff, relax=False)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(LIB.aasm_topology_sort(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(order), P(status), int(device)))
+    return order, status
+
+
+def sssp_dag(g_voff, rowptr, col, w5, src, order=False, device=0):
+    """shortest_path_dag() of the reference's solver (k_shortest_walks.hpp:160-175) on the GPU over a batch of DAGs whose edges may
+    have negative score sums.  Returns (d: [V, 5] int64, prev: [V] int32, status: [G] int32), and with order=True topology_sort()'s
+    vector as a fourth.  status 0: d / prev are the reference's vectors (among equal candidates the first in (Kahn position of the
+    tail, list position) stays); 1: the graph holds a cycle, d is max but IDENTITY at src, prev and order are -1."""
+    g_voff, rowptr, col, src, _, w5, _ = graph_inputs(g_voff, rowptr, col, src, w5=w5)
+    d, prev, od, status = dag_outputs(g_voff)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(LIB.aasm_sssp_dag(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(w5), P(src), P(d), P(prev), P(od) if order else None,
+                             P(status), int(device)))
+    return (d, prev, status, od) if order else (d, prev, status)
 
 
 def k_shortest_walks(g_voff, rowptr, col, w, source, sink, k, walks=True, tree=False, device=0, _hooks=0, cycles=False, negative=False):

@@ -67,7 +67,7 @@ AASM_PIPELINE_KERNELS(K, KL)
 #define AASM_FAMILY (PackArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_PACK_KERNELS(K, KL)
 #undef AASM_FAMILY
-// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, ★L bellman_ford, K5 Dial) ...
+// the generic graph entries: bodies in aasm_sssp.h (★J dijkstra, ★L bellman_ford, ★M topology_sort / shortest_path_dag, K5 Dial) ...
 #define AASM_FAMILY (SsspArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_SSSP_KERNELS(K, KL)
 #undef AASM_FAMILY
@@ -1034,6 +1034,26 @@ int aasm_sssp_bellman_ford(int64_t n_graphs, const int64_t *g_voff, const int64_
     const int rc = bellman_ford_check_args(n_graphs, g_voff, rowptr, col, w5, src, d5, prev, status, cycle_off, cycle, &why);
     return graph_entry("aasm_sssp_bellman_ford", rc, why, device, [&](GraphGpu &be) {
         return bellman_ford_run(be, n_graphs, g_voff, rowptr, col, w5, src, d5, prev, status, cycle_off, cycle, nullptr, &why);
+    });
+}
+
+// topology_sort (k_shortest_walks.hpp:132-156) over a batch of graphs; host pointers in and out
+int aasm_topology_sort(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, int32_t *order, int32_t *status,
+                       int device) {
+    const char *why = "";
+    const int rc = dag_check_args(n_graphs, g_voff, rowptr, col, nullptr, nullptr, nullptr, nullptr, order, status, true, &why);
+    return graph_entry("aasm_topology_sort", rc, why, device, [&](GraphGpu &be) {
+        return dag_run(be, n_graphs, g_voff, rowptr, col, nullptr, nullptr, nullptr, nullptr, order, status, &why);
+    });
+}
+
+// shortest_path_dag (k_shortest_walks.hpp:160-175) over a batch of graphs, with its topology_sort where order is given
+int aasm_sssp_dag(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5, const int32_t *src,
+                  int64_t *d5, int32_t *prev, int32_t *order, int32_t *status, int device) {
+    const char *why = "";
+    const int rc = dag_check_args(n_graphs, g_voff, rowptr, col, w5, src, d5, prev, order, status, false, &why);
+    return graph_entry("aasm_sssp_dag", rc, why, device, [&](GraphGpu &be) {
+        return dag_run(be, n_graphs, g_voff, rowptr, col, w5, src, d5, prev, order, status, &why);
     });
 }
 

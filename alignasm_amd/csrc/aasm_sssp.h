@@ -1,8 +1,9 @@
 // aasm_sssp.h -- single-source shortest paths over a batch of caller graphs, and the checks of the layout that aasm_sssp_dijkstra,
 // aasm_sssp_dial and aasm_k_shortest_walks share (include/alignasm_amd.h), run on the host before a device is touched.
 // Kernel bodies in KCtx style, so tests/host_emul/graphs_emul.cpp compiles them for one lane on the host: kb_sssp_dijkstra, the solver's
-// dijkstra() (row ★J), kb_sssp_bellman_ford, its bellman_ford() (row ★L), and kb_sssp_dial, Dial's bucketed BFS (row K5); host drivers
-// dijkstra_run / bellman_ford_run / dial_run as ksw_run (aasm_ksw.h).
+// dijkstra() (row ★J), kb_sssp_bellman_ford, its bellman_ford() (row ★L), kb_sssp_dag, its topology_sort() and shortest_path_dag()
+// (row ★M), and kb_sssp_dial, Dial's bucketed BFS (row K5); host drivers dijkstra_run / bellman_ford_run / dag_run / dial_run as
+// ksw_run (aasm_ksw.h).
 #pragma once
 #include "aasm_dev.h"
 #include "../../include/alignasm_amd.h"
@@ -23,6 +24,9 @@ struct SsspArgs {
     const int64_t *soff;                                                     //       [soff[g], soff[g + 1])
     // bellman_ford: graph g's queue ring is [hoff[g], hoff[g + 1]) of heap; its cycle goes to cyc[voff[g] + g ...], clen[g] entries
     int32_t *status, *cyc, *mark; int64_t *clen, *qhigh;
+    // dag: in-degrees in mark, the Kahn order (and FIFO) in order, the first improving lane of a head in claim; w5 == nullptr is the
+    // sort alone (no src, d, prv, claim)
+    int32_t *order, *claim;
 };
 
 AASM_DEV Dist edge_w5(const int64_t *w5, int64_t e) {
@@ -254,6 +258,129 @@ AASM_DEV void kb_sssp_bellman_ford(const KCtx &k, const SsspArgs &a) {
     for (int64_t v = lane; v < V; v += AASM_WAVE) { dg[v] = dist_max(); pg[v] = -1; }   // the reference returns no distance vector
 }
 
+// ---- the solver's topology_sort() and shortest_path_dag() (k_shortest_walks.hpp:132-156, :160-175) ------------------------------
+// The two the reference's command line reaches (is_dag = true, paf_data.cpp:728), as an entry from a SOURCE over the caller's own
+// lists; kb_ksw_tree (aasm_ksw.h) keeps its own copy on lane 0, from the sink over the reversed graph, and is not routed through
+// this.  Kahn's algorithm with a FIFO: the vertices of in-degree 0 in ascending id, then a vertex when its last in-edge is
+// processed, "last" in (queue position of the tail, list position); parallel edges count once each.  The relaxation walks the
+// finished order, skips a vertex whose distance == max() (:166) and takes each list in list order under the strict test
+// `d[to] > d[v] + w` (:168), so the first candidate in (Kahn position of the tail, list position) among equals stays, with its own
+// five numbers.  A vertex's distance is final when it leaves the queue (every in-edge's tail left before it), so the two passes are
+// fused: a vertex is relaxed when it is popped.  On a cycle the reference asserts (:144-147); built with NDEBUG it returns an empty
+// order and relaxes nothing, which is what status 1 gives back: order -1, d max() but IDENTITY at src, prv -1.
+//
+// One wave per graph, wave-uniform control, order[] itself the FIFO (head, tail), every loop bounded by V or E, and every cell of
+// working memory (in-degrees, claim, d, prv, order) written here before it is read.  In-degrees: a lane per edge, atomic adds.
+// Sources: 64 vertices at a time, a ballot and a prefix count keep ascending id.  The popped vertex's list, AASM_DAG_CHUNK edges at
+// a time (as bf_spfa's):
+//  1. every lane takes its edge's head off the in-degree (atomically: heads repeat) and reads it back; the lanes that read 0 hold
+//     the heads that became ready in this chunk - an in-degree reaches 0 once, with the vertex's last in-edge, so a head that
+//     repeats across chunks of the list is ready only in the chunk of its last edge.  They are appended in lane order = list order,
+//     a head that repeats inside the chunk by its LAST lane only.
+//  2. d[u] is fixed for the whole list (the graph is acyclic, or the results are reset), so every lane forms d[u] + w and the strict
+//     predicate at once.  The improving lanes take the minimum of their lane ids on claim[head]: a lane that does not read its own
+//     id back shares its head with an earlier improving lane.  Heads named by one improving lane are stored in parallel; the lanes
+//     of a shared head are settled in lane order by lane 0, each re-tested against the value as it then stands, so the first of
+//     equals stays.  (A lane that did not improve at the chunk's start cannot improve later in it: d[] only falls.)
+//  3. a popped vertex at max() relaxes nothing and still counts down its heads.
+// With one lane (the host emulation) a chunk is one edge, the reference's own walk.  -DAASM_DAG_EDGEWISE (tools/dag_probe.py's
+// comparison build) takes one edge per step on the device too: lane 0 alone holds an edge.
+#if defined(AASM_DAG_EDGEWISE)
+#define AASM_DAG_CHUNK 1
+#else
+#define AASM_DAG_CHUNK AASM_WAVE
+#endif
+enum { DAG_DONE = 0, DAG_CYCLE = 1 };
+template <int W>
+AASM_DEV void dag_sort_relax(const KCtx &k, const SsspArgs &a) {
+    const int64_t g = k.bid;
+    if (g >= a.n_graphs) return;
+    const int lane = k.lane;
+    const bool relax = a.w5 != nullptr;                              // false: topology_sort() alone
+    const int64_t vb = a.voff[g], V = a.voff[g + 1] - vb, e0 = a.rowptr[vb], e1 = a.rowptr[vb + V];
+    const int64_t *rp = a.rowptr + vb;
+    int32_t *deg = a.mark + vb, *order = a.order + vb;
+    Dist *dg = relax ? a.d + vb : nullptr;
+    int32_t *pg = relax ? a.prv + vb : nullptr, *claim = relax ? a.claim + vb : nullptr;
+    const int32_t s = relax ? a.src[g] : 0;
+    for (int64_t v = lane; v < V; v += AASM_WAVE) {
+        deg[v] = 0; order[v] = -1;
+        if (relax) { dg[v] = dist_max(); pg[v] = -1; claim[v] = INT32_MAX; }
+    }
+    wave_fence();
+    for (int64_t e = e0 + lane; e < e1; e += AASM_WAVE) atomic_add(&deg[a.col[e]], (int32_t)1);   // :135-137
+    if (relax && lane == 0) dg[s] = dist_zero();                     // IDENTITY_DISTANCE (:163)
+    wave_fence();
+    int64_t head = 0, tail = 0;
+    for (int64_t v0 = 0; v0 < V; v0 += AASM_WAVE) {                  // :139-141, ascending id
+        const int64_t v = v0 + lane;
+        const bool src0 = v < V && ld_shared_i32(&deg[v]) == 0;
+        const uint64_t m = wave_ballot(src0);
+        if (src0) order[tail + popc64(m & lanemask_lt(lane))] = (int32_t)v;
+        tail += popc64(m);
+    }
+    wave_fence();
+    while (head < tail) {                                            // at most V pops: a vertex is appended once
+        const int32_t u = uni(order[head++]);
+        Dist du = dist_max();
+        if (relax) du = uni(dg[u]);
+        const bool live = relax && !dist_is_max(du);                 // :166
+        const int64_t r1 = uni(rp[u + 1]);
+        for (int64_t r0 = uni(rp[u]); r0 < r1; r0 += W) {
+            const int64_t r = r0 + (W > 1 ? lane : 0);
+            const bool act = r < r1 && (W > 1 || lane == 0);
+            const int32_t to = act ? a.col[r] : -1;
+            // 1. the countdown (:151-153)
+            if (act) atomic_add(&deg[to], (int32_t)-1);
+            wave_fence();
+            const bool ready = act && ld_shared_i32(&deg[to]) == 0;
+            for (uint64_t m = wave_ballot(ready); m; m &= m - 1) {
+                const int j = ffs64(m) - 1;
+                const int32_t h = wave_readlane(to, j);
+                if ((wave_ballot(ready && to == h) >> j) >> 1) continue;   // a later lane names h again: that one appends it
+                if (tail < V) { if (lane == 0) order[tail] = h; tail++; }
+            }
+            // 2. the relaxation (:167-172)
+            if (live) {
+                Dist cand = du;
+                bool imp = false;
+                if (act) { cand = dist_add(du, edge_w5(a.w5, r)); imp = dist_lt<CALC_SUM_MODE>(cand, dg[to]); }
+                if (wave_ballot(imp)) {
+                    if (imp) atomic_min_i32(&claim[to], (int32_t)lane);
+                    wave_fence();
+                    const bool first = imp && ld_shared_i32(&claim[to]) == lane;
+                    bool shared = false;
+                    for (uint64_t f = wave_ballot(imp && !first); f;) {          // the heads that several improving lanes name
+                        const int32_t h = wave_readlane(to, ffs64(f) - 1);
+                        shared |= imp && to == h;
+                        f &= ~wave_ballot(to == h);
+                    }
+                    if (imp && !shared) { dg[to] = cand; pg[to] = u; }
+                    if (first) claim[to] = INT32_MAX;
+                    wave_fence();
+                    for (uint64_t m = wave_ballot(shared); m; m &= m - 1) {      // in lane order = list order
+                        const int j = ffs64(m) - 1;
+                        const int32_t h = wave_readlane(to, j);
+                        const Dist c = uni(dist_add(du, edge_w5(a.w5, r0 + j)));
+                        if (!uni(dist_lt<CALC_SUM_MODE>(c, dg[h]))) continue;    // d[to] > d[v] + w, as it stands now
+                        if (lane == 0) { dg[h] = c; pg[h] = u; }
+                        wave_fence();
+                    }
+                }
+            }
+        }
+        wave_fence();                                                // order[] written by lane 0, read by every lane
+    }
+    if (tail < V) {                                                  // a cycle: the empty order, nothing relaxed (:144-147)
+        for (int64_t v = lane; v < V; v += AASM_WAVE) {
+            order[v] = -1;
+            if (relax) { dg[v] = v == s ? dist_zero() : dist_max(); pg[v] = -1; }
+        }
+    }
+    if (lane == 0) a.status[g] = tail < V ? DAG_CYCLE : DAG_DONE;
+}
+AASM_DEV void kb_sssp_dag(const KCtx &k, const SsspArgs &a) { dag_sort_relax<AASM_DAG_CHUNK>(k, a); }
+
 // ---- Dial's bucketed BFS (k_weighted_bfs.hpp:16-37), one wave per graph -------------------------------------------------
 // The reference keeps lim + 1 circular buckets, each a LIFO stack, and walks d = 0, 1, ...: pop the top of bucket d mod (lim + 1),
 // skip it when its distance is stale, relax its out-edges in list order; a successful relaxation (dist[nxt] == -1 or > d + cost)
@@ -388,10 +515,11 @@ static inline int check_fail(const char **why, int rc, const std::string &msg) {
 
 // The common layout of a graph batch.  Returns AASM_OK, or AASM_E_INVAL with a message in *why.  The offsets are checked first
 // (g_voff from 0 and strictly increasing, then rowptr from 0 and non-decreasing), and only then is anything read through them.
-// more: the entry's other pointers, which must not be NULL either.
+// more: the entry's other pointers, which must not be NULL either.  has_src = false: an entry without sources (aasm_topology_sort);
+// src is then neither required nor read.
 static inline int check_graph_batch(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *src,
-                                    std::initializer_list<const void *> more, const char **why) {
-    bool null = !g_voff || !rowptr || !col || !src;
+                                    std::initializer_list<const void *> more, const char **why, bool has_src = true) {
+    bool null = !g_voff || !rowptr || !col || (has_src && !src);
     for (const void *p : more) null |= !p;
     if (n_graphs <= 0 || null) return check_fail(why, AASM_E_INVAL, "empty batch or NULL pointer");
     if (g_voff[0] != 0) return check_fail(why, AASM_E_INVAL, "graph offsets do not start at 0");
@@ -403,7 +531,7 @@ static inline int check_graph_batch(int64_t n_graphs, const int64_t *g_voff, con
         if (rowptr[v + 1] < rowptr[v]) return check_fail(why, AASM_E_INVAL, "row pointers decrease at vertex " + std::to_string(v));
     for (int64_t g = 0; g < n_graphs; g++) {
         const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
-        if (src[g] < 0 || src[g] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": source outside it");
+        if (has_src && (src[g] < 0 || src[g] >= v1 - v0)) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": source outside it");
         for (int64_t e = rowptr[v0]; e < rowptr[v1]; e++)
             if (col[e] < 0 || col[e] >= v1 - v0) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": edge head outside the graph");
     }
@@ -436,6 +564,23 @@ static inline int bellman_ford_check_args(int64_t n_graphs, const int64_t *g_vof
                                           const int32_t *cycle, const char **why) {
     const int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, src, {w5, d5, prev, status, cycle_off, cycle}, why);
     return rc != AASM_OK ? rc : check_w5(w5, rowptr[g_voff[n_graphs]], true, why);
+}
+// aasm_sssp_dag (w5, src, d5, prev given; order may be NULL) and aasm_topology_sort (sort_only: none of the four, order required).
+// A graph's in-degrees and edge positions are int32: fewer than 2^31 edges per graph; the relaxation sums up to V - 1 weights of
+// |w| < 2^39 in int64: at most 2^20 vertices per graph (AASM_KSW_MAX_V, aasm_ksw.h, for the same reason).
+#define AASM_DAG_MAX_V ((int64_t)1 << 20)
+static inline int dag_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                                 const int32_t *src, const int64_t *d5, const int32_t *prev, const int32_t *order, const int32_t *status,
+                                 bool sort_only, const char **why) {
+    const int rc = sort_only ? check_graph_batch(n_graphs, g_voff, rowptr, col, nullptr, {order, status}, why, false)
+                             : check_graph_batch(n_graphs, g_voff, rowptr, col, src, {w5, d5, prev, status}, why);
+    if (rc != AASM_OK) return rc;
+    for (int64_t g = 0; g < n_graphs; g++) {
+        const int64_t V = g_voff[g + 1] - g_voff[g], E = rowptr[g_voff[g + 1]] - rowptr[g_voff[g]];
+        if (!sort_only && V > AASM_DAG_MAX_V) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(g) + ": more than 2^20 vertices");
+        if (V > INT32_MAX || E > INT32_MAX) return check_fail(why, AASM_E_OVERFLOW, "graph " + std::to_string(g) + ": 2^31 vertices or edges, or more");
+    }
+    return sort_only ? AASM_OK : check_w5(w5, rowptr[g_voff[n_graphs]], true, why);
 }
 static inline int dial_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
                                   const int32_t *src, int lim, const int64_t *dist, const int64_t *pre, const char **why) {
@@ -470,7 +615,8 @@ template <class BE> struct DevMem {
 #define AASM_SSSP_KERNELS(K, KL)                                     \
     K(SSSP_K_DIJKSTRA, aasm_sssp_dijkstra_kernel, 64, 1, kb_sssp_dijkstra) \
     KL(SSSP_K_DIAL, aasm_sssp_dial_kernel, 64, 1, sizeof(DialLds), 0, kb_sssp_dial) \
-    K(SSSP_K_BELLMAN_FORD, aasm_sssp_bellman_ford_kernel, 64, 1, kb_sssp_bellman_ford)
+    K(SSSP_K_BELLMAN_FORD, aasm_sssp_bellman_ford_kernel, 64, 1, kb_sssp_bellman_ford) \
+    K(SSSP_K_DAG, aasm_sssp_dag_kernel, 64, 1, kb_sssp_dag)
 enum { AASM_SSSP_KERNELS(AASM_ROW_ID, AASM_ROW_ID) };
 constexpr int sssp_block[] = {AASM_SSSP_KERNELS(AASM_ROW_BLOCK, AASM_ROW_BLOCK)};
 AASM_KERNEL_BODY(run_sssp_body, AASM_SSSP_KERNELS, SsspArgs)
@@ -563,6 +709,41 @@ int bellman_ford_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int6
         const int64_t len = clen[(size_t)g] < 0 || clen[(size_t)g] > g_voff[g + 1] - g_voff[g] + 1 ? 0 : clen[(size_t)g];
         if (len && !be.d2h(cycle + cycle_off[g], a.cyc + g_voff[g] + g, (size_t)len * 4)) return be.err();
         cycle_off[g + 1] = cycle_off[g] + len;
+    }
+    return AASM_OK;
+}
+
+// topology_sort() and shortest_path_dag() of every graph in one launch.  status[g]: 0 with order / d5 / prev the reference's vectors;
+// 1 for a cycle, with order -1, d5 max() but IDENTITY at src, prev -1.  w5 == nullptr: the sort alone (src, d5, prev unused).
+// order == nullptr: not wanted.  A graph's status never fails the call.
+template <class BE>
+int dag_run(BE &be, int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+            const int32_t *src, int64_t *d5, int32_t *prev, int32_t *order, int32_t *status, const char **why) {
+    (void)why;
+    const int64_t G = n_graphs, VT = g_voff[G], ET = rowptr[VT];
+    DevMem<BE> m{be};
+    SsspArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_graphs = G;
+    a.voff = (const int64_t *)m.up(g_voff, (size_t)(G + 1) * 8);
+    a.rowptr = (const int64_t *)m.up(rowptr, (size_t)(VT + 1) * 8);
+    a.col = (const int32_t *)m.up(col, (size_t)ET * 4);
+    a.mark = (int32_t *)m.alloc((size_t)VT * 4);
+    a.order = (int32_t *)m.alloc((size_t)VT * 4);
+    a.status = (int32_t *)m.alloc((size_t)G * 4);
+    if (w5) {
+        a.src = (const int32_t *)m.up(src, (size_t)G * 4);
+        a.w5 = (const int64_t *)m.up(w5, (size_t)ET * 40);
+        a.d = (Dist *)m.alloc((size_t)VT * sizeof(Dist));
+        a.prv = (int32_t *)m.alloc((size_t)VT * 4);
+        a.claim = (int32_t *)m.alloc((size_t)VT * 4);
+    }
+    if (!m.ok || !be.launch(SSSP_K_DAG, G, a) || !be.sync() || !be.d2h(status, a.status, (size_t)G * 4) ||
+        (order && !be.d2h(order, a.order, (size_t)VT * 4))) return be.err();
+    if (w5) {
+        std::vector<Dist> hd((size_t)VT);
+        if (!be.d2h(hd.data(), a.d, (size_t)VT * sizeof(Dist)) || !be.d2h(prev, a.prv, (size_t)VT * 4)) return be.err();
+        for (int64_t v = 0; v < VT; v++) put_d5(d5 + 5 * v, hd[(size_t)v]);
     }
     return AASM_OK;
 }

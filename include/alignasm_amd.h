@@ -240,6 +240,28 @@ int  aasm_sssp_dijkstra(int64_t n_graphs, const int64_t *g_voff, const int64_t *
 int  aasm_sssp_bellman_ford(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
                             const int32_t *src, int64_t *d5, int32_t *prev, int32_t *status, int64_t *cycle_off, int32_t *cycle, int device);
 
+/* The solver's topology_sort() (src/k_shortest_walks.hpp:132-156) and shortest_path_dag() (:160-175) - the two its command line
+ * reaches, with is_dag = true - over a batch of graphs in aasm_sssp_dijkstra's layout.  Per graph g:
+ *   status[g] = 0   the graph is acyclic.  order[g_voff[g] ..] is topology_sort()'s vector as local ids: Kahn's algorithm with a FIFO
+ *                   queue - the vertices of in-degree 0 in ascending id, then a vertex when its last in-edge is processed, "last" in
+ *                   (position of the tail in the queue, position in the tail's list); parallel edges count once each.  d5 / prev are
+ *                   shortest_path_dag(g, src)'s two vectors: d[src] = IDENTITY, the vertices taken in that order, one whose distance
+ *                   == PafDistance::max() skipped, each list walked in list order under the strict test d[to] > d[v] + w (CALC_SUM
+ *                   mode).  So among candidates the order cannot tell apart the FIRST in (Kahn position of the tail, list position)
+ *                   stays, with its own five numbers, and prev is its tail; and the sort covers the whole graph, not only what src
+ *                   reaches.
+ *   status[g] = 1   the graph holds a cycle (a self-loop included), anywhere in it.  The reference asserts; built with NDEBUG it
+ *                   returns an empty order and relaxes nothing: order is -1 everywhere, d5 is PafDistance::max() everywhere except
+ *                   IDENTITY at src, prev is -1 everywhere.
+ * A graph's status never fails the call, and the rest of the batch is solved.  The weight domain of aasm_sssp_dag is
+ * aasm_sssp_bellman_ford's (the DAG relaxation assumes no sign); it accepts at most 2^20 vertices and fewer than 2^31 edges per
+ * graph (AASM_E_OVERFLOW before a device is touched), aasm_topology_sort fewer than 2^31 of either.  order may be NULL in
+ * aasm_sssp_dag.  Layout and pointer errors are AASM_E_INVAL, as for the other graph entries. */
+int  aasm_topology_sort(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col,
+                        int32_t *order, int32_t *status, int device);
+int  aasm_sssp_dag(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int64_t *w5,
+                   const int32_t *src, int64_t *d5, int32_t *prev, int32_t *order /* may be NULL */, int32_t *status, int device);
+
 /* Dial's bucketed BFS, k_weighted_bfs() (src/k_weighted_bfs.hpp:16-37; the solver runs it with lim = 2 on the anomaly weights,
  * src/paf_data.cpp:704-713), over a batch of digraphs that may contain cycles and parallel edges: same graph layout as
  * aasm_sssp_dijkstra, cost one int32 per edge in 0 .. lim (lim <= 7), src the local source per graph.  dist (-1 = unreachable)
