@@ -13,6 +13,8 @@ all weight fields, anom_dis[dest], d / best, both Kahn orders, every heap node a
                                                     # (coordinates, weights and score sums above 2^31 / 2^32, up to 2^40 - 1)
     python tests/golden/make_ref_prefix.py overhang # ref_prefix_overhang.npz: the same from tests/overhang_cases.py's rewrites
                                                     # (qry_end >= qry_total - 1: negative dest edges and walk sums)
+    python tests/golden/make_ref_prefix.py enum     # ref_prefix_enum.npz: the same from tests/enum_cases.py's crafted contigs
+                                                    # (walk-sum distributions chosen on purpose; all 10 000 distances)
 """
 import os
 import sys
@@ -27,6 +29,7 @@ import aasm_testlib as T   # noqa: E402
 from test_fuzz import make_batch   # noqa: E402
 import wide_cases as W   # noqa: E402
 import overhang_cases as O   # noqa: E402
+import enum_cases as E   # noqa: E402
 
 KD = ("kd_qry", "kd_ref", "kd_anom", "kd_qnz", "kd_qtot")
 KD_SHORT = 64
@@ -94,6 +97,12 @@ OVERHANG_BATCHES = [
 ]
 
 
+# the crafted contigs of tests/enum_cases.py in one batch (under 40 records each; equal sums compress to next to nothing)
+ENUM_BATCHES = [
+    ("enum", lambda: E.batch(E.contigs())[1], False, True),
+]
+
+
 def _narrow(a):
     return a.astype(np.int32) if a.size and np.abs(a).max() < 2 ** 31 else a       # storage only; the loader widens again
 
@@ -158,5 +167,7 @@ if __name__ == "__main__":
         main(WIDE_BATCHES, "ref_prefix_wide.npz", packed=True)
     elif sys.argv[1:] == ["overhang"]:
         main(OVERHANG_BATCHES, "ref_prefix_overhang.npz", packed=True)
+    elif sys.argv[1:] == ["enum"]:
+        main(ENUM_BATCHES, "ref_prefix_enum.npz", packed=True)
     else:
         main()

@@ -1,7 +1,8 @@
 """GPU tier, K8 (k_shortest_walks.hpp:217-249): the sorted-front / sorted-runs queue (aasm_enum.h) against the oracle AND
 against the d-ary heap form of the same kernel - every popped distance, the insertion index of every pop, and the
 (heap node, predecessor) record of every push, at K large enough that the insertion buffer is flushed, runs are merged
-down several levels, cut at K - found, and the front is refilled from the run heads many times."""
+down several levels, cut at K - found, and the front is refilled from the run heads many times.  (These are synth() batches;
+tests/test_gpu_enum_edges.py runs the same check on walk-sum distributions chosen on purpose.)"""
 import numpy as np
 import pytest
 
@@ -25,13 +26,23 @@ def test_enumeration_queue_forms_agree_with_each_other_and_the_oracle(T, case):
     check_queue_forms(T, T.synth(nc, nr, seed, dense=dense, dup_every=dup), K)
 
 
-def check_queue_forms(T, hb, K, expect=None):
-    """The three queue forms of K8 on one batch (tests/test_gpu_overhang.py calls this too; `expect(c)`: the oracle's
-    intermediates of contig c where the caller has them already)."""
+def check_queue_forms(T, hb, K, expect=None, want=None, emul=None, recorded=None):
+    """The three queue forms of K8 on one batch (tests/test_gpu_overhang.py and tests/test_gpu_enum_edges.py call this too).
+    `expect(c)`: the oracle's intermediates of contig c where the caller has them already; `want`: T.oracle_solve(hb, K) likewise;
+    `emul`: enum_cases.emul_enum's per-contig (kfound, kd, klast, kcand rows) of an emulated solve at the same K - every form's
+    klast[:kfound] and kcand[:last popped index + 1] (heap node, predecessor) must equal the CPU emulation's;
+    `recorded(c)`: vectors recorded from the reference for contig c (or {}), checked like the oracle's."""
     nc = hb.n_contigs
     api = T.api()
     db = api.DeviceBatch(hb)
     got = {}
+    if expect is None:
+        memo = {}
+
+        def expect(c):                                               # (one oracle run per contig for the three forms)
+            if c not in memo:
+                memo[c] = T.oracle_debug(hb, c, K)
+            return memo[c]
     for form in ("runs", "runs40", "heap"):                          # 64-entry front, the 40-entry front of big batches, the d-ary heap
         res = db.solve(max_paths=K, keep_debug=True, enum_heap=(form == "heap"), enum_small=(form == "runs40"))
         kf = res.debug("kfound", np.int32)[:nc].copy()
@@ -41,8 +52,10 @@ def check_queue_forms(T, hb, K, expect=None):
         cand = res.debug("kcand", np.int32)[:nc * S * 8].reshape(nc * S, 8)    # {heap node, predecessor, qry (2 words)}, {anom, qnz, qtot, -}
         knodes, kprev = cand[:, 0].copy(), cand[:, 1].copy()
         got[form] = (kf, kd, klast, knodes, kprev, res.fetch())
-        if form == "runs":
-            assert T.diff_intermediates(hb, res.debug, K, expect=expect) == []      # kfound + every popped distance vs the oracle
+        assert T.diff_intermediates(hb, res.debug, K, expect=expect) == [], form     # kfound + every popped distance vs the oracle
+        if recorded is not None:
+            have = [c for c in range(nc) if recorded(c)]
+            assert T.diff_intermediates(hb, res.debug, K, contigs=have, expect=recorded) == [], form
         res.close()
     db.close()
     for other in ("heap", "runs40"):
@@ -59,7 +72,19 @@ def check_queue_forms(T, hb, K, expect=None):
             assert np.array_equal(a[3][c * S:c * S + pushed], b[3][c * S:c * S + pushed]), (other, c)
             assert np.array_equal(a[4][c * S:c * S + pushed], b[4][c * S:c * S + pushed]), (other, c)
         assert T.diff_outputs(a[5], b[5]) == [], other
-    assert T.diff_outputs(T.oracle_solve(hb, K), got["runs"][5]) == []
+    want = want if want is not None else T.oracle_solve(hb, K)
+    for form in got:
+        assert T.diff_outputs(want, got[form][5]) == [], form
+    if emul is not None:
+        S = 3 * K + 1
+        for form, (kf, kd, klast, knodes, kprev, _) in got.items():
+            for c in range(nc):
+                found, ekd, eklast, ecand = emul[c]
+                assert int(kf[c]) == found, (form, c)
+                assert np.array_equal(klast[c * K:c * K + found], eklast), (form, c, "klast")
+                pushed = int(eklast.max()) + 1 if found else 0
+                assert np.array_equal(knodes[c * S:c * S + pushed], ecand[:pushed, 0]), (form, c, "kcand node")
+                assert np.array_equal(kprev[c * S:c * S + pushed], ecand[:pushed, 1]), (form, c, "kcand predecessor")
 
 
 def test_queue_forms_agree_on_mixed_batches_and_many_k(T):

@@ -9,8 +9,9 @@ lines compiled in place; oracle/Makefile).  Checked against them here:
             kernel bodies in the 1-lane emulation;
   GPU tier: the HIP kernels' intermediates on the card, at K = 10 000 and at small K, with either K7 kernel.
 tests/golden/ref_prefix_overhang.npz holds the same for batches of tests/overhang_cases.py (records that run to or past the
-query's end: negative dest edges and walk sums); every check here runs over both files - one body per check, a test per
-file (the first file's tests keep their names)."""
+query's end: negative dest edges and walk sums), tests/golden/ref_prefix_enum.npz for the crafted contigs of tests/enum_cases.py
+(walk-sum distributions chosen on purpose, all in one batch); every check here runs over the three files - one body per check, a
+test per file (the first file's tests keep their names)."""
 import os
 
 import numpy as np
@@ -27,6 +28,11 @@ def V(T):
 @pytest.fixture(scope="module")
 def VO(T):
     return T.RefPrefixVectors(os.path.join(T.GOLDEN, "ref_prefix_overhang.npz"))
+
+
+@pytest.fixture(scope="module")
+def VE(T):
+    return T.RefPrefixVectors(os.path.join(T.GOLDEN, "ref_prefix_enum.npz"))
 
 
 def test_fixture_covers_the_stages(T, V):
@@ -66,12 +72,38 @@ def test_overhang_fixture_holds_its_input_class(T, VO):
     assert n_neg_edges > 300 and n_all_neg >= 10 and n_cross >= 3 and n_touch >= 6 and n_dist > 50000 and n_nsl >= 1 and spread > 50000
 
 
+def test_enum_fixture_holds_the_crafted_contigs(T, VE):
+    """The recorded batch IS enum_cases.contigs() (tests/test_gpu_enum_edges.py checks the card against these vectors by contig
+    index), every contig is recorded, and the reference's own distances show the distributions: one sum, all sums distinct,
+    groups of ties, sums below zero."""
+    import enum_cases as EC
+    names, hb = EC.batch(EC.contigs())
+    assert VE.tags == ["enum"]
+    rec, nsl, full = VE.batch("enum")
+    assert full and not nsl and set(rec.arrays) == set(hb.arrays)
+    for k in hb.arrays:
+        assert np.array_equal(rec.arrays[k], hb.arrays[k]), k
+    R = {n: VE.contig("enum", c) for c, n in enumerate(names)}
+    assert all(set(T.PREFIX_NAMES) <= set(r) for r in R.values())
+    sums = {n: r["kd_qry"] + r["kd_ref"] for n, r in R.items()}
+    assert len(sums["all_equal"]) == 4096 and len(np.unique(sums["all_equal"])) == 1
+    assert len(sums["all_equal_big"]) == 10000 and R["all_equal_big"]["kfound"][0] == 10000 and len(np.unique(sums["all_equal_big"])) == 1
+    assert len(np.unique(sums["all_distinct"])) == 4096 and len(np.unique(sums["clusters"])) == 4
+    assert len(sums["negative_ties"]) == 1024 and (sums["negative_ties"] < 0).all() and len(np.unique(sums["negative_ties"])) == 4
+    assert len(np.unique(R["anom_split"]["kd_anom"])) == 6 and len(np.unique(sums["anom_split"])) == 1
+    assert [len(sums[n]) for n in ("chain", "few_2", "few_3", "few_4", "few_5")] == [1, 2, 3, 4, 5]
+
+
 def test_oracle_matches_recorded_reference_prefix(T, V):
     _oracle_matches(T, V)
 
 
 def test_oracle_matches_recorded_reference_prefix_overhang(T, VO):
     _oracle_matches(T, VO)
+
+
+def test_oracle_matches_recorded_reference_prefix_enum(T, VE):
+    _oracle_matches(T, VE)
 
 
 def _oracle_matches(T, V):
@@ -86,6 +118,10 @@ def _oracle_matches(T, V):
             for n in T.PREFIX_NAMES:
                 want = r[n]
                 assert np.array_equal(o[n][:len(want)] if n.startswith("kd_") else o[n], want), (tag, c, n)
+
+
+def test_kernel_bodies_match_recorded_reference_prefix_enum(T, VE):
+    _kernel_bodies_match(T, VE)
 
 
 def test_kernel_bodies_match_recorded_reference_prefix(T, V):
@@ -114,6 +150,12 @@ def test_hip_intermediates_match_recorded_reference_prefix(T, V, heap_waves, cha
 @pytest.mark.parametrize("heap_waves,chain", HIP_FORMS)
 def test_hip_intermediates_match_recorded_reference_prefix_overhang(T, VO, heap_waves, chain):
     _hip_intermediates_match(T, VO, heap_waves, chain)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("heap_waves,chain", HIP_FORMS)
+def test_hip_intermediates_match_recorded_reference_prefix_enum(T, VE, heap_waves, chain):
+    _hip_intermediates_match(T, VE, heap_waves, chain)
 
 
 def _hip_intermediates_match(T, V, heap_waves, chain):

@@ -1,15 +1,20 @@
 """K8 stress: the sorted-front / sorted-runs queue (64- and 40-entry fronts) against the d-ary heap form on many contigs of mixed
-shape and many K: kfound, every popped distance, every pop's insertion index, every numbered push."""
+shape (and the crafted walk-sum distributions of tests/enum_cases.py) and many K: kfound, every popped distance, every pop's
+insertion index, every numbered push."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import aasm_testlib as T
+import enum_cases as EC
 api = T.api()
 n_checked = 0
-for seed, nc, nr, dense, dup, heavy in ((1, 60, 300, False, 0, True), (2, 30, 500, False, 3, False), (3, 24, 220, True, 0, False), (4, 40, 120, True, 2, True),
-                                       (5, 80, 90, False, 0, True), (6, 12, 900, False, 5, False), (7, 10, 400, True, 4, False)):
-    hb = T.synth(nc, nr, seed, dense=dense, dup_every=dup, heavy_tail=heavy)
+INPUTS = [(seed, T.synth(nc, nr, seed, dense=dense, dup_every=dup, heavy_tail=heavy))
+          for seed, nc, nr, dense, dup, heavy in ((1, 60, 300, False, 0, True), (2, 30, 500, False, 3, False), (3, 24, 220, True, 0, False), (4, 40, 120, True, 2, True),
+                                                  (5, 80, 90, False, 0, True), (6, 12, 900, False, 5, False), (7, 10, 400, True, 4, False))]
+INPUTS += [("crafted", EC.batch(EC.contigs())[1]), ("crafted_mixed", EC.mixed(T)[1])]      # tests/enum_cases.py: walk-sum distributions chosen on purpose
+for seed, hb in INPUTS:
+    nc = hb.n_contigs
     db = api.DeviceBatch(hb)
     for K in (22, 65, 130, 700, 2500, 10000):
         got = {}
