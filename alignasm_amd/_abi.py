@@ -348,6 +348,28 @@ DAG_ARGTYPES = {
 }
 
 
+class GraphsIn(C.Structure):
+    """aasm_graphs_in: a graph batch's arrays (host arrays for aasm_graphs_upload, DEVICE arrays for aasm_graphs_wrap_device and
+    in aasm_graphs_view's answer) with their lengths as the caller states them."""
+    _fields_ = [("n_graphs", C.c_int64), ("n_vertices", C.c_int64), ("n_edges", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("g_voff", "rowptr", "col", "w5", "cost")] + [("lim", C.c_int32), ("reserved", C.c_int32)]
+
+
+# resident graph batches (include/alignasm_amd.h): (restype, argtypes) in the header's order; handles, structures, arrays and
+# streams are all passed as pointers.  api.py sets them on the library.
+GRAPHS_SIGS = {
+    "aasm_graphs_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),                     # host, device, gb
+    "aasm_graphs_wrap_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),    # dev, device, stream, gb
+    "aasm_graphs_view": (C.c_int, [C.c_void_p, C.c_void_p]),                                # gb, dev_view
+    "aasm_graphs_free": (None, [C.c_void_p]),                                               # gb
+    "aasm_sssp_dijkstra_device": (C.c_int, [C.c_void_p] * 5),                               # gb, src, d5, prev, stream
+    "aasm_sssp_bellman_ford_device": (C.c_int, [C.c_void_p] * 8),                           # gb, src, d5, prev, status, cycle_off, cycle, stream
+    "aasm_topology_sort_device": (C.c_int, [C.c_void_p] * 4),                               # gb, order, status, stream
+    "aasm_sssp_dag_device": (C.c_int, [C.c_void_p] * 7),                                    # gb, src, d5, prev, order, status, stream
+    "aasm_sssp_dial_device": (C.c_int, [C.c_void_p] * 6),                                   # gb, src, dist, pre, status, stream
+}
+
+
 def dag_outputs(g_voff, relax=True):
     """The caller's arrays of aasm_sssp_dag for a batch: d5 [VT, 5], prev [VT], order [VT], status [G]; of aasm_topology_sort
     (relax=False) the last two."""

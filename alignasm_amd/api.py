@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (DAG_ARGTYPES, dag_outputs, AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+from ._abi import (DAG_ARGTYPES, GRAPHS_SIGS, GraphsIn, dag_outputs, AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
                    DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, bellman_ford_outputs, graph_inputs, ksw_inputs, unpack_cycles, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,6 +83,9 @@ def _load():
     for name, argtypes in DAG_ARGTYPES.items():                       # aasm_topology_sort, aasm_sssp_dag
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, (restype, argtypes) in GRAPHS_SIGS.items():             # resident graph batches
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
@@ -97,6 +100,8 @@ EXPORTED = [
     "aasm_result_sizes", "aasm_result_export", "aasm_k_shortest_walks", "aasm_ksw_free", "aasm_cut_plans_device", "aasm_writer_append_cuts",
     "aasm_paf_parse_device", "aasm_paf_read_device", "aasm_paf_parse_device_rows", "aasm_paf_read_device_rows",
     "aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device", "aasm_paf_merge_alt_device",
+    "aasm_graphs_upload", "aasm_graphs_wrap_device", "aasm_graphs_view", "aasm_graphs_free", "aasm_sssp_dijkstra_device",
+    "aasm_sssp_bellman_ford_device", "aasm_topology_sort_device", "aasm_sssp_dag_device", "aasm_sssp_dial_device",
 ]
 
 
@@ -199,6 +204,156 @@ def sssp_dial(g_voff, rowptr, col, cost, src, lim=2, device=0):
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     _check(LIB.aasm_sssp_dial(C.c_int64(len(g_voff) - 1), P(g_voff), P(rowptr), P(col), P(cost), P(src), int(lim), P(dist), P(pre), int(device)))
     return dist, pre
+
+
+class GraphResult(dict):
+    """What GraphBatch's methods return: a dict of torch tensors on the device, by the host entries' names; torch_to_numpy knows it."""
+
+
+class GraphBatch:
+    """A checked graph batch (sssp_dijkstra's layout) resident on one device: the five graph entries over it take their sources and
+    leave their results on the device, without the checks, the upload and the download of a host-pointer call.  The methods return
+    GraphResult dicts of torch tensors in the host entries' shapes - word for word what sssp_dijkstra / sssp_bellman_ford / topology_sort /
+    sssp_dag / sssp_dial return for the same graphs and sources (bellman_ford's cycles packed as cycle_off / cycle; dial with a
+    status per graph) - made on the current torch stream of the device (or stream=) and tied to it with record_stream;
+    torch_to_numpy brings such a dict to the host.  src: a numpy array (uploaded on that stream) or a contiguous int32 device
+    tensor that is ready on it.  dijkstra waits for its result; the others return once their sources are checked."""
+
+    def __init__(self, handle, device, keep=None):
+        self._h, self.device, self._keep = handle, int(device), keep
+        v = GraphsIn()
+        _check(LIB.aasm_graphs_view(self._h, C.byref(v)))
+        self.dev_view, self.n_graphs, self.n_vertices, self.n_edges = v, int(v.n_graphs), int(v.n_vertices), int(v.n_edges)
+
+    @classmethod
+    def upload(cls, g_voff, rowptr, col, w5=None, cost=None, lim=2, device=0):
+        """From numpy arrays (aasm_graphs_upload: checked on the host, copied).  w5 / cost: what the batch will be asked for -
+        dijkstra, bellman_ford and dag need w5, dial needs cost (0 .. lim <= 7)."""
+        g_voff, rowptr, col, _, _, w5, cost = graph_inputs(g_voff, rowptr, col, None, w5=w5, cost=cost)
+        P = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        ne = len(col)
+        if not ne:                                                   # (col must not be NULL)
+            col = np.zeros(1, np.int32)
+        gi = GraphsIn(len(g_voff) - 1, len(rowptr) - 1, ne, P(g_voff), P(rowptr), P(col), P(w5), P(cost), int(lim), 0)
+        h = C.c_void_p()
+        _check(LIB.aasm_graphs_upload(C.byref(gi), int(device), C.byref(h)))
+        return cls(h, device)
+
+    @classmethod
+    def from_torch(cls, g_voff, rowptr, col, w5=None, cost=None, lim=2):
+        """Over contiguous tensors that are already on a device (aasm_graphs_wrap_device): g_voff, rowptr int64, col int32, w5 int64
+        [E, 5] or flat, cost int32.  The tensors are borrowed - never written; the batch keeps references, and they must stay
+        unchanged while it lives - and checked on the device.  The tensors' current stream is waited for first."""
+        import torch
+        _check_one_hip_runtime()
+        want = (("g_voff", g_voff, torch.int64), ("rowptr", rowptr, torch.int64), ("col", col, torch.int32), ("w5", w5, torch.int64), ("cost", cost, torch.int32))
+        for name, t, dt in want:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.device != g_voff.device):
+                raise AlignasmError(AASM_E_INVAL, f"from_torch: {name} must be a contiguous {dt} tensor on the batch's device")
+        device = g_voff.device.index if g_voff.device.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(device)
+        stream.synchronize()
+        ne = int(col.numel())
+        if (w5 is not None and w5.numel() != 5 * ne) or (cost is not None and cost.numel() != ne):
+            raise ValueError("from_torch: w5 needs 5 words and cost one word per entry of col")
+        P = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        keep = [g_voff, rowptr, col, w5, cost]
+        if not ne:                                                   # (an empty tensor has no address; col must not be NULL)
+            keep.append(torch.zeros(1, dtype=torch.int32, device=g_voff.device))
+        gi = GraphsIn(int(g_voff.numel()) - 1, int(rowptr.numel()) - 1, ne, P(g_voff), P(rowptr), P(col) if ne else keep[-1].data_ptr(), P(w5) if ne else None,
+                      P(cost) if ne else None, int(lim), 0)
+        if not ne:                                                   # (what the batch may be asked for is kept: empty arrays of their own)
+            gi.w5 = keep[-1].data_ptr() if w5 is not None else None
+            gi.cost = keep[-1].data_ptr() if cost is not None else None
+        h = C.c_void_p()
+        _check(LIB.aasm_graphs_wrap_device(C.byref(gi), int(device), C.c_void_p(stream.cuda_stream or 0), C.byref(h)))
+        return cls(h, device, keep)
+
+    def _begin(self, src, stream):
+        import torch
+        _check_one_hip_runtime()
+        if not self._h:
+            raise AlignasmError(AASM_E_INVAL, "the graph batch is closed")
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        if src is not None and not isinstance(src, torch.Tensor):
+            src = np.ascontiguousarray(src, np.int32).reshape(-1)
+            if len(src) != self.n_graphs:
+                raise ValueError(f"src: {len(src)} entries, {self.n_graphs} needed")
+            with torch.cuda.device(dev), torch.cuda.stream(stream):
+                src = torch.from_numpy(src).to(dev)
+        elif src is not None and (not src.is_cuda or src.dtype != torch.int32 or not src.is_contiguous() or src.numel() != self.n_graphs):
+            raise AlignasmError(AASM_E_INVAL, "src must be a contiguous int32 device tensor with one entry per graph")
+        if src is not None:
+            src.record_stream(stream)
+
+        def empty(shape, dtype):
+            with torch.cuda.device(dev), torch.cuda.stream(stream):
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            t.record_stream(stream)                                  # (the caching allocator hands a freed block to other work)
+            return t
+        return torch, src, stream, empty
+
+    @staticmethod
+    def _p(t):
+        return None if t is None or not t.numel() else t.data_ptr()
+
+    def dijkstra(self, src, stream=None):
+        """-> {"d": [V, 5] int64, "prev": [V] int32}; waits for the result (its heap room grows while a graph runs out of it)."""
+        torch, src, stream, empty = self._begin(src, stream)
+        d, prev = empty((self.n_vertices, 5), torch.int64), empty(self.n_vertices, torch.int32)
+        _check(LIB.aasm_sssp_dijkstra_device(self._h, self._p(src), self._p(d), self._p(prev), stream.cuda_stream or None))
+        return GraphResult(d=d, prev=prev)
+
+    def bellman_ford(self, src, stream=None):
+        """-> {"d", "prev", "status": [G] int32, "cycle_off": [G + 1] int64, "cycle": [V + G] int32}: graph g's closed cycle (status 1)
+        is cycle[cycle_off[g]:cycle_off[g + 1]]; the list is packed on the device, and cycle beyond cycle_off[G] is not written."""
+        torch, src, stream, empty = self._begin(src, stream)
+        G, V = self.n_graphs, self.n_vertices
+        out = GraphResult({"d": empty((V, 5), torch.int64), "prev": empty(V, torch.int32), "status": empty(G, torch.int32), "cycle_off": empty(G + 1, torch.int64),
+                           "cycle": empty(V + G, torch.int32)})
+        _check(LIB.aasm_sssp_bellman_ford_device(self._h, self._p(src), *(self._p(out[k]) for k in ("d", "prev", "status", "cycle_off", "cycle")),
+                                                 stream.cuda_stream or None))
+        return out
+
+    def topology_sort(self, stream=None):
+        """-> {"order": [V] int32, "status": [G] int32}."""
+        torch, _, stream, empty = self._begin(None, stream)
+        out = GraphResult(order=empty(self.n_vertices, torch.int32), status=empty(self.n_graphs, torch.int32))
+        _check(LIB.aasm_topology_sort_device(self._h, self._p(out["order"]), self._p(out["status"]), stream.cuda_stream or None))
+        return out
+
+    def dag(self, src, order=False, stream=None):
+        """-> {"d", "prev", "status"}, and with order=True "order"."""
+        torch, src, stream, empty = self._begin(src, stream)
+        G, V = self.n_graphs, self.n_vertices
+        out = GraphResult(d=empty((V, 5), torch.int64), prev=empty(V, torch.int32), status=empty(G, torch.int32))
+        if order:
+            out["order"] = empty(V, torch.int32)
+        _check(LIB.aasm_sssp_dag_device(self._h, self._p(src), self._p(out["d"]), self._p(out["prev"]), self._p(out.get("order")), self._p(out["status"]),
+                                        stream.cuda_stream or None))
+        return out
+
+    def dial(self, src, stream=None):
+        """-> {"dist": [V] int64, "pre": [V] int64, "status": [G] int32 (0; AASM_E_INTERNAL for a bucket overflow, which must not happen)}."""
+        torch, src, stream, empty = self._begin(src, stream)
+        out = GraphResult(dist=empty(self.n_vertices, torch.int64), pre=empty(self.n_vertices, torch.int64), status=empty(self.n_graphs, torch.int32))
+        _check(LIB.aasm_sssp_dial_device(self._h, self._p(src), self._p(out["dist"]), self._p(out["pre"]), self._p(out["status"]), stream.cuda_stream or None))
+        return out
+
+    def close(self):
+        """Waits for the batch's work in flight, then frees what it owns (borrowed tensors are only released)."""
+        if self._h:
+            LIB.aasm_graphs_free(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def debug_counter(name):
@@ -691,7 +846,10 @@ def _check_one_hip_runtime():
 
 def torch_to_numpy(d):
     """DeviceResult.to_torch()'s dict -> unpack_out()'s numpy form (without `stats`).  The copies to the host are ordered on
-    the device's current torch stream: export on another stream, and that stream has to be waited for first."""
+    the device's current torch stream: export on another stream, and that stream has to be waited for first.
+    A GraphResult (what GraphBatch's methods return): every tensor as the numpy array the host entry returns."""
+    if isinstance(d, GraphResult):
+        return {k: t.cpu().numpy() for k, t in d.items()}
     out = {"n_contigs": int(d["n_contigs"])}
     for k in ("main_off", "alt_off", "all_path_off", "all_elem_off", "status"):
         out[k] = d[k].cpu().numpy()

@@ -3,7 +3,8 @@
 // * one named __global__ per row of the kernel tables (row shapes: aasm_dev.h; tables: aasm_pipeline.h, aasm_sssp.h, aasm_ksw.h,
 //   aasm_cut.h, aasm_read.h, aasm_rows.h), from ONE generator, so rocprofv3 --kernel-trace shows `aasm_k6_rev_sweep` etc., and ONE launch (launch_row);
 // * the generic graph entries (dijkstra, Dial, k shortest walks): bodies, argument checks and host drivers in aasm_sssp.h and
-//   aasm_ksw.h, run here through one backend (GraphGpu);
+//   aasm_ksw.h, run here through one backend (GraphGpu); their resident form (aasm_graphs.h: a checked batch on the device, device
+//   pointers in and out on the caller's stream) through GraphsGpu;
 // * exclusive scans (count -> offsets): ONE launch each, single pass with decoupled look-back (aasm_scan_chain);
 // * a per-device arena: device memory is carved by bump allocation out of a few large
 //   hipMalloc blocks that persist across solves (no hipMalloc in the steady state);
@@ -26,6 +27,7 @@
 
 #include "aasm_pipeline.h"
 #include "aasm_ksw.h"
+#include "aasm_graphs.h"
 #include "aasm_cut.h"
 #include "aasm_read.h"
 #include "aasm_alt.h"
@@ -71,6 +73,10 @@ AASM_PACK_KERNELS(K, KL)
 #define AASM_FAMILY (SsspArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_SSSP_KERNELS(K, KL)
 #undef AASM_FAMILY
+// ... the kernels around them on a resident graph batch (aasm_graphs.h) ...
+#define AASM_FAMILY (GraphsArgs a), (int64_t)blockIdx.x, a, AASM_DIRECT
+AASM_GRAPHS_KERNELS(K, KL)
+#undef AASM_FAMILY
 // ... and aasm_ksw.h (★K: a launch covers the graphs [g0, g0 + grid))
 #define AASM_FAMILY (int64_t g0, KswArgs a), g0 + (int64_t)blockIdx.x, a, AASM_DIRECT
 AASM_KSW_KERNELS(K, KL)
@@ -101,6 +107,7 @@ template <class... P> struct KernelSym { void (*fn)(P...); const char *name; int
 static const KernelSym<WS> pipeline_syms[] = {AASM_PIPELINE_KERNELS(K, K)};
 static const KernelSym<PackArgs> pack_syms[] = {AASM_PACK_KERNELS(K, K)};
 static const KernelSym<SsspArgs> sssp_syms[] = {AASM_SSSP_KERNELS(K, K)};
+static const KernelSym<GraphsArgs> graphs_syms[] = {AASM_GRAPHS_KERNELS(K, K)};
 static const KernelSym<int64_t, KswArgs> ksw_syms[] = {AASM_KSW_KERNELS(K, K)};
 static const KernelSym<CutArgs> cut_syms[] = {AASM_CUT_KERNELS(K, K)};
 static const KernelSym<ReadArgs> read_syms[] = {AASM_READ_KERNELS(K, K)};
@@ -1063,6 +1070,154 @@ int aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowpt
     const char *why = "";
     const int rc = dial_check_args(n_graphs, g_voff, rowptr, col, cost, src, lim, dist, pre, &why);
     return graph_entry("aasm_sssp_dial", rc, why, device, [&](GraphGpu &be) { return dial_run(be, n_graphs, g_voff, rowptr, col, cost, src, lim, dist, pre, &why); });
+}
+
+// ---- resident graph batches (aasm_graphs.h): the five entries above with device pointers in and out, on the caller's stream ----
+extern "C++" {
+namespace {
+// The backend of one call on a resident batch: the call's stream; memory that outlives it (the handle frees it).
+struct GraphsGpu {
+    int device;
+    hipStream_t stream;
+    hipEvent_t ev;                                                   // the handle's event (nullptr while the handle is being made)
+    hipStream_t last;                                                // the stream of the handle's latest call
+    hipError_t e = hipSuccess;
+    bool entered = false;                                            // something was enqueued
+    // before the call's first enqueue: a stream other than the latest call's waits for that call's event
+    bool ready() {
+        if (!entered) { entered = true; if (ev && stream != last && e == hipSuccess) e = hipStreamWaitEvent(stream, ev, 0); }
+        return e == hipSuccess;
+    }
+    void *alloc(size_t n) {
+        void *p = nullptr;
+        if (e != hipSuccess) return nullptr;
+        if ((e = hipMalloc(&p, n ? n : 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return p;
+    }
+    void free_dev(void *p) { (void)hipFree(p); }
+    bool h2d(void *d, const void *h, size_t n) { return ready() && (e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)) == hipSuccess; }
+    bool fill(void *d, int byte, size_t n) { return ready() && (e = hipMemsetAsync(d, byte, n, stream)) == hipSuccess; }
+    bool sync() { return e == hipSuccess && (e = hipStreamSynchronize(stream)) == hipSuccess; }
+    bool read(void *h, const void *d, size_t n) {
+        if (ready()) e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream);
+        return sync();
+    }
+    void poison(void *d, size_t n) { if (const int pz = poison_byte()) { if (n) fill(d, pz, n); } }
+    void quiesce() { if (ev && e == hipSuccess) e = hipEventSynchronize(ev); }
+    bool dev_ok(const void *p, int64_t n, size_t align) { return dev_buffer_ok(p, n, align, device); }
+    bool launched() { return e == hipSuccess && (e = hipGetLastError()) == hipSuccess; }
+    bool launch_gr(int kid, int64_t nblocks, const GraphsArgs &a) {
+        if (!ready()) return false;
+        launch_row(graphs_syms, kid, nblocks, 0, stream, a);
+        return launched();
+    }
+    bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
+        if (!ready()) return false;
+        launch_row(sssp_syms, kid, n_graphs, 0, stream, a);
+        return launched();
+    }
+    int err() {
+        if (e == hipSuccess) { e = hipErrorOutOfMemory; }
+        return e == hipErrorOutOfMemory ? AASM_E_NOMEM : AASM_E_HIP;
+    }
+};
+}  // namespace
+
+struct aasm_graphs {
+    int device;
+    GraphsCore *core;
+    hipEvent_t ev;                                                   // recorded behind each call
+    hipStream_t last;                                                // the stream of the latest call
+    std::mutex mu;
+};
+
+// rc of a creation or a call as the entry returns it: the checks' message, or the HIP error's
+static int graphs_result(const char *entry, int rc, const char *why, const GraphsGpu &be) {
+    if (rc == AASM_OK) return rc;
+    if (*why) set_last_error(std::string(entry) + ": " + why);
+    else set_last_error(be.e == hipSuccess ? std::string(entry) + ": failed" : hip_err(entry, be.e));
+    return rc;
+}
+static int graphs_make(const char *entry, const aasm_graphs_in *in, int device, hipStream_t stream, bool wrap, aasm_graphs **gb) {
+    if (!in || !gb) { set_last_error(std::string(entry) + ": NULL argument"); return AASM_E_INVAL; }
+    *gb = nullptr;
+    const char *why = "";
+    GraphsGpu be{device, stream, nullptr, nullptr};
+    int rc = wrap ? AASM_OK : graphs_check_host(*in, &why);          // (an upload is checked on the host, before any device is touched)
+    if (rc != AASM_OK) return graphs_result(entry, rc, why, be);
+    if ((rc = ctx_init(device)) != AASM_OK) return rc;
+    hipSetDevice(device);
+    if (!wrap) be.stream = g_ctx[device].stream;
+    GraphsCore *core = nullptr;
+    rc = wrap ? graphs_wrap(be, *in, &core, &why) : graphs_upload(be, *in, &core);
+    if (rc != AASM_OK) return graphs_result(entry, rc, why, be);
+    aasm_graphs *h = new aasm_graphs;
+    h->device = device; h->core = core; h->last = be.stream;
+    if ((be.e = hipEventCreateWithFlags(&h->ev, hipEventDisableTiming)) != hipSuccess || (be.e = hipEventRecord(h->ev, be.stream)) != hipSuccess) {
+        graphs_destroy(be, core);
+        delete h;
+        return graphs_result(entry, AASM_E_HIP, why, be);
+    }
+    *gb = h;
+    return AASM_OK;
+}
+// One call on a handle: under its lock; a stream other than the latest call's waits for that call's event first; run(be, why) is the
+// driver; the event is recorded behind whatever was enqueued.
+template <class Run> static int graphs_call(const char *entry, aasm_graphs *gb, void *stream, Run run) {
+    if (!gb) { set_last_error(std::string(entry) + ": NULL handle"); return AASM_E_INVAL; }
+    std::lock_guard<std::mutex> lk(gb->mu);
+    hipSetDevice(gb->device);
+    GraphsGpu be{gb->device, (hipStream_t)stream, gb->ev, gb->last};
+    const char *why = "";
+    int rc = run(be, &why);
+    if (be.entered) {                                                // (a call refused by its checks has enqueued nothing)
+        gb->last = be.stream;
+        const hipError_t er = hipEventRecord(gb->ev, be.stream);
+        if (rc == AASM_OK && er != hipSuccess) { be.e = er; rc = AASM_E_HIP; }
+    }
+    return graphs_result(entry, rc, why, be);
+}
+}  // extern "C++"
+
+int aasm_graphs_upload(const aasm_graphs_in *host, int device, aasm_graphs **gb) { return graphs_make("aasm_graphs_upload", host, device, nullptr, false, gb); }
+int aasm_graphs_wrap_device(const aasm_graphs_in *dev, int device, void *stream, aasm_graphs **gb) {
+    return graphs_make("aasm_graphs_wrap_device", dev, device, (hipStream_t)stream, true, gb);
+}
+int aasm_graphs_view(const aasm_graphs *gb, aasm_graphs_in *dev_view) {
+    if (!gb || !dev_view) return AASM_E_INVAL;
+    *dev_view = gb->core->view;
+    return AASM_OK;
+}
+void aasm_graphs_free(aasm_graphs *gb) {
+    if (!gb) return;
+    hipSetDevice(gb->device);
+    (void)hipEventSynchronize(gb->ev);
+    GraphsGpu be{gb->device, nullptr, nullptr, nullptr};
+    graphs_destroy(be, gb->core);
+    (void)hipEventDestroy(gb->ev);
+    delete gb;
+}
+int aasm_sssp_dijkstra_device(aasm_graphs *gb, const int32_t *src, int64_t *d5, int32_t *prev, void *stream) {
+    return graphs_call("aasm_sssp_dijkstra_device", gb, stream, [&](GraphsGpu &be, const char **why) { return graphs_dijkstra(be, *gb->core, src, d5, prev, why); });
+}
+int aasm_sssp_bellman_ford_device(aasm_graphs *gb, const int32_t *src, int64_t *d5, int32_t *prev, int32_t *status, int64_t *cycle_off, int32_t *cycle,
+                                  void *stream) {
+    return graphs_call("aasm_sssp_bellman_ford_device", gb, stream, [&](GraphsGpu &be, const char **why) {
+        return graphs_bellman_ford(be, *gb->core, src, d5, prev, status, cycle_off, cycle, why);
+    });
+}
+int aasm_topology_sort_device(aasm_graphs *gb, int32_t *order, int32_t *status, void *stream) {
+    return graphs_call("aasm_topology_sort_device", gb, stream, [&](GraphsGpu &be, const char **why) {
+        return graphs_dag(be, *gb->core, nullptr, nullptr, nullptr, order, status, true, why);
+    });
+}
+int aasm_sssp_dag_device(aasm_graphs *gb, const int32_t *src, int64_t *d5, int32_t *prev, int32_t *order, int32_t *status, void *stream) {
+    return graphs_call("aasm_sssp_dag_device", gb, stream, [&](GraphsGpu &be, const char **why) {
+        return graphs_dag(be, *gb->core, src, d5, prev, order, status, false, why);
+    });
+}
+int aasm_sssp_dial_device(aasm_graphs *gb, const int32_t *src, int64_t *dist, int64_t *pre, int32_t *status, void *stream) {
+    return graphs_call("aasm_sssp_dial_device", gb, stream, [&](GraphsGpu &be, const char **why) { return graphs_dial(be, *gb->core, src, dist, pre, status, why); });
 }
 
 // k shortest walks (k_shortest_walks.hpp:177-290, is_dag = true) over a batch of DAGs; host pointers in, library-allocated out

@@ -516,9 +516,11 @@ static inline int check_fail(const char **why, int rc, const std::string &msg) {
 // The common layout of a graph batch.  Returns AASM_OK, or AASM_E_INVAL with a message in *why.  The offsets are checked first
 // (g_voff from 0 and strictly increasing, then rowptr from 0 and non-decreasing), and only then is anything read through them.
 // more: the entry's other pointers, which must not be NULL either.  has_src = false: an entry without sources (aasm_topology_sort);
-// src is then neither required nor read.
+// src is then neither required nor read.  n_vertices / n_edges >= 0: the arrays' lengths as the caller of a resident batch states them
+// (aasm_graphs.h), which the offsets must end at; each is asked before anything is read through the offsets it closes.
 static inline int check_graph_batch(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *src,
-                                    std::initializer_list<const void *> more, const char **why, bool has_src = true) {
+                                    std::initializer_list<const void *> more, const char **why, bool has_src = true, int64_t n_vertices = -1,
+                                    int64_t n_edges = -1) {
     bool null = !g_voff || !rowptr || !col || (has_src && !src);
     for (const void *p : more) null |= !p;
     if (n_graphs <= 0 || null) return check_fail(why, AASM_E_INVAL, "empty batch or NULL pointer");
@@ -526,9 +528,11 @@ static inline int check_graph_batch(int64_t n_graphs, const int64_t *g_voff, con
     for (int64_t g = 0; g < n_graphs; g++)
         if (g_voff[g + 1] <= g_voff[g]) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": empty, or graph offsets not increasing");
     const int64_t VT = g_voff[n_graphs];
+    if (n_vertices >= 0 && VT != n_vertices) return check_fail(why, AASM_E_INVAL, "graph offsets do not end at n_vertices");
     if (rowptr[0] != 0) return check_fail(why, AASM_E_INVAL, "row pointers do not start at 0");
     for (int64_t v = 0; v < VT; v++)
         if (rowptr[v + 1] < rowptr[v]) return check_fail(why, AASM_E_INVAL, "row pointers decrease at vertex " + std::to_string(v));
+    if (n_edges >= 0 && rowptr[VT] != n_edges) return check_fail(why, AASM_E_INVAL, "row pointers do not end at n_edges");
     for (int64_t g = 0; g < n_graphs; g++) {
         const int64_t v0 = g_voff[g], v1 = g_voff[g + 1];
         if (has_src && (src[g] < 0 || src[g] >= v1 - v0)) return check_fail(why, AASM_E_INVAL, "graph " + std::to_string(g) + ": source outside it");
@@ -543,12 +547,15 @@ static inline void put_d5(int64_t *o, const Dist &x) { o[0] = x.qry; o[1] = x.re
 
 // The w5 weight domain of dijkstra and k-walks; with `negative` (bellman_ford, AASM_KSW_NEGATIVE) without the clause on the score
 // sum's sign.  AASM_OK, or AASM_E_OVERFLOW.
+static inline int w5_fail(int64_t e, bool negative, const char **why) {
+    return check_fail(why, AASM_E_OVERFLOW, "edge " + std::to_string(e) + ": weight outside the supported range (" + (negative ? "" : "score sum >= 0, ") + "|scores| < 2^39, anom 0..2, mapq counts 0..1)");
+}
 static inline int check_w5(const int64_t *w5, int64_t n_edges, bool negative, const char **why) {
     const int64_t lim = (int64_t)1 << 39;
     for (int64_t e = 0; e < n_edges; e++) {
         const int64_t *w = w5 + 5 * e;
         if (w[0] < -lim || w[0] >= lim || w[1] < -lim || w[1] >= lim || (!negative && w[0] + w[1] < 0) || w[2] < 0 || w[2] > 2 || w[3] < 0 || w[3] > 1 || w[4] < 0 || w[4] > 1)
-            return check_fail(why, AASM_E_OVERFLOW, "edge " + std::to_string(e) + ": weight outside the supported range (" + (negative ? "" : "score sum >= 0, ") + "|scores| < 2^39, anom 0..2, mapq counts 0..1)");
+            return w5_fail(e, negative, why);
     }
     return AASM_OK;
 }
@@ -582,14 +589,21 @@ static inline int dag_check_args(int64_t n_graphs, const int64_t *g_voff, const 
     }
     return sort_only ? AASM_OK : check_w5(w5, rowptr[g_voff[n_graphs]], true, why);
 }
+// Dial's lim and the cost range
+static inline int dial_lim_fail(const char **why) { return check_fail(why, AASM_E_INVAL, "lim outside 0 .. 7"); }
+static inline int dial_cost_fail(int64_t e, const char **why) {
+    return check_fail(why, AASM_E_INVAL, "edge " + std::to_string(e) + ": cost outside 0 .. lim (the reference asserts it, k_weighted_bfs.hpp:27)");
+}
+static inline int check_dial_costs(const int32_t *cost, int64_t n_edges, int lim, const char **why) {
+    if (lim < 0 || lim >= DIAL_MAXB) return dial_lim_fail(why);
+    for (int64_t e = 0; e < n_edges; e++)
+        if (cost[e] < 0 || cost[e] > lim) return dial_cost_fail(e, why);
+    return AASM_OK;
+}
 static inline int dial_check_args(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
                                   const int32_t *src, int lim, const int64_t *dist, const int64_t *pre, const char **why) {
     const int rc = check_graph_batch(n_graphs, g_voff, rowptr, col, src, {cost, dist, pre}, why);
-    if (rc != AASM_OK) return rc;
-    if (lim < 0 || lim + 1 > DIAL_MAXB) return check_fail(why, AASM_E_INVAL, "lim outside 0 .. 7");
-    for (int64_t e = 0; e < rowptr[g_voff[n_graphs]]; e++)
-        if (cost[e] < 0 || cost[e] > lim) return check_fail(why, AASM_E_INVAL, "edge " + std::to_string(e) + ": cost outside 0 .. lim (the reference asserts it, k_weighted_bfs.hpp:27)");
-    return AASM_OK;
+    return rc != AASM_OK ? rc : check_dial_costs(cost, rowptr[g_voff[n_graphs]], lim, why);
 }
 
 // Device memory of one driver run through backend BE: after the first failure `ok` stays false and every later call returns

@@ -270,6 +270,57 @@ int  aasm_sssp_dag(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowpt
 int  aasm_sssp_dial(int64_t n_graphs, const int64_t *g_voff, const int64_t *rowptr, const int32_t *col, const int32_t *cost,
                     const int32_t *src, int lim, int64_t *dist, int64_t *pre, int device);
 
+/* ---- Resident graph batches: the five entries above over a checked batch that lives on one device, results left on the device ----
+ * A batch is checked and made resident ONCE (aasm_graphs_upload from host arrays, which are copied and owned by the handle;
+ * aasm_graphs_wrap_device over DEVICE arrays, which are borrowed: never written, never freed, and kept alive and unchanged by the
+ * caller while the handle lives).  The *_device entries then take `src` and every output as DEVICE arrays the caller owns, in the
+ * host entries' shapes (d5 [n_vertices * 5], prev / order / dist / pre [n_vertices], status [n_graphs], cycle_off [n_graphs + 1],
+ * cycle room for n_vertices + n_graphs), enqueue everything on `stream` (a hipStream_t of the device, NULL = the null stream) and
+ * touch no output outside its stated length.  When the stream gets there every output holds, word for word, what the host entry of
+ * the same name returns for the same graphs and sources, with two differences: aasm_sssp_dial_device reports Dial's must-not-happen
+ * bucket overflow as status[g] = AASM_E_INTERNAL instead of failing the call, and cycle_off / cycle are packed on the device.
+ *
+ * Pointers (as aasm_result_export): an array that is not empty must be memory of the batch's device, aligned to 8 bytes (4 for
+ * int32 arrays) - else AASM_E_INVAL and nothing is enqueued; col must be non-NULL even with n_edges == 0.
+ * An array's SIZE is not checked: the lengths are the caller's word, and an overstated one makes the kernels read past the array.
+ * Creation checks: the host entries' (layout; the w5 domain of aasm_sssp_bellman_ford; with cost, lim 0..7 and the cost range), with
+ * the host entries' codes and message texts, plus "graph offsets do not end at n_vertices" and "row pointers do not end at n_edges"
+ * (AASM_E_INVAL).  aasm_graphs_wrap_device runs them as kernels in three stages (graph offsets, row pointers, edges), the host
+ * reading one verdict word between stages: nothing is read through an offset before the stage that validated it has passed.  The
+ * handle remembers the first edge whose score sum is negative: aasm_sssp_dijkstra_device on such a batch returns aasm_sssp_dijkstra's
+ * AASM_E_OVERFLOW and message for it; bellman_ford and dag accept it.
+ * Per call: the entry's size limits (2^20 vertices for _dag_device, fewer than 2^31 vertices or edges per graph) from counts the
+ * handle keeps on the host; the sources by a small kernel whose one-word verdict is read back ("graph g: source outside it",
+ * AASM_E_INVAL, nothing more enqueued); an entry whose array the batch lacks (w5, cost) is AASM_E_INVAL.
+ * Waiting: topology_sort, dag, bellman_ford and dial return without waiting for the solve (their only host wait is the source
+ * verdict; topology_sort has none).  dijkstra waits to the end: its heap room grows 1x, 4x, 16x, 64x for as long as any graph ran out
+ * of it (one word per round, reduced on the device), and at 64x it returns aasm_sssp_dijkstra's AASM_E_OVERFLOW and message.
+ * Working memory belongs to the handle, grows on demand and is kept between calls (aasm_debug_poison fills it before each call).  The
+ * handle records an event behind each call, and a call on another stream makes that stream wait for it first: two streams may share
+ * a handle.  aasm_graphs_free waits for the handle's work in flight; NULL is accepted. */
+typedef struct aasm_graphs aasm_graphs;           /* a checked graph batch resident on one device */
+typedef struct aasm_graphs_in {
+    int64_t n_graphs, n_vertices, n_edges;        /* the arrays' lengths, stated by the caller */
+    const int64_t *g_voff;   /* [n_graphs+1]   */
+    const int64_t *rowptr;   /* [n_vertices+1] */
+    const int32_t *col;      /* [n_edges]      */
+    const int64_t *w5;       /* [n_edges*5] or NULL: no dijkstra / bellman_ford / dag on this batch */
+    const int32_t *cost;     /* [n_edges]   or NULL: no dial */
+    int32_t lim, reserved;   /* dial's lim (0..7), read only with cost */
+} aasm_graphs_in;
+int  aasm_graphs_upload(const aasm_graphs_in *host, int device, aasm_graphs **gb);              /* copies; the handle owns them */
+int  aasm_graphs_wrap_device(const aasm_graphs_in *dev, int device, void *stream, aasm_graphs **gb); /* borrows; checked ON the device */
+int  aasm_graphs_view(const aasm_graphs *gb, aasm_graphs_in *dev_view);
+void aasm_graphs_free(aasm_graphs *gb);           /* waits for the handle's work in flight */
+
+int  aasm_sssp_dijkstra_device    (aasm_graphs *gb, const int32_t *src, int64_t *d5, int32_t *prev, void *stream);
+int  aasm_sssp_bellman_ford_device(aasm_graphs *gb, const int32_t *src, int64_t *d5, int32_t *prev, int32_t *status,
+                                   int64_t *cycle_off, int32_t *cycle, void *stream);
+int  aasm_topology_sort_device    (aasm_graphs *gb, int32_t *order, int32_t *status, void *stream);
+int  aasm_sssp_dag_device         (aasm_graphs *gb, const int32_t *src, int64_t *d5, int32_t *prev, int32_t *order /* may be NULL */,
+                                   int32_t *status, void *stream);
+int  aasm_sssp_dial_device        (aasm_graphs *gb, const int32_t *src, int64_t *dist, int64_t *pre, int32_t *status, void *stream);
+
 /* The solver's k shortest walks, k_shortest_walks(source, sink, k) with is_dag = true and kth_shortest_walk_recover()
  * (src/k_shortest_walks.hpp:177-290), over a batch of DAGs in aasm_sssp_dijkstra's layout and weight domain (score sum >= 0,
  * |scores| < 2^39, anom 0..2, qul counts 0..1), at most 2^20 vertices per graph, 1 <= k <= 2^24.  Results are the
