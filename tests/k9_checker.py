@@ -121,11 +121,17 @@ def window_dp(g, a, b, wl=None):
 
 
 def enumerate_paths(g, a, b, wl=None, limit=200000):
-    """Every a -> b path (a DAG: all of them stay inside the window of topological positions); None when there are too many."""
+    """Every a -> b path (a DAG: all of them stay inside the window of topological positions); None when there are more than
+    `limit`, or when more than 4 * limit + 1000 prefixes had to be visited (prefixes that the whitelist never lets reach b are
+    work too): None means too many paths OR too much work."""
     out, stack = [], [(a, [a], Dist())]
     pb = int(g.pos[b])
+    steps = 0
     while stack:
         u, path, d = stack.pop()
+        steps += 1
+        if steps > 4 * limit + 1000:
+            return None
         for v, w in g.out(u):
             if int(g.pos[v]) > pb or not _hop_allowed(g, u, v, b, wl):
                 continue
@@ -166,9 +172,21 @@ def check_conversion(g, pathA, pathB, brute_max=12, stats=None):
             return
         nwin = int(g.pos[b]) - int(g.pos[a]) + 1
         stats["dp"] = stats.get("dp", 0) + 1
+        win = None
+        if "windows" in stats:                                        # one record per window DP, in call order (tests/k9_cases.py)
+            pa = int(g.pos[a])
+            rows = g.order[pa:pa + nwin - 1]                          # whole rows of the positions [pa, pa + W), as the kernel's forms count them
+            win = dict(a=a, b=b, wl=wl, pa=pa, W=nwin - 1, E=int((g.rowptr[rows + 1] - g.rowptr[rows]).sum()), it=it, out_len=len(mine),
+                       drop_last=drop_last, own=list(own_edges), res=list(zip(vs, vs[1:])), paths=None, ndist=None, skipped=False)
+            win["differs"] = win["res"] != win["own"]
+            stats["windows"].append(win)
         if nwin <= brute_max:
-            allp = enumerate_paths(g, a, b, wl)
+            allp = enumerate_paths(g, a, b, wl, limit=stats.get("path_limit", 200000))
+            if allp is None and win is not None:
+                win["skipped"] = True
             if allp is not None:
+                if win is not None:
+                    win["paths"], win["ndist"] = len(allp), len({dd.key() for _, dd in allp})
                 stats["brute"] = stats.get("brute", 0) + 1
                 stats["brute_paths"] = stats.get("brute_paths", 0) + len(allp)
                 if vs not in [p for p, _ in allp]:
@@ -186,10 +204,12 @@ def check_conversion(g, pathA, pathB, brute_max=12, stats=None):
         mine.extend(es)
 
     it, n = 0, len(pathA)
+    own_edges = []                                                    # the walk's edges the step at hand replaces (the window records read it)
     if n < 2 or pathA[0][0] != src or pathA[-1][1] != dest:
         return ["walk does not run src -> dest"]
     while it < n:
         u, v = pathA[it]
+        own_edges[:] = pathA[it:it + 1] if v == dest and u != src else pathA[it:it + 2]
         if u == src or (v != dest and int(g.v_i[v]) == int(g.v_j[v])):
             cont = src if u == src else mine[-1][1]
             y = int(g.v_j[v])
