@@ -370,6 +370,25 @@ GRAPHS_SIGS = {
 }
 
 
+class KswSizes(C.Structure):
+    """aasm_ksw_sizes: what aasm_k_shortest_walks_device returns and aasm_ksw_export_device takes back unchanged."""
+    _fields_ = [(n, C.c_int64) for n in ("n_graphs", "n_vertices", "k", "n_walks", "n_walk_edges")] + [("flags", C.c_int32), ("reserved", C.c_int32),
+                                                                                                     ("serial", C.c_int64)]
+
+
+class KswDevOut(C.Structure):
+    """aasm_ksw_dev_out: the caller's DEVICE arrays of aasm_ksw_export_device."""
+    _fields_ = [(n, C.c_void_p) for n in ("n_found", "found_off", "dist5", "walk_off", "walk_edges", "d5", "best", "heap_nodes", "status")]
+
+
+# k shortest walks on a resident graph batch (include/alignasm_amd.h): (restype, argtypes) in the header's order.  A table of its
+# own: unlike GRAPHS_SIGS' entries these take scalars (k, flags) beside their pointers.  api.py sets them on the library.
+KSW_DEVICE_SIGS = {
+    "aasm_k_shortest_walks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),   # gb, source, sink, k, flags, stream, sz
+    "aasm_ksw_export_device": (C.c_int, [C.c_void_p] * 4),                                                                       # gb, sz, dst, stream
+}
+
+
 def dag_outputs(g_voff, relax=True):
     """The caller's arrays of aasm_sssp_dag for a batch: d5 [VT, 5], prev [VT], order [VT], status [G]; of aasm_topology_sort
     (relax=False) the last two."""

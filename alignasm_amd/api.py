@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._abi import (DAG_ARGTYPES, GRAPHS_SIGS, GraphsIn, dag_outputs, AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
+from ._abi import (DAG_ARGTYPES, GRAPHS_SIGS, KSW_DEVICE_SIGS, GraphsIn, KswDevOut, KswSizes, dag_outputs, AASM_CUT_ERRORS, AASM_CUT_E_RECORD, AASM_E_INVAL, AASM_E_PARSE, AASM_KSW_CYCLES, AASM_KSW_HOOK_ARENA, AASM_KSW_NEGATIVE, AASM_KSW_TREE, AASM_KSW_WALKS, AASM_OK, AASM_READ_TEXT_ON_DEVICE, CUT_DT, DEBUG_POISON_SIG, OUT_ELEM_DTYPE, BatchIn, BatchOut, Cuts, DevCuts, DevOut,
                    DevRows, HostBatch, RowCols, RowsInfo, KswOut, Opts, OutSizes, Stats, SynthCfg, bellman_ford_outputs, graph_inputs, ksw_inputs, unpack_cycles, make_opts, unpack_ksw, unpack_out)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,7 +83,7 @@ def _load():
     for name, argtypes in DAG_ARGTYPES.items():                       # aasm_topology_sort, aasm_sssp_dag
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, C.c_int
-    for name, (restype, argtypes) in GRAPHS_SIGS.items():             # resident graph batches
+    for name, (restype, argtypes) in list(GRAPHS_SIGS.items()) + list(KSW_DEVICE_SIGS.items()):   # resident graph batches
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
@@ -102,6 +102,7 @@ EXPORTED = [
     "aasm_paf_upload_rows", "aasm_rows_sizes_device", "aasm_rows_format_device", "aasm_writer_append_device", "aasm_paf_merge_alt_device",
     "aasm_graphs_upload", "aasm_graphs_wrap_device", "aasm_graphs_view", "aasm_graphs_free", "aasm_sssp_dijkstra_device",
     "aasm_sssp_bellman_ford_device", "aasm_topology_sort_device", "aasm_sssp_dag_device", "aasm_sssp_dial_device",
+    "aasm_k_shortest_walks_device", "aasm_ksw_export_device",
 ]
 
 
@@ -340,6 +341,41 @@ class GraphBatch:
         torch, src, stream, empty = self._begin(src, stream)
         out = GraphResult(dist=empty(self.n_vertices, torch.int64), pre=empty(self.n_vertices, torch.int64), status=empty(self.n_graphs, torch.int32))
         _check(LIB.aasm_sssp_dial_device(self._h, self._p(src), self._p(out["dist"]), self._p(out["pre"]), self._p(out["status"]), stream.cuda_stream or None))
+        return out
+
+    def k_shortest_walks(self, source, sink, k, walks=True, tree=False, cycles=False, negative=False, stream=None):
+        """k_shortest_walks (the host entry of that name: its flags, statuses and limits) over the batch, which must carry w5; source,
+        sink: numpy arrays or contiguous int32 device tensors, one entry per graph.  -> tensors packed by n_found, never padded to k:
+        {"n_found": [G], "found_off": [G + 1] (its prefix sums), "dist5": [n_walks, 5], "heap_nodes": [G], "status": [G] int32}; with
+        walks, "walk_off": [n_walks + 1] and "walk_edges" (caller CSR positions, source -> sink); with tree, "d5": [V, 5] and "best": [V].
+        Walk i of graph g is walk found_off[g] + i; it equals walk g * k + i of api.k_shortest_walks.  The solve waits for its sizes (a
+        few words read back, whatever G is); the export into the tensors is enqueued on the stream."""
+        sz = self.ksw_solve(source, sink, k, walks=walks, tree=tree, cycles=cycles, negative=negative, stream=stream)
+        return self.ksw_export(sz, stream=stream)
+
+    def ksw_solve(self, source, sink, k, walks=True, tree=False, cycles=False, negative=False, stream=None):
+        """The first half of k_shortest_walks (aasm_k_shortest_walks_device): -> KswSizes, final when it returns.  The result stays in
+        the batch's working memory until the next call on the batch other than ksw_export."""
+        _, source, stream, _ = self._begin(source, stream)
+        sink = self._begin(sink, stream)[1]
+        flags = (AASM_KSW_WALKS if walks else 0) | (AASM_KSW_TREE if tree else 0) | (AASM_KSW_CYCLES if cycles else 0) | (AASM_KSW_NEGATIVE if negative else 0)
+        sz = KswSizes()
+        _check(LIB.aasm_k_shortest_walks_device(self._h, self._p(source), self._p(sink), int(k), flags, stream.cuda_stream or None, C.byref(sz)))
+        return sz
+
+    def ksw_export(self, sz, stream=None):
+        """The second half (aasm_ksw_export_device): tensors allocated from the sizes, the export into them enqueued on the stream.
+        May be called again for the same solve; AlignasmError(AASM_E_INVAL) once another call has taken the working memory."""
+        torch, _, stream, empty = self._begin(None, stream)
+        G, V, NW = self.n_graphs, self.n_vertices, int(sz.n_walks)
+        out = GraphResult(n_found=empty(G, torch.int64), found_off=empty(G + 1, torch.int64), dist5=empty((NW, 5), torch.int64),
+                          heap_nodes=empty(G, torch.int64), status=empty(G, torch.int32))
+        if sz.flags & AASM_KSW_WALKS:
+            out.update(walk_off=empty(NW + 1, torch.int64), walk_edges=empty(int(sz.n_walk_edges), torch.int64))
+        if sz.flags & AASM_KSW_TREE:
+            out.update(d5=empty((V, 5), torch.int64), best=empty(V, torch.int32))
+        dst = KswDevOut(**{name: self._p(out.get(name)) for name, _ in KswDevOut._fields_})
+        _check(LIB.aasm_ksw_export_device(self._h, C.byref(sz), C.byref(dst), stream.cuda_stream or None))
         return out
 
     def close(self):

@@ -1097,6 +1097,7 @@ struct GraphsGpu {
     void free_dev(void *p) { (void)hipFree(p); }
     bool h2d(void *d, const void *h, size_t n) { return ready() && (e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)) == hipSuccess; }
     bool fill(void *d, int byte, size_t n) { return ready() && (e = hipMemsetAsync(d, byte, n, stream)) == hipSuccess; }
+    bool d2d(void *d, const void *s, size_t n) { return ready() && (n == 0 || (e = hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream)) == hipSuccess); }
     bool sync() { return e == hipSuccess && (e = hipStreamSynchronize(stream)) == hipSuccess; }
     bool read(void *h, const void *d, size_t n) {
         if (ready()) e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream);
@@ -1114,6 +1115,11 @@ struct GraphsGpu {
     bool launch(int kid, int64_t n_graphs, const SsspArgs &a) {
         if (!ready()) return false;
         launch_row(sssp_syms, kid, n_graphs, 0, stream, a);
+        return launched();
+    }
+    bool launch_ksw(int kid, int64_t n_graphs, const KswArgs &a) {
+        if (!ready()) return false;
+        launch_row(ksw_syms, kid, n_graphs, 0, stream, (int64_t)0, a);
         return launched();
     }
     int err() {
@@ -1218,6 +1224,16 @@ int aasm_sssp_dag_device(aasm_graphs *gb, const int32_t *src, int64_t *d5, int32
 }
 int aasm_sssp_dial_device(aasm_graphs *gb, const int32_t *src, int64_t *dist, int64_t *pre, int32_t *status, void *stream) {
     return graphs_call("aasm_sssp_dial_device", gb, stream, [&](GraphsGpu &be, const char **why) { return graphs_dial(be, *gb->core, src, dist, pre, status, why); });
+}
+
+// k shortest walks on a resident batch: the solve (returns when the sizes are final), and the export into the caller's device arrays
+int aasm_k_shortest_walks_device(aasm_graphs *gb, const int32_t *source, const int32_t *sink, int64_t k, int flags, void *stream, aasm_ksw_sizes *sz) {
+    return graphs_call("aasm_k_shortest_walks_device", gb, stream, [&](GraphsGpu &be, const char **why) {
+        return graphs_ksw(be, *gb->core, source, sink, k, flags, sz, why);
+    });
+}
+int aasm_ksw_export_device(aasm_graphs *gb, const aasm_ksw_sizes *sz, const aasm_ksw_dev_out *dst, void *stream) {
+    return graphs_call("aasm_ksw_export_device", gb, stream, [&](GraphsGpu &be, const char **why) { return graphs_ksw_export(be, *gb->core, sz, dst, why); });
 }
 
 // k shortest walks (k_shortest_walks.hpp:177-290, is_dag = true) over a batch of DAGs; host pointers in, library-allocated out

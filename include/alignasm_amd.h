@@ -370,6 +370,63 @@ int  aasm_k_shortest_walks(int64_t n_graphs, const int64_t *g_voff, const int64_
                            const int32_t *source, const int32_t *sink, int64_t k, int flags, int device, aasm_ksw_out *out);
 void aasm_ksw_free(aasm_ksw_out *out);
 
+/* k shortest walks on a resident graph batch (a handle that carries w5), results left on the device: a solve that returns sizes,
+ * then an export into DEVICE arrays the caller allocates from them - the pattern of aasm_result_sizes / aasm_result_export.
+ * `source` and `sink` are device arrays [n_graphs]; k and flags mean what they mean in aasm_k_shortest_walks, with every per-graph
+ * status and limit of it (AASM_KSW_HOOK_ARENA is refused as an unknown flag).
+ *
+ * The result is PACKED by n_found instead of padded to k, and nothing in either entry allocates or touches n_graphs * k words:
+ * found_off is the prefix sum of n_found, walk i of graph g is walk found_off[g] + i.  For the same graphs, sources, sinks, k and
+ * flags, n_found, heap_nodes, status, d5 and best are word for word aasm_k_shortest_walks'; dist5[(found_off[g] + i) * 5 ..] is its
+ * dist5[(g * k + i) * 5 ..] and walk found_off[g] + i holds the edge ids of its walk g * k + i, for i < n_found[g]; a graph it
+ * reports with empty walk ranges has empty ranges here.
+ *
+ * aasm_k_shortest_walks_device.  Checks before anything is enqueued: the pointers (as the other *_device entries), the batch's
+ * w5, 2^20 vertices and fewer than 2^31 edges per graph, k, the flags, and - without AASM_KSW_NEGATIVE - the batch's first edge
+ * with a negative score sum (aasm_k_shortest_walks' AASM_E_OVERFLOW and message).  Sources and sinks are checked by a kernel with a
+ * one-word verdict: "graph g: source outside it" / "graph g: sink outside it" (AASM_E_INVAL), the lowest g, its source first.
+ * The solve is NOT asynchronous: it returns when *sz is final.  Its host waits do not grow with the batch: the host reads the
+ * source / sink verdict, three totals after the tree stage (the arena, queue and result room: the per-graph bounds and the scans
+ * that place them are made by a kernel), two totals after the enumeration, and under AASM_KSW_CYCLES without AASM_KSW_NEGATIVE one
+ * word per round of heap room (1x, 4x, 16x: which graphs run again is decided on the device).  The whole batch is solved in one
+ * piece out of the handle's working memory (aasm_debug_poison covers it); its size, every array rounded up to 256 bytes:
+ *     80 B per vertex + 8 B per edge + 124 B per graph (+ 2 words)
+ *   + the larger of the tree stage's heap room  (48 B x: nothing in DAG mode; 2 * (E + 2) entries per graph with AASM_KSW_NEGATIVE;
+ *                with AASM_KSW_CYCLES alone E + 2 per graph, then 4, 16, 64 x (E + 2) for the graphs that run again)
+ *     and the enumeration's                     (48 B x sum of arena nodes + 56 B x sum of queue entries + 44 B x sum of walks[g]),
+ * where per graph with a walk arena nodes = ins * (floor(log2(ins + 1)) + 2) (ins: the sidetrack edges reachable from the sink's
+ * tree, <= E), queue entries = 3 * walks - 2, walks = min(k, number of walks) - so at most about 200 B x k per graph beside the
+ * arena.  While the block grows between the stages the old and the new one exist together.  If it cannot be had the call returns
+ * AASM_E_NOMEM; the handle stays usable and the caller splits the batch.
+ *
+ * aasm_ksw_export_device is asynchronous on `stream`: no host wait, no read-back, no allocation, no cell touched outside the
+ * stated lengths.  It may be called more than once for one solve.  AASM_E_INVAL with nothing enqueued: sz is not what the latest
+ * k-walk solve on this handle returned; a later call on the handle (any *_device entry, another k-walk solve) has reused the
+ * working memory the result lives in; an array that is not empty is NULL, not memory of the batch's device, or misaligned
+ * (walk_off / walk_edges are asked for only with AASM_KSW_WALKS, d5 / best only with AASM_KSW_TREE).  The handle's event ordering
+ * covers both entries: two streams may share a handle, and aasm_graphs_free waits for exports in flight. */
+typedef struct aasm_ksw_sizes {      /* filled by the solve, handed back unchanged to the export */
+    int64_t n_graphs, n_vertices, k;
+    int64_t n_walks;                 /* sum of n_found                                  */
+    int64_t n_walk_edges;            /* 0 without AASM_KSW_WALKS                        */
+    int32_t flags, reserved;
+    int64_t serial;                  /* which solve of this handle                      */
+} aasm_ksw_sizes;
+typedef struct aasm_ksw_dev_out {    /* DEVICE arrays, caller-owned */
+    int64_t *n_found;      /* [n_graphs]                                                */
+    int64_t *found_off;    /* [n_graphs + 1] prefix sums of n_found                     */
+    int64_t *dist5;        /* [n_walks * 5]  walk i of graph g at found_off[g] + i      */
+    int64_t *walk_off;     /* [n_walks + 1] into walk_edges; AASM_KSW_WALKS             */
+    int64_t *walk_edges;   /* [n_walk_edges] caller CSR positions, source -> sink       */
+    int64_t *d5;           /* [n_vertices * 5]; AASM_KSW_TREE                           */
+    int32_t *best;         /* [n_vertices];     AASM_KSW_TREE                           */
+    int64_t *heap_nodes;   /* [n_graphs]                                                */
+    int32_t *status;       /* [n_graphs]                                                */
+} aasm_ksw_dev_out;
+int  aasm_k_shortest_walks_device(aasm_graphs *gb, const int32_t *source, const int32_t *sink, int64_t k, int flags, void *stream,
+                                  aasm_ksw_sizes *sz);
+int  aasm_ksw_export_device(aasm_graphs *gb, const aasm_ksw_sizes *sz, const aasm_ksw_dev_out *dst, void *stream);
+
 /* Same, with the batch already resident in device memory (in->pointers are device
  * pointers; in->ctg_rec_off / rec_rng_off too).  `stream` is a hipStream_t (or NULL).
  * The device result stays resident in an opaque handle until fetched/freed.          */
