@@ -6,12 +6,15 @@ Loads the CHECKERS (never used by the product):
                                           built only where /root/reference exists, the
                                           prebuilt files travel to the GPU box)
   tests/host_emul/libaasm_emul.so         1-lane host build of the product's kernel bodies (its other families' libraries
-                                          and sanitizer programs are built where a test asks: build_emul)
+                                          and sanitizer programs are built where a test asks, once per process: build_emul)
 and the PRODUCT through alignasm_amd.api (libalignasm_amd.so, C-ABI).
 """
+import atexit
 import ctypes as C
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -41,16 +44,33 @@ def _ensure(path, make_dir):
     return path
 
 
-def build_emul(name, out_dir=EMUL_DIR, san=None):
-    """tests/host_emul's Makefile for lib<name>.so, and for the sanitizer program `san` beside it where one is named, into out_dir
-    -> the loaded library, or (library, path of the program)."""
-    targets = [os.path.join(str(out_dir), f) for f in (f"lib{name}.so", san) if f]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
-    return (lib, targets[1]) if san else lib
-
-
 _cache = {}
+_emul = {}                                                           # "dir", the targets built there, the libraries loaded from it
+
+
+def _emul_target(name):
+    """tests/host_emul's Makefile for one target, at most once per process, into a directory of this process's own (so nothing an
+    older commit built is ever picked up; removed at exit) -> the target's path."""
+    if "dir" not in _emul:
+        _emul["dir"] = tempfile.mkdtemp(prefix="aasm_emul_")
+        atexit.register(shutil.rmtree, _emul["dir"], ignore_errors=True)
+    path = os.path.join(_emul["dir"], name)
+    if path not in _emul:
+        subprocess.run(["make", "-s", "-C", EMUL_DIR, f"OUT={_emul['dir']}", path], check=True)
+        _emul[path] = True
+    return path
+
+
+def build_emul(family, san=False, declare=None):
+    """The host emulation of one kernel family (tests/host_emul/<family>_emul.cpp; "pipeline": emul.cpp) -> its loaded library, the
+    same object at every call; san: -> (library, path of the family's sanitizer program <family>_emul_san), which is built only where
+    it is asked for.  declare(lib) states the family's ctypes declarations, once, when the library is loaded."""
+    if family not in _emul:
+        lib = C.CDLL(_emul_target("libaasm_emul.so" if family == "pipeline" else f"libaasm_emul_{family}.so"))
+        if declare:
+            declare(lib)
+        _emul[family] = lib
+    return (_emul[family], _emul_target(family + "_emul_san")) if san else _emul[family]
 
 
 def oracle():
@@ -64,7 +84,7 @@ def oracle():
 
 def emul():
     if "e" not in _cache:
-        lib = C.CDLL(EMUL_SO) if os.path.exists(EMUL_SO) else build_emul("aasm_emul")
+        lib = C.CDLL(EMUL_SO) if os.path.exists(EMUL_SO) else build_emul("pipeline")
         lib.emul_debug_fetch.restype = C.c_int64
         lib.emul_last_bad_record.restype = C.c_int64
         lib.emul_launch_log.restype = C.c_int64

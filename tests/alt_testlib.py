@@ -1,8 +1,6 @@
 """Helpers of the tests of the --alt merge on the device (tests/test_alt_device_cpu.py, tests/test_gpu_alt_device.py): the host
 route that is the yardstick, the emulated merge, the I/O oracle's independent reading, the comparisons."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -11,21 +9,18 @@ import read_cols_testlib as XR
 import read_testlib as X
 from alignasm_amd._abi import BatchIn, RowCols
 
-EMUL_DIR = aasm_testlib.EMUL_DIR
-
-
-def build_emul(out_dir, san=True):
-    """tests/host_emul/alt_emul.cpp built by alt.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_alt.so",) + (("alt_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "alt.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
+def _declare(lib):
     lib.emalt_merge.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_double, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emalt_free.argtypes = [C.c_void_p]
     lib.emalt_host_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emalt_host_cols_free.argtypes = [C.c_void_p]
     lib.emalt_counter.restype = C.c_int64
     lib.aasm_last_error.restype = C.c_char_p
-    return lib, (targets[1] if san else None)
+
+
+def build_emul(san=False):
+    """tests/host_emul/alt_emul.cpp -> its library, or with san (library, path of alt_emul_san)."""
+    return aasm_testlib.build_emul("alt", san, _declare)
 
 
 def host_cols(lib, paf):

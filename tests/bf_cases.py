@@ -3,7 +3,6 @@ tests/test_gpu_bf.py, tests/golden/make_ref_bellman_ford.py): small graphs with 
 (tests/golden/ref_bellman_ford.npz), and the runs of the emulation, the product and the checker."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
@@ -14,7 +13,6 @@ from alignasm_amd._abi import AASM_KSW_CYCLES, AASM_KSW_NEGATIVE, bellman_ford_o
 
 ROOT = KC.ROOT
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_bellman_ford.npz")
-EMUL_DIR = os.path.join(ROOT, "tests", "host_emul")
 NEG = KC.ALL | AASM_KSW_NEGATIVE                 # the DAG mode with negative weights
 NEG_CYC = NEG | AASM_KSW_CYCLES                  # the tree of bellman_ford()
 E_INVAL, E_OVERFLOW = -1, -5
@@ -183,18 +181,7 @@ def first_walks(want, k):
     return None if want is None else CC.first_walks(want, k)
 
 
-# ---- runs --------------------------------------------------------------------------------------------------------------
-def build_emul(out_dir, san=True):
-    """tests/host_emul/bf_emul.cpp built by bf.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_bf.so",) + (("bf_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "bf.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
-    for fn in (lib.emk_k_shortest_walks, lib.emk_sssp_bellman_ford, lib.emk_sssp_dijkstra):
-        fn.restype = C.c_int
-    lib.emk_bf_queue_room.restype, lib.emk_bf_queue_room.argtypes = C.c_int64, [C.c_int64]
-    return lib, (targets[1] if san else None)
-
-
+# ---- runs (lib: the graph family's emulation library, KC.build_emul) -----------------------------------------------------
 def emul_bf(lib, batch, raw=None):
     """emk_sssp_bellman_ford on a batch -> (rc, {d, prev, status, cycles, qhigh}).  raw: replacements for the pointer arguments by
     name (None = NULL), for the argument checks."""

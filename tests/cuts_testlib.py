@@ -15,11 +15,13 @@ from alignasm_amd._abi import (AASM_CUT_E_EDIT, AASM_CUT_E_INS_CLIP, AASM_CUT_E_
 LISTS = ("main", "alt", "all")
 
 
-def build_emul(out_dir):
-    """tests/host_emul/cuts_emul.cpp built into out_dir -> (library, path of the sanitizer program)."""
-    lib, san = aasm_testlib.build_emul("aasm_emul_cuts", out_dir, san="cuts_emul_san")
+def _declare(lib):
     lib.emc_chunk.restype = C.c_int64
-    return lib, san
+
+
+def build_emul(san=False):
+    """tests/host_emul/cuts_emul.cpp -> its library, or with san (library, path of cuts_emul_san)."""
+    return aasm_testlib.build_emul("cuts", san, _declare)
 
 
 def golden_cs(T):

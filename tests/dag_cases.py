@@ -3,7 +3,6 @@ tests/golden/make_ref_dag.py): the case list - the smallest shapes at which the 
 recorded reference runs (tests/golden/ref_dag.npz), and the runs of the emulation, the product and the checker."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
@@ -14,7 +13,6 @@ from alignasm_amd._abi import dag_outputs, graph_inputs
 
 ROOT = KC.ROOT
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_dag.npz")
-EMUL_DIR = os.path.join(ROOT, "tests", "host_emul")
 E_INVAL, E_OVERFLOW = -1, -5
 HUB_DEGREES = (64, 65, 129, 200)
 LIM = 1 << 39
@@ -181,17 +179,7 @@ def golden_graphs():
     return _GOLD
 
 
-# ---- runs --------------------------------------------------------------------------------------------------------------
-def build_emul(out_dir, san=True):
-    """tests/host_emul/dag_emul.cpp built by dag.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_dag.so",) + (("dag_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "dag.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
-    for fn in (lib.emk_k_shortest_walks, lib.emk_topology_sort, lib.emk_sssp_dag):
-        fn.restype = C.c_int
-    return lib, (targets[1] if san else None)
-
-
+# ---- runs (lib: the graph family's emulation library, KC.build_emul) -----------------------------------------------------
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 

@@ -1,9 +1,7 @@
 """Shared pieces of the tests of resident graph batches (tests/test_graphs_resident_cpu.py, tests/test_gpu_graphs_resident.py): the
-emulation's build and runs (tests/host_emul/graphs_resident_emul.cpp), the single-defect batches, the seeded mutations, the sanitizer
-program's file format, and the host entries' answers in the resident entries' shape."""
+emulation's runs (the emr_* entries of tests/host_emul/graphs_emul.cpp, in KC.build_emul's library), the single-defect batches, the
+seeded mutations, the sanitizer program's file format, and the host entries' answers in the resident entries' shape."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -11,28 +9,9 @@ import ksw_cases as KC
 from alignasm_amd._abi import GraphsIn
 
 ROOT = KC.ROOT
-EMUL_DIR = os.path.join(ROOT, "tests", "host_emul")
 E_INVAL, E_OVERFLOW, E_INTERNAL = -1, -5, -6
 LIM = 1 << 39
 TYPES = {"g_voff": np.int64, "rowptr": np.int64, "col": np.int32, "w": np.int64, "cost": np.int32, "src": np.int32}
-
-
-def build_emul(out_dir, san=True):
-    """graphs_resident_emul.cpp built by graphs_resident.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_graphs_resident.so",) + (("graphs_resident_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "graphs_resident.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
-    lib.emr_last_error.restype = C.c_char_p
-    lib.emr_first_negative.restype = lib.emr_work_bytes.restype = C.c_int64
-    lib.emr_first_negative.argtypes = lib.emr_work_bytes.argtypes = lib.emr_graphs_free.argtypes = [C.c_void_p]
-    lib.emr_graphs_free.restype = None
-    for fn, n in ((lib.emr_host_check, 1), (lib.emr_graphs_make, None), (lib.emr_dijkstra, 4), (lib.emr_bellman_ford, 7), (lib.emr_topology_sort, 3),
-                  (lib.emr_dag, 6), (lib.emr_dial, 5), (lib.emk_sssp_dijkstra, None), (lib.emk_sssp_dial, None)):
-        fn.restype = C.c_int
-        if n:
-            fn.argtypes = [C.c_void_p] * n
-    lib.emr_graphs_make.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    return lib, (targets[1] if san else None)
 
 
 # ---- batches -----------------------------------------------------------------------------------------------------------

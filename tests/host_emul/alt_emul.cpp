@@ -136,23 +136,15 @@ void emalt_host_cols_free(void *handle) { delete (HostCols *)handle; }
 int64_t emalt_counter(int which) { return which == 0 ? g_verdicts : g_merges; }
 }
 
-#if defined(AASM_ALT_SAN_MAIN)
-static bool slurp(const char *path, std::vector<char> &data) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return false;
-    char buf[1 << 16];
-    size_t n;
-    while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + n);
-    std::fclose(f);
-    return true;
-}
+#if defined(AASM_EMUL_SAN_MAIN)
+#include "emul_san.h"
 // alt_emul_san MAIN ALT BASELINE ...: every triple through the emulated merge, under every combination of the two hooks, grids capped
 // at 3 blocks as well as free.  Prints one line per run: the alt file's name, the flags, the entry's code, merged records, reference
 // names, bytes of names.  The sanitizer ends the program at the first bad access, and reports a block nobody freed.
 int main(int argc, char **argv) {
     for (int i = 1; i + 2 < argc; i += 3) {
         std::vector<char> main_text, alt;
-        if (!slurp(argv[i], main_text) || !slurp(argv[i + 1], alt)) return 2;
+        if (!emul_san::read_bytes(argv[i], main_text) || !emul_san::read_bytes(argv[i + 1], alt)) return 2;
         const double baseline = std::atof(argv[i + 2]);
         aasm_paf *paf = nullptr;
         if (aasm_paf_parse_mem_opts(main_text.data(), (int64_t)main_text.size(), AASM_READ_DEVICE_RANGES, &paf) != AASM_OK) return 2;

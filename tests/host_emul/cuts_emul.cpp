@@ -42,20 +42,15 @@ int emc_cut_plans(const aasm_batch_in *in, const aasm_out_sizes *sz, const aasm_
 int64_t emc_chunk(void) { return AASM_CUT_CHUNK; }
 }
 
-#if defined(AASM_CUTS_SAN_MAIN)
+#if defined(AASM_EMUL_SAN_MAIN)
+#include "emul_san.h"
 // cuts_emul_san IN OUT, for a batch of one-record contigs with main elements only.  IN = int64 {R, NM, text bytes}, then qs[R],
 // qe[R], cs_off[R + 1], main_off[R + 1], the NM elements (40 bytes each), fwd[R] and the cs text; OUT = the NM plans.
 // Every record is planned on its own, from a private copy of its tag that ENDS where its heap block ends and starts at the
 // tag's own alignment inside an 8-byte word: the sanitizer ends the program at the first byte read behind a tag.
 int main(int argc, char **argv) {
-    if (argc != 3) return 2;
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
     std::vector<int64_t> raw;
-    int64_t word;
-    while (std::fread(&word, 8, 1, f) == 1) raw.push_back(word);    // (the file is padded to whole words)
-    std::fclose(f);
-    if (raw.size() < 3) return 2;
+    if (argc != 3 || !emul_san::read_words(argv[1], raw) || raw.size() < 3) return 2;
     const int64_t R = raw[0], NM = raw[1], TB = raw[2];
     const int64_t *qs = raw.data() + 3, *qe = qs + R, *cs_off = qe + R, *main_off = cs_off + R + 1;
     const aasm_out_elem *el = (const aasm_out_elem *)(main_off + R + 1);
@@ -66,7 +61,7 @@ int main(int argc, char **argv) {
     for (int64_t r = 0; r < R; r++) {
         const int64_t len = cs_off[r + 1] - cs_off[r], mis = cs_off[r] & 7, n = main_off[r + 1] - main_off[r];
         if (n == 0) continue;
-        char *block = (char *)std::malloc((size_t)(mis + len) + (mis + len == 0));
+        char *block = emul_san::block<char>(mis + len);
         std::memcpy(block + mis, text + cs_off[r], (size_t)len);
         const int64_t rec_off[2] = {0, 1}, off[2] = {0, n}, zero[2] = {0, 0}, one_cs[2] = {mis, mis + len};
         aasm_batch_in in;
@@ -82,10 +77,6 @@ int main(int argc, char **argv) {
         if (run(&in, &sz, &o, &d, 0) != AASM_OK) return 3;
         std::free(block);
     }
-    FILE *g = std::fopen(argv[2], "wb");
-    if (!g) return 2;
-    std::fwrite(plans.data(), sizeof(aasm_cut_plan), (size_t)NM, g);
-    std::fclose(g);
-    return 0;
+    return emul_san::write_bytes(argv[2], plans.data(), sizeof(aasm_cut_plan) * (size_t)NM) ? 0 : 2;
 }
 #endif

@@ -101,21 +101,16 @@ int64_t emrc_counter(int which) { return which == 0 ? g_slow_rows : g_fallbacks;
 int64_t emrc_pack_lanes(void) { return AASM_READ_PACK_LANES; }
 }
 
-#if defined(AASM_READ_COLS_SAN_MAIN)
+#if defined(AASM_EMUL_SAN_MAIN)
+#include "emul_san.h"
 // read_cols_emul_san FILE...: every file through the emulated reader with row columns, host text and "device" text, grids capped
 // at 3 blocks as well as free.  Prints one line per run: the file's name, the entry's code, rows, reference names, bytes of names.
 // The sanitizer ends the program at the first bad access, and reports a block nobody freed.
 int main(int argc, char **argv) {
     for (int i = 1; i < argc; i++) {
-        FILE *f = std::fopen(argv[i], "rb");
-        if (!f) return 2;
         std::vector<char> data;
-        char buf[1 << 16];
-        size_t n;
-        while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + n);
-        std::fclose(f);
-        char *text = (char *)std::malloc(data.size() ? data.size() : 1);   // (exactly the text: nothing readable behind it)
-        std::memcpy(text, data.data(), data.size());
+        if (!emul_san::read_bytes(argv[i], data)) return 2;
+        char *text = emul_san::exact<char>(data.data(), (int64_t)data.size());   // (exactly the text: nothing readable behind it)
         for (int64_t cap : {(int64_t)0, (int64_t)3})
             for (int device_text : {0, 1}) {
                 void *h = nullptr;

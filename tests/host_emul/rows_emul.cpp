@@ -116,7 +116,8 @@ int64_t emw_cut_fetches(int64_t *out, int64_t cap) {                 // -> the f
 int64_t emw_sample(void) { return AASM_ROWS_SAMPLE; }
 }
 
-#if defined(AASM_ROWS_SAN_MAIN)
+#if defined(AASM_EMUL_SAN_MAIN)
+#include "emul_san.h"
 // rows_emul_san IN OUT.  IN, in 8-byte words: {C, R, n_chr, NM, NA, NP, NE, names bytes, text bytes}, then per record qry_total,
 // qry_str, qry_end, ref_total, rec_cs_off[R + 1], ctg_rec_off[C + 1], ctg_name_off[C + 1], chr_name_off[n_chr + 1], main_off[C + 1],
 // alt_off[C + 1], all_path_off[C + 1], all_elem_off[NP + 1], the NM + NA + NE elements (40 bytes each), their plans (48 bytes
@@ -126,14 +127,8 @@ int64_t emw_sample(void) { return AASM_ROWS_SAMPLE; }
 // the tag ends and starts at the tag's own alignment inside an 8-byte word: the sanitizer ends the program at the first byte
 // read behind a tag or written outside the text.
 int main(int argc, char **argv) {
-    if (argc != 3) return 2;
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
     std::vector<int64_t> raw;
-    int64_t word;
-    while (std::fread(&word, 8, 1, f) == 1) raw.push_back(word);
-    std::fclose(f);
-    if (raw.size() < 9) return 2;
+    if (argc != 3 || !emul_san::read_words(argv[1], raw) || raw.size() < 9) return 2;
     const int64_t C = raw[0], R = raw[1], NCHR = raw[2], NM = raw[3], NA = raw[4], NP = raw[5], NE = raw[6], NB = raw[7], TB = raw[8];
     const int64_t *p = raw.data() + 9;
     auto take = [&](int64_t n) { const int64_t *q = p; p += n; return q; };
@@ -151,17 +146,15 @@ int main(int argc, char **argv) {
     std::vector<char *> blocks((size_t)R);
     for (int64_t r = 0; r < R; r++) {
         const int64_t len = cs_off[r + 1] - cs_off[r], mis = cs_off[r] & 7;
-        blocks[(size_t)r] = (char *)std::malloc((size_t)(mis + len) + (mis + len == 0));
+        blocks[(size_t)r] = emul_san::block<char>(mis + len);
         std::memcpy(blocks[(size_t)r] + mis, text + cs_off[r], (size_t)len);
     }
-    FILE *g = std::fopen(argv[2], "wb");
-    if (!g) return 2;
     // A table of R + 1 offsets cannot hold R unrelated blocks, so the batch is rebuilt with 2 R records: record 2 r is the real one,
     // its tag at [rec_cs_off[2 r], rec_cs_off[2 r + 1]) relative to the first block, record 2 r + 1 a spacer no element names.
     std::vector<int64_t> x_cs_off((size_t)(2 * R) + 1, 0), x_rec_off((size_t)C + 1), x_qtot((size_t)(2 * R)), x_qs((size_t)(2 * R)), x_qe((size_t)(2 * R)), x_rtot((size_t)(2 * R));
     std::vector<int32_t> x_chr((size_t)(2 * R)), x_mat((size_t)(2 * R)), x_aln((size_t)(2 * R)), x_idx((size_t)(2 * R));
     std::vector<uint8_t> x_fwd((size_t)(2 * R)), x_mq((size_t)(2 * R)), x_cord((size_t)(2 * R));
-    const char *origin = R ? blocks[0] : (const char *)&word;
+    const char *origin = R ? blocks[0] : "";
     for (int64_t r = 0; r < R; r++) {
         const int64_t len = cs_off[r + 1] - cs_off[r], mis = cs_off[r] & 7;
         x_cs_off[(size_t)(2 * r)] = (blocks[(size_t)r] + mis) - origin; x_cs_off[(size_t)(2 * r) + 1] = x_cs_off[(size_t)(2 * r)] + len;
@@ -190,23 +183,23 @@ int main(int argc, char **argv) {
     const aasm_dev_cuts d{(aasm_cut_plan *)pl, (aasm_cut_plan *)pl + NM, (aasm_cut_plan *)pl + NM + NA};
     const int64_t n[3] = {NM, NA, NE};
     int64_t *ro[3];
-    for (int l = 0; l < 3; l++) ro[l] = (int64_t *)std::malloc((size_t)(n[l] + 1) * 8);   // (exactly n + 1 offsets)
+    for (int l = 0; l < 3; l++) ro[l] = emul_san::block<int64_t>(n[l] + 1);               // (exactly n + 1 offsets)
     const aasm_dev_rows rows{ro[0], ro[1], ro[2]};
     aasm_rows_info info;
     if (sizes(&in, &cols, &sz, &o, &d, &rows, 0, &info) != AASM_OK) return 3;
     if (info.n_flagged != 0) return 4;
+    std::vector<char> lists;
     for (int l = 0; l < 3; l++) {
-        char *t = (char *)std::malloc((size_t)info.bytes[l] + (info.bytes[l] == 0));   // (exactly the list's bytes)
+        char *t = emul_san::block<char>(info.bytes[l]);              // (exactly the list's bytes)
         // in two ranges, so that a range's first byte is not the block's
         const int64_t mid = n[l] / 2;
         if (format(&in, &cols, &sz, &o, &d, &rows, &info, l, 0, mid, t, 0) != AASM_OK) return 5;
         if (format(&in, &cols, &sz, &o, &d, &rows, &info, l, mid, n[l], t + (ro[l][mid] - ro[l][0]), 3) != AASM_OK) return 5;
-        std::fwrite(t, 1, (size_t)info.bytes[l], g);
+        lists.insert(lists.end(), t, t + info.bytes[l]);
         std::free(t);
     }
-    std::fclose(g);
     for (int l = 0; l < 3; l++) std::free(ro[l]);
     for (char *b : blocks) std::free(b);
-    return 0;
+    return emul_san::write_bytes(argv[2], lists.data(), lists.size()) ? 0 : 2;
 }
 #endif

@@ -14,12 +14,29 @@ ALL = AASM_KSW_WALKS | AASM_KSW_TREE | AASM_KSW_HOOK_ARENA
 LIM = 1 << 39
 
 
-def build_emul(out_dir):
-    """The host emulation of the generic graph entries (tests/host_emul/graphs_emul.cpp): emk_k_shortest_walks, emk_sssp_dijkstra, emk_sssp_dial."""
-    lib = aasm_testlib.build_emul("aasm_emul_graphs", out_dir)
-    for fn in (lib.emk_k_shortest_walks, lib.emk_sssp_dijkstra, lib.emk_sssp_dial):
+def _declare(lib):
+    """The graph family's entries (tests/host_emul/graphs_emul.cpp): the host drivers emk_*, resident batches emr_*, k shortest walks on
+    them emw_*."""
+    for fn, n in ((lib.emk_k_shortest_walks, None), (lib.emk_sssp_dijkstra, None), (lib.emk_sssp_dial, None), (lib.emk_sssp_bellman_ford, None),
+                  (lib.emk_topology_sort, None), (lib.emk_sssp_dag, None), (lib.emr_host_check, 1), (lib.emr_dijkstra, 4), (lib.emr_bellman_ford, 7),
+                  (lib.emr_topology_sort, 3), (lib.emr_dag, 6), (lib.emr_dial, 5), (lib.emw_export, 3)):
         fn.restype = C.c_int
-    return lib
+        if n:
+            fn.argtypes = [C.c_void_p] * n
+    lib.emk_bf_queue_room.restype, lib.emk_bf_queue_room.argtypes = C.c_int64, [C.c_int64]
+    lib.emr_last_error.restype = C.c_char_p
+    lib.emr_first_negative.restype = lib.emr_work_bytes.restype = C.c_int64
+    lib.emr_first_negative.argtypes = lib.emr_work_bytes.argtypes = lib.emr_graphs_free.argtypes = [C.c_void_p]
+    lib.emr_graphs_free.restype = None
+    lib.emr_graphs_make.restype, lib.emr_graphs_make.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_void_p]
+    lib.emw_solve.restype, lib.emw_solve.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    lib.emw_read_bytes.restype = C.c_int64
+    lib.emw_alloc_limit.restype, lib.emw_alloc_limit.argtypes = None, [C.c_int64]
+
+
+def build_emul(san=False):
+    """The host emulation of the graph family -> its library, or with san (library, path of graphs_emul_san)."""
+    return aasm_testlib.build_emul("graphs", san, _declare)
 
 
 def emul_run(lib, batch, k, flags=ALL, budget=0):

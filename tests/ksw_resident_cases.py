@@ -1,8 +1,7 @@
 """Shared pieces of the tests of k shortest walks on a resident graph batch (tests/test_ksw_resident_cpu.py,
-tests/test_gpu_ksw_resident.py): the emulation's build and runs (tests/host_emul/ksw_resident_emul.cpp), the packed result unpacked
-into the host entry's layout, the small batches, the sanitizer program's file format."""
+tests/test_gpu_ksw_resident.py): the emulation's runs (the emw_* entries of tests/host_emul/graphs_emul.cpp, in KC.build_emul's
+library), the packed result unpacked into the host entry's layout, the small batches, the sanitizer program's file format."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -18,24 +17,6 @@ MODES = {"dag": 0, "cycles": AASM_KSW_CYCLES, "negative": AASM_KSW_CYCLES | AASM
 GUARD = 0x5EA15EA15EA15EA1                                           # sentinel words round every output array
 OUT_TYPES = {"n_found": np.int64, "found_off": np.int64, "dist5": np.int64, "walk_off": np.int64, "walk_edges": np.int64, "d5": np.int64,
              "best": np.int32, "heap_nodes": np.int64, "status": np.int32}
-
-
-def build_emul(out_dir, san=True):
-    """ksw_resident_emul.cpp built by ksw_resident.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_ksw_resident.so",) + (("ksw_resident_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", GR.EMUL_DIR, "-f", "ksw_resident.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
-    lib.emr_last_error.restype = C.c_char_p
-    lib.emr_work_bytes.restype, lib.emr_work_bytes.argtypes = C.c_int64, [C.c_void_p]
-    lib.emr_graphs_free.restype, lib.emr_graphs_free.argtypes = None, [C.c_void_p]
-    lib.emr_graphs_make.restype, lib.emr_graphs_make.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_void_p]
-    lib.emr_topology_sort.restype, lib.emr_topology_sort.argtypes = C.c_int, [C.c_void_p] * 3
-    lib.emw_solve.restype, lib.emw_solve.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    lib.emw_export.restype, lib.emw_export.argtypes = C.c_int, [C.c_void_p] * 3
-    lib.emw_read_bytes.restype = C.c_int64
-    lib.emw_alloc_limit.restype, lib.emw_alloc_limit.argtypes = None, [C.c_int64]
-    lib.emk_k_shortest_walks.restype = C.c_int
-    return lib, (targets[1] if san else None)
 
 
 def out_lengths(sz, flags):
@@ -169,14 +150,14 @@ def reversed_heap_retry_graph(m=10):
 
 # ---- the sanitizer program -------------------------------------------------------------------------------------------------
 def san_run(prog, tmp_path, b, k, flags, mode=0):
-    """-> (OUT words, stdout) of ksw_resident_emul_san on a batch (b["w"] None: a batch without w5)."""
+    """-> (OUT words, stdout) of graphs_emul_san ksw_resident on a batch (b["w"] None: a batch without w5)."""
     t = GR.typed(dict(b, w=None if b.get("w") is None else np.asarray(b["w"], np.int64).reshape(-1)))
     G = len(t["g_voff"]) - 1
     parts = [np.array([G, t["n_vertices"], t["n_edges"], t["w"] is not None, k, flags, mode], np.int64), t["g_voff"], t["rowptr"], t["col"].astype(np.int64)]
     parts += [] if t["w"] is None else [t["w"]]
     parts += [np.asarray(b["src"], np.int64), np.asarray(b["sink"], np.int64)]
     np.concatenate(parts).tofile(tmp_path / "in.bin")
-    r = subprocess.run([prog, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
+    r = subprocess.run([prog, "ksw_resident", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     return np.fromfile(tmp_path / "out.bin", np.int64), r.stdout
 

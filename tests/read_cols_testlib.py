@@ -1,8 +1,6 @@
 """Helpers of the tests of the device reader's resident row columns (tests/test_read_cols_cpu.py, tests/test_gpu_read_cols.py):
 the emulated reader with row columns, aasm_row_cols as numpy arrays (host or device memory), the yardstick's columns."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -10,21 +8,20 @@ import aasm_testlib
 import read_testlib as X
 from alignasm_amd._abi import BatchIn, RowCols
 
-EMUL_DIR = aasm_testlib.EMUL_DIR
 # per-record columns of aasm_row_cols
 ROW_KEYS = (("ref_total", np.int64), ("mat_num", np.int32), ("aln_len", np.int32), ("row_index", np.int32), ("cord_type", np.uint8))
 
 
-def build_emul(out_dir, san=True):
-    """tests/host_emul/read_cols_emul.cpp built by read_cols.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_read_cols.so",) + (("read_cols_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "read_cols.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
+def _declare(lib):
     lib.emrc_parse.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emrc_free.argtypes = [C.c_void_p]
     lib.emrc_counter.restype = lib.emrc_pack_lanes.restype = C.c_int64
     lib.aasm_last_error.restype = C.c_char_p
-    return lib, (targets[1] if san else None)
+
+
+def build_emul(san=False):
+    """tests/host_emul/read_cols_emul.cpp -> its library, or with san (library, path of read_cols_emul_san)."""
+    return aasm_testlib.build_emul("read_cols", san, _declare)
 
 
 def cols_arrays(cols: RowCols, n_contigs, n_records, fetch=X.host_fetch):

@@ -17,11 +17,7 @@ VIEW_ARRAYS = {
 }
 
 
-def build_emul(out_dir, san=True):
-    """tests/host_emul/read_emul.cpp built into out_dir -> (library, path of the sanitizer program); san = False: the library alone
-    (and None)."""
-    built = aasm_testlib.build_emul("aasm_emul_read", out_dir, san="read_emul_san" if san else None)
-    lib, prog = built if san else (built, None)
+def _declare(lib):
     lib.emr_parse_device.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emr_free.argtypes = [C.c_void_p]
     lib.emr_counter.restype = C.c_int64
@@ -31,7 +27,11 @@ def build_emul(out_dir, san=True):
     lib.aasm_paf_batch.argtypes = [C.c_void_p, C.c_void_p]
     lib.aasm_paf_to_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.aasm_paf_write_outputs.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
-    return lib, prog
+
+
+def build_emul(san=False):
+    """tests/host_emul/read_emul.cpp -> its library, or with san (library, path of read_emul_san)."""
+    return aasm_testlib.build_emul("read", san, _declare)
 
 
 def host_fetch(ptr, n, dtype):

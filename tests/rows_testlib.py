@@ -18,7 +18,6 @@ from alignasm_amd._abi import (AASM_CUT_IRREGULAR, AASM_CUT_IS_CUT, CUT_DT, OUT_
                                _np_from, render_cut)
 
 LISTS = X.LISTS
-EMUL_DIR = aasm_testlib.EMUL_DIR
 CHUNK = 128                                                          # AASM_ROWS_CHUNK (the emulation library reports it: emw_chunk)
 LEN_CHUNK = 2048                                                     # the length pass's chunk (emw_len_chunk)
 SAMPLE = 1024                                                        # AASM_ROWS_SAMPLE: the device writer's sampled row offsets (emw_sample)
@@ -28,15 +27,15 @@ COL_KEYS = (("ref_total", np.int64), ("mat_num", np.int32), ("aln_len", np.int32
             ("ctg_name_off", np.int64), ("chr_name_off", np.int64))
 
 
-def build_emul(out_dir, san=True):
-    """tests/host_emul/rows_emul.cpp built by rows.mk into out_dir -> (library, path of the sanitizer program or None)."""
-    targets = [os.path.join(str(out_dir), f) for f in ("libaasm_emul_rows.so",) + (("rows_emul_san",) if san else ())]
-    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "rows.mk", f"OUT={out_dir}"] + targets, check=True)
-    lib = C.CDLL(targets[0])
+def _declare(lib):
     lib.emw_chunk.restype = lib.emw_len_chunk.restype = C.c_int64
     lib.emw_cut_pieces.restype = lib.emw_cut_fetches.restype = lib.emw_sample.restype = C.c_int64
     assert lib.emw_chunk() == CHUNK and lib.emw_len_chunk() == LEN_CHUNK and lib.emw_sample() == SAMPLE
-    return lib, (targets[1] if san else None)
+
+
+def build_emul(san=False):
+    """tests/host_emul/rows_emul.cpp -> its library, or with san (library, path of rows_emul_san)."""
+    return aasm_testlib.build_emul("rows", san, _declare)
 
 
 # ---- the row layout, restated (the issue's contract; str() on Python ints) -------------------------------------------------------

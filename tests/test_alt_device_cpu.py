@@ -15,8 +15,8 @@ HOOKS = {"weak": _abi.AASM_READ_H_WEAK_HASH, "few": _abi.AASM_READ_H_FEW_BLOCKS,
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    return XA.build_emul(tmp_path_factory.mktemp("alt_emul"))
+def built():
+    return XA.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """CPU tier of aasm_sssp_bellman_ford and of aasm_k_shortest_walks with AASM_KSW_NEGATIVE: the kernels of alignasm_amd/csrc/aasm_sssp.h
-and aasm_ksw.h with their host drivers (1-lane host emulation, tests/host_emul/bf_emul.cpp) against the real reference's runs recorded
+and aasm_ksw.h with their host drivers (1-lane host emulation, tests/host_emul/graphs_emul.cpp) against the real reference's runs recorded
 in ref_bellman_ford.npz, against the plain-Python checker (tests/bf_checker.py) on graphs the file does not hold, and against a
 brute-force relaxation; the argument checks, the queue's room, the sanitizer program, and the refactored AASM_KSW_CYCLES tree kernel
 against its own recorded runs."""
@@ -21,8 +21,8 @@ N_RECORDED = 66
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    return BC.build_emul(tmp_path_factory.mktemp("emul_bf"))
+def built():
+    return KC.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")
@@ -218,7 +218,7 @@ def test_sanitizer_program_runs_clean_and_agrees(built, tmp_path):
     raw = np.concatenate([np.array(words, np.int64), b["g_voff"], b["rowptr"], b["col"].astype(np.int64), b["w"].reshape(-1).astype(np.int64),
                           b["src"].astype(np.int64), b["sink"].astype(np.int64)])
     raw.tofile(tmp_path / "in.bin")
-    r = subprocess.run([prog, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
+    r = subprocess.run([prog, "bf", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     out = np.fromfile(tmp_path / "out.bin", np.int64)
     rc, bf = BC.emul_bf(emk, b)

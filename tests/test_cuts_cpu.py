@@ -24,8 +24,28 @@ NEW_FUNCS = ("aasm_cut_plans_device", "aasm_writer_append_cuts")
 
 
 @pytest.fixture(scope="module")
-def emc(tmp_path_factory):
-    return X.build_emul(tmp_path_factory.mktemp("emul_cuts"))
+def emc():
+    return X.build_emul(san=True)
+
+
+# ---- 0. the build of the emulation: once per process, the sanitizer program only where asked ----------------------------------
+def test_build_emul_builds_once_and_no_program_unasked(T, emc, monkeypatch):
+    def refuse(*args, **kwargs):
+        raise AssertionError("build_emul started a process for a target this process has built: %r" % (args,))
+    with monkeypatch.context() as m:                                 # the fixture built library and program: no second make
+        m.setattr(T.subprocess, "run", refuse)
+        assert X.build_emul() is emc[0] and X.build_emul(san=True) == emc and T.build_emul("cuts") is emc[0]
+    assert os.path.dirname(emc[1]) == T._emul["dir"] and os.path.basename(emc[1]) == "cuts_emul_san"
+    # a process that never asks for a program builds none: a cache of its own, as a fresh process has it
+    monkeypatch.setattr(T, "_emul", {})
+    lib = T.build_emul("cuts")
+    try:
+        assert lib is not emc[0] and T._emul["dir"] != os.path.dirname(emc[1])
+        assert sorted(os.listdir(T._emul["dir"])) == ["libaasm_emul_cuts.so"]
+        monkeypatch.setattr(T.subprocess, "run", refuse)
+        assert T.build_emul("cuts") is lib
+    finally:
+        shutil.rmtree(T._emul["dir"])
 
 
 # ---- 1. the surface ---------------------------------------------------------------------------------------------------------

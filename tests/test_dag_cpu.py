@@ -1,5 +1,5 @@
 """CPU tier of aasm_topology_sort and aasm_sssp_dag: the kernel of alignasm_amd/csrc/aasm_sssp.h with its host driver (1-lane host
-emulation, tests/host_emul/dag_emul.cpp) against the real reference's runs recorded in ref_dag.npz, against the plain-Python checker
+emulation, tests/host_emul/graphs_emul.cpp) against the real reference's runs recorded in ref_dag.npz, against the plain-Python checker
 (tests/dag_checker.py) on graphs the file does not hold, and against the tree of aasm_k_shortest_walks on reversed graphs; the
 argument checks, the sanitizer program, and the surface.  The emulation walks a list one edge at a time: what a chunk of 64 edges
 does is proved on the card alone (tests/test_gpu_dag.py)."""
@@ -19,8 +19,8 @@ N_RECORDED = 73
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    return DC.build_emul(tmp_path_factory.mktemp("emul_dag"))
+def built():
+    return KC.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")
@@ -165,7 +165,7 @@ def test_sanitizer_program_runs_clean_and_agrees(built, tmp_path):
     raw = np.concatenate([np.array([len(gs), int(b["g_voff"][-1]), len(b["col"])], np.int64), b["g_voff"], b["rowptr"], b["col"].astype(np.int64),
                           b["w"].reshape(-1).astype(np.int64), b["src"].astype(np.int64)])
     raw.tofile(tmp_path / "in.bin")
-    r = subprocess.run([prog, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
+    r = subprocess.run([prog, "dag", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     out = np.fromfile(tmp_path / "out.bin", np.int64)
     rc, got = DC.emul_dag(emk, b)

@@ -96,8 +96,8 @@ def test_one_hip_runtime_per_process(order):
 
 # ---- the pack kernels, emulated, against fetch_results on the same workspace -------------------------------------------
 @pytest.fixture(scope="module")
-def emx(tmp_path_factory, T):
-    return T.build_emul("aasm_emul_export", tmp_path_factory.mktemp("emul_export"))
+def emx(T):
+    return T.build_emul("export")
 
 
 def _emulated_export_and_fetch(emx, T, hb, K, nsl=False, **hooks):

@@ -16,9 +16,9 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def emc(tmp_path_factory):
+def emc():
     """The emulated kernel, what the device plans of damaged tags are compared with."""
-    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_gpu"))[0]
+    return X.build_emul()
 
 
 @pytest.fixture(scope="module")

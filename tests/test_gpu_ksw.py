@@ -32,9 +32,9 @@ def test_gpu_equals_oracle_mixed_batch(T, K):
     assert KC.compare(b, gs, wants, got, K) == []
 
 
-def test_gpu_equals_emulation_bitwise(T, tmp_path):
+def test_gpu_equals_emulation_bitwise(T):
     api = T.api()
-    lib = KC.build_emul(tmp_path)
+    lib = KC.build_emul()
     b = KC.make_batch(KC.random_graphs(77, 150))
     rc, want = KC.emul_run(lib, b, 37)
     assert rc == 0

@@ -56,10 +56,10 @@ def test_gpu_equals_checker_mixed_batch(T, K):
         assert np.array_equal(got["hook_arena"][off[gi]:off[gi + 1]], _arena(w)), gi
 
 
-def test_gpu_equals_emulation_bitwise(T, tmp_path):
+def test_gpu_equals_emulation_bitwise(T):
     """All output arrays; the guards' graphs (tree guard, walk-edge cap) ride in the batch."""
     api = T.api()
-    lib = KC.build_emul(tmp_path)
+    lib = KC.build_emul()
     gs = CC.random_graphs(78, 148) + [CC.sink_improves()]
     ring = 8192
     gs.append(CC.from_edges(ring, [(i, (i + 1) % ring) for i in range(ring)], [1] * ring, 0, ring - 1))
@@ -106,10 +106,10 @@ def test_gpu_tree_equals_the_real_headers_dijkstra(T):
         assert np.array_equal(got["d"][vb:vb + n].reshape(-1), d) and np.array_equal(got["best"][vb:vb + n], prv), gi
 
 
-def test_gpu_default_mode_equals_emulation(T, tmp_path):
+def test_gpu_default_mode_equals_emulation(T):
     """The flag off: DAGs and a cycle among them, every output array equal to the emulation's."""
     api = T.api()
-    lib = KC.build_emul(tmp_path)
+    lib = KC.build_emul()
     gs = KC.random_graphs(91, 100)
     gs.insert(40, KC.cycle_graph())
     b = KC.make_batch(gs)

@@ -27,8 +27,8 @@ def torch():
 
 
 @pytest.fixture(scope="module")
-def emc(tmp_path_factory):
-    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_gpu_rows"))[0]
+def emc():
+    return X.build_emul()
 
 
 def hand_cases():

@@ -22,8 +22,8 @@ def torch():
 
 
 @pytest.fixture(scope="module")
-def emw(tmp_path_factory):
-    return W.build_emul(tmp_path_factory.mktemp("emul_rows_gpu"), san=False)[0]
+def emw():
+    return W.build_emul()
 
 
 def count_pieces(emw, off, limit):

@@ -1,4 +1,4 @@
-"""CPU tier of resident graph batches (alignasm_amd/csrc/aasm_graphs.h) in the host emulation (tests/host_emul/graphs_resident_emul.cpp):
+"""CPU tier of resident graph batches (alignasm_amd/csrc/aasm_graphs.h) in the host emulation (tests/host_emul/graphs_emul.cpp):
 the *_device drivers against the host entries' drivers on the existing case sets, through both creation paths; the check kernels
 against the host checks on single-defect batches and on seeded mutations; the sanitizer program on the case sets and on every hostile
 batch; what the product library answers without a device; the surface.  Every comparison is exact."""
@@ -21,8 +21,8 @@ import test_sssp_cpu as TS
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    return GR.build_emul(tmp_path_factory.mktemp("emul_graphs_resident"))
+def built():
+    return KC.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")
@@ -31,11 +31,8 @@ def emr(built):
 
 
 @pytest.fixture(scope="module")
-def host_call(tmp_path_factory, emr):
-    """The emulated HOST entries by name: dag_emul.cpp's, bf_emul.cpp's, graphs_emul.cpp's."""
-    dag = DC.build_emul(tmp_path_factory.mktemp("emul_dag_r"), san=False)[0]
-    bf = BC.build_emul(tmp_path_factory.mktemp("emul_bf_r"), san=False)[0]
-
+def host_call(emr):
+    """The emulated HOST entries by name: graphs_emul.cpp's emk_*."""
     def call(name, g_voff, rowptr, col, *rest):
         b = {"g_voff": g_voff, "rowptr": rowptr, "col": col}
         if name == "dijkstra":
@@ -45,13 +42,13 @@ def host_call(tmp_path_factory, emr):
             rc, dist, pre = TS.emul_dial(emr, g_voff, rowptr, col, rest[0], rest[1], rest[2])
             out = (dist, pre)
         elif name == "bellman_ford":
-            rc, r = BC.emul_bf(bf, dict(b, w=rest[0], src=rest[1]))
+            rc, r = BC.emul_bf(emr, dict(b, w=rest[0], src=rest[1]))
             out = (r["d"], r["prev"], r["status"], r["cycles"])
         elif name == "dag":
-            rc, r = DC.emul_dag(dag, dict(b, w=rest[0], src=rest[1]))
+            rc, r = DC.emul_dag(emr, dict(b, w=rest[0], src=rest[1]))
             out = (r["d"], r["prev"], r["status"], r["order"])
         else:
-            rc, r = DC.emul_topo(dag, b)
+            rc, r = DC.emul_topo(emr, b)
             out = (r["order"], r["status"])
         assert rc == 0, (name, rc)
         return out
@@ -187,7 +184,7 @@ def test_fuzz_single_mutations(emr):
 # ---- the sanitizer program -----------------------------------------------------------------------------------------------------------
 def _san(prog, tmp_path, b):
     GR.san_input(b, tmp_path / "in.bin")
-    r = subprocess.run([prog, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
+    r = subprocess.run([prog, "resident", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     return np.fromfile(tmp_path / "out.bin", np.int64), r.stdout
 

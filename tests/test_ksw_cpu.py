@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
-def emk(tmp_path_factory):
-    return KC.build_emul(tmp_path_factory.mktemp("emul_graphs"))
+def emk():
+    return KC.build_emul()
 
 
 def test_header_declares_the_entry_and_abi_stays_3(T):

@@ -18,8 +18,8 @@ ROOT = KC.ROOT
 
 
 @pytest.fixture(scope="module")
-def emk(tmp_path_factory):
-    return KC.build_emul(tmp_path_factory.mktemp("emul_graphs_cyc"))
+def emk():
+    return KC.build_emul()
 
 
 def _arena(want):

@@ -1,5 +1,5 @@
 """CPU tier of k shortest walks on a resident graph batch (alignasm_amd/csrc/aasm_graphs.h: graphs_ksw / graphs_ksw_export) in the host
-emulation (tests/host_emul/ksw_resident_emul.cpp): the resident driver against the emulated host driver (which existing tests pin to
+emulation (tests/host_emul/graphs_emul.cpp): the resident driver against the emulated host driver (which existing tests pin to
 the oracle and the reference's recorded runs) through both creation paths, for whole batches and for every graph alone; the heap
 retry chosen on the device; sizes and host read-backs that do not depend on k or on G; every refusal with code and message; guard
 words round every output; the sanitizer program; the surface.  Every comparison is exact."""
@@ -23,8 +23,8 @@ MAX_K = 1 << 24
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    return KR.build_emul(tmp_path_factory.mktemp("emul_ksw_resident"))
+def built():
+    return KC.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")

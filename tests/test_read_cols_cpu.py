@@ -23,13 +23,13 @@ NEW_FUNCS = ("aasm_paf_parse_device_rows", "aasm_paf_read_device_rows")
 
 
 @pytest.fixture(scope="module")
-def emrc(tmp_path_factory):
-    return XR.build_emul(tmp_path_factory.mktemp("emul_read_cols"))
+def emrc():
+    return XR.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")
-def rows_lib(tmp_path_factory):
-    return XW.build_emul(tmp_path_factory.mktemp("emul_rows_for_cols"), san=False)[0]
+def rows_lib():
+    return XW.build_emul()
 
 
 @pytest.fixture(scope="module")

@@ -19,8 +19,8 @@ NEW_FUNCS = ("aasm_paf_parse_device", "aasm_paf_read_device")
 
 
 @pytest.fixture(scope="module")
-def emr(tmp_path_factory):
-    return X.build_emul(tmp_path_factory.mktemp("emul_read"))
+def emr():
+    return X.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")

@@ -15,8 +15,8 @@ KINDS = ("fewer than 12 columns", "non-numeric field", "Missing cs:Z tag")
 
 
 @pytest.fixture(scope="module")
-def emr(tmp_path_factory):
-    return X.build_emul(tmp_path_factory.mktemp("emul_read_fuzz"), san=False)[0]
+def emr():
+    return X.build_emul()
 
 
 def host_verdict(api, text):

@@ -18,13 +18,13 @@ G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module")
-def emw(tmp_path_factory):
-    return W.build_emul(tmp_path_factory.mktemp("emul_rows"))
+def emw():
+    return W.build_emul(san=True)
 
 
 @pytest.fixture(scope="module")
-def emc(tmp_path_factory):
-    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_rows"))[0]
+def emc():
+    return X.build_emul()
 
 
 def _variants():

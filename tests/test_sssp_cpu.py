@@ -18,9 +18,9 @@ DIAL_WIN = 256
 
 
 @pytest.fixture(scope="module")
-def emk(tmp_path_factory):
+def emk():
     """tests/host_emul/graphs_emul.cpp, built on demand"""
-    return KC.build_emul(tmp_path_factory.mktemp("emul_graphs"))
+    return KC.build_emul()
 
 
 def _P(a):

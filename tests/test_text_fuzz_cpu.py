@@ -18,13 +18,13 @@ N_TEXTS = 36                                                         # x 2 (K, n
 
 
 @pytest.fixture(scope="module")
-def emc(tmp_path_factory):
-    return X.build_emul(tmp_path_factory.mktemp("emul_cuts_tf"))[0]
+def emc():
+    return X.build_emul()
 
 
 @pytest.fixture(scope="module")
-def emr(tmp_path_factory):
-    return XR.build_emul(tmp_path_factory.mktemp("emul_read_tf"), san=False)[0]
+def emr():
+    return XR.build_emul()
 
 
 def emul_k0_solve(T, view, K, nsl):
